@@ -7,9 +7,9 @@ kernel-matrix build -> blocked Cholesky (with y and the test point riding along)
 mean/variance at m=1 for each.  The metric stays GP fits/sec (= 40 x steps / time).  Inputs (the years' X, y, Xs)
 are resident in HBM before the timed region.
 
-N > 1 (one process per GPU, RCCL for the barrier / max-reduce only -- independent fits need no data-path collective; AFTER the
-metric the same ranks run BASELINE configs[3] / [4] as ONE fit sharded over all of them -- the library's own RCCL communicator,
-block-row panel broadcast -- and rank 0 adds the untimed "sharded" record to the line):
+N > 1 (one process per GPU, RCCL for the barrier / max-reduce only -- independent fits need no data-path collective; with --full,
+AFTER the metric the same ranks run BASELINE configs[3] / [4] as ONE fit sharded over all of them -- the library's own RCCL
+communicator, block-row panel broadcast -- and rank 0 adds the untimed "sharded" record to the line):
   --scaling weak   (default) every rank holds its own 40 years and runs the same number of steps: per-GPU work fixed
   --scaling strong the fixed job (steps x 40 fits) is dealt round-robin over the ranks (a rank's lockstep groups then mix
                    years and grid points)
@@ -19,9 +19,15 @@ abbreviations of ITS options even after the script name, e.g. --n / --d / --no: 
 form, or as a JSON list in SIGP_BENCH_ARGV with no flags on the command line; --gpus / --steps / --warmup are unaffected.)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid smoke|full] [--scaling weak|strong] [--n 8192] [--d 8]
+                    [--dump-outputs DIR] [--full]
 
-This file is the TIMED path and the line it prints; every untimed extra record (other configs, MLII, the reference kernel's grid and
-optimiser, the sharded fits, the CPU leg) lives in bench_extras.py and runs after the timed region.
+This file is the TIMED path and the line it prints.  A plain run sets up, warms up, times the K steps (no HIP-event brackets inside
+them), writes the last step's outputs if --dump-outputs is given, and prints the line.  --full adds what the headline does not need:
+the brackets of the dominant kernel inside the timed region and the roofline they give, and every untimed extra record (per-kernel
+table, other configs, MLII, the reference kernel's grid and optimiser, the sharded fits, the CPU leg), which lives in bench_extras.py
+and runs after the timed region; --no-profile / --no-extras / --no-cpu-baseline / --no-sharded drop single parts of it.
+--dump-outputs DIR writes what run_batch returned for (rank 0's) fits of the last timed step -- sigma_f, nlml, info, sigma_n, mean,
+var -- as DIR/<name>.npy in float64; the inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -136,13 +142,17 @@ def main():
     ap.add_argument("--outer", type=int, default=8, help="outer panel width in 128-column blocks (K of the trailing update = 128*outer)")
     ap.add_argument("--host-timing", action="store_true")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (repeatable)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0's fits) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true", help="also the event brackets + roofline, the untimed extra records, the CPU leg and (N > 1) the sharded record")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU leg")
     ap.add_argument("--cpu-reps", type=int, default=3, help="timed CPU repetitions at n=8192 after one warm-up (BASELINE.md section 2 protocol: 1 + 3, median; ~48 s each in the reference idiom); 1 = one cold fit")
-    ap.add_argument("--no-sharded", action="store_true", help="N > 1: skip the untimed sharded configs[3]/[4] record")
+    ap.add_argument("--no-sharded", action="store_true", help="--full, N > 1: skip the untimed sharded configs[3]/[4] record")
     ap.add_argument("--sharded-timeout", type=float, default=240.0, help="N > 1: seconds after which the line is printed without the sharded record")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event brackets")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra records (other configs, MLII, reference-kernel grid)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel HIP-event brackets")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the untimed extra records (other configs, MLII, reference-kernel grid)")
     args = ap.parse_args(json.loads(os.environ["SIGP_BENCH_ARGV"]) if len(sys.argv) == 1 and "SIGP_BENCH_ARGV" in os.environ else None)
+    if not args.full:                  # a plain run: the timed steps and the line only
+        args.no_profile = args.no_extras = args.no_cpu_baseline = args.no_sharded = True
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -254,6 +264,11 @@ def main():
     gp.profile(False)
     elapsed = t1 - t0
     assert np.all(r["info"] == 0) and np.all(np.isfinite(r["mean"]))
+    if args.dump_outputs and rank == 0:
+        last = fit_step[n_warm:] == total_steps - 1             # this rank's fits of the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in r.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), np.asarray(v[last], dtype=np.float64))
     import bench_extras as X_
     ctx = dict(gp=gp, args=args, rank=rank, world=world, W=W, K=K, ell=ell, sn=sn, Xb=Xb, yb=yb, my_years=my_years, d=d, sync=sync, barrier=barrier)
     unbracketed = X_.unbracketed_rerun(ctx) if (not args.no_profile and not args.no_extras) else None

@@ -270,6 +270,31 @@ def test_bench_falls_back_to_fewer_grid_points_when_hbm_is_short():
     assert len(p.stdout.strip().splitlines()[-1]) <= 1500
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_against_oracle(tmp_path):
+    """A plain ``bench.py --dump-outputs DIR`` (small n, so it takes seconds): --steps sets the timed steps, the line carries ms_per_step and no
+    --full record, and DIR holds what run_batch returned for the fits of the LAST timed step, float64, one .npy per array -- checked
+    against the oracle on the same seeded inputs."""
+    import bench
+    n, d, years, G, warm, steps = 1024, 8, 8, 16, 1, 2
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warm), "--n", str(n), "--d", str(d),
+                        "--years", str(years), "--group", str(G), "--dump-outputs", str(out)], capture_output=True, text=True, timeout=280, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["config"]["fits_per_step"] == G and line["ms_per_step"] > 0
+    assert abs(line["value"] - G / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["roofline"] is None and "cpu_baseline" not in line and "c1_ms" not in line
+    r = {k: np.load(out / (k + ".npy")) for k in ("sigma_f", "nlml", "info", "sigma_n", "mean", "var")}
+    assert all(v.dtype == np.float64 and v.shape[0] == G for v in r.values()) and np.all(r["info"] == 0)
+    for j in (0, 7, 8, G - 1):
+        i = (warm + steps - 1) * G + j                           # global fit index: data set i % years at grid point i // years
+        X, y, Xs = bench.synthetic_problem(n, d, 20240002 + i % years)
+        ell, sn = bench.grid_point(i // years, d, "smoke")
+        ref = O.fit_predict(X, y, Xs, ell, sn, kind="rbf", ref_idiom=False)
+        assert rel(r["mean"][j], ref["fmean"]) <= TOL_PRED and rel(r["var"][j], ref["fvar"]) <= TOL_PRED, j
+        assert rel(r["nlml"][j], ref["nlml"]) <= 1e-9 and rel(r["sigma_f"][j], ref["sigma_f"]) <= 1e-9, j
+
+
 def test_strip_solve_skipping_the_zero_tile_slices_is_bit_identical(S):
     """panel_strip_kernel multiplies a strip by [Mt_j0 .. Mt_jj]^T; Mt_jj = inv(L_jj) is lower triangular, and the `strip_tri` form
     (default) issues only the 16-column x 16-k tile-slices of that block that are not identically zero (its column tiles interleaved

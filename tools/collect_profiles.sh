@@ -1,20 +1,21 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): bench line, rocprofv3 kernel stats of the same command, and the PMC passes
 # (FETCH_SIZE / WRITE_SIZE in separate runs, as the MI355X guide prescribes).  Outputs under gpurun_out/<round>/.
-#   tools/collect_profiles.sh r03 bench     the default bench line (with the CPU protocol: ~5 min) + kernel stats of the same command
+#   tools/collect_profiles.sh r03 bench     the bench line with every record (bench.py --full, CPU protocol included: ~5 min) + kernel stats
 #   tools/collect_profiles.sh r03 pmc       PMC passes of the bench command (trailing update, covariance build)
 #   tools/collect_profiles.sh r03 f32       kernel stats + PMC passes of one fp32 fit at configs[4]'s shape (syrk128_kernel<float>)
 # then, back in the authoring container:  python tools/summarize_pmc.py r03
 R=${1:-r05}
 WHAT=${2:-bench}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$WHAT" = "bench" ]; then
-  python3 $GRAFT_REPO_ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench.err || exit 1       # stdout: the compact metric line; the full record:
+  python3 $ROOT/bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err || exit 1       # stdout: the compact metric line; the full record:
   cp $GRAFT_REPO_ROOT/gpurun_out/bench_verbose.json $OUT/bench.json                              # (bench.py writes it there and to stderr)
   echo "bench done"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
   echo "stats done"
 fi
 if [ "$WHAT" = "pmc" ]; then

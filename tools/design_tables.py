@@ -35,7 +35,7 @@ out = []
 A = out.append
 A("<!-- BEGIN GENERATED: tables (tools/design_tables.py %s) -->" % R)
 A("")
-A("**Headline** (`profiles/%s_bench_line_verbose.json`, the default `python bench.py`, CPU protocol included; compact form `profiles/%s_bench_line.json`):" % (R, R))
+A("**Headline** (`profiles/%s_bench_line_verbose.json`, `python bench.py --full`, CPU protocol included; compact form `profiles/%s_bench_line.json`):" % (R, R))
 A("")
 A("| quantity | value | source |")
 A("|---|---|---|")
