@@ -14,8 +14,8 @@ enum { KID_NETDIFFUSION = 0, KID_RBF = 1, KID_MATERN52 = 2,
 struct KParams {
   int kernel_id;
   int ds;           // data-set index of this batch member (X + ds*strideX, y + ds*stridey, Xs + ds*strideXs)
-  double c_rbf;     // -0.5 / ell^2
-  double inv_ell;   // 1 / ell
+  double c_rbf;     // -0.5 / ell^2, clamped at -DBL_MAX (make_kparams)
+  double inv_ell;   // 1 / ell, clamped at DBL_MAX
   double sn;        // sigma_n tilde (added on the diagonal)
 };
 
@@ -60,17 +60,21 @@ __device__ __forceinline__ double exp_cov_tab(double x, const double* tab) {
   return ldexp(t * p, ki >> 6);
 }
 
+// Total for every length scale: make_kparams keeps c_rbf and inv_ell finite (l -> 0: c_rbf * 0 stays 0 on the diagonal), the Matern
+// argument is bounded (the function rounds to 0 from s = 758 on; s^2 must not reach inf where exp(-s) is 0), and the RBF derivative is formed
+// from the clamped argument x = c_rbf |d|^2 (|d|^2 / l^2 = -2 x) instead of from inv_ell^2.
+constexpr double KS_MAX = 1e3;
 __device__ inline double cov_from_sq(const KParams& kp, double sq) {
   if (kp.kernel_id == KID_RBF) return exp_cov(kp.c_rbf * sq);
-  if (kp.kernel_id == KID_RBF_DLOGL) return exp_cov(kp.c_rbf * sq) * sq * (kp.inv_ell * kp.inv_ell);   // k * |d|^2 / l^2
-  const double s = sqrt(5.0 * sq) * kp.inv_ell;
+  if (kp.kernel_id == KID_RBF_DLOGL) { const double x = fmax(kp.c_rbf * sq, -746.0); return exp_cov(x) * (-2.0 * x); }   // k * |d|^2 / l^2
+  const double s = fmin(sqrt(5.0 * sq) * kp.inv_ell, KS_MAX);
   if (kp.kernel_id == KID_MATERN52_DLOGL) return (s * s * (1.0 / 3.0)) * (1.0 + s) * exp_cov(-s);
   return (1.0 + s + s * s * (1.0 / 3.0)) * exp_cov(-s);
 }
 __device__ inline double cov_from_sq_tab(const KParams& kp, double sq, const double* tab) {      // (the two covariance functions of a fit, table-driven exp)
   if (kp.kernel_id == KID_RBF) return exp_cov_tab(kp.c_rbf * sq, tab);
   if (kp.kernel_id == KID_MATERN52) {
-    const double s = sqrt(5.0 * sq) * kp.inv_ell;
+    const double s = fmin(sqrt(5.0 * sq) * kp.inv_ell, KS_MAX);
     return (1.0 + s + s * s * (1.0 / 3.0)) * exp_cov_tab(-s, tab);
   }
   return cov_from_sq(kp, sq);
@@ -198,9 +202,12 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const double* __restrict__ 
 // the kernel is left with its stores.  Wave w owns tile rows 16 w .. 16 w + 15 and all eight 16-column tiles; the column operand is fed
 // in the order sigma(i) = 4 (i mod 4) + i div 4, so that a lane's four accumulator registers (rows lq + 4 r of the MFMA result) are FOUR
 // CONSECUTIVE COLUMNS 4 lq .. 4 lq + 3 of matrix row lr: one 32-byte (fp64) / 16-byte (fp32) store per lane and tile, a whole 128-byte
-// line per matrix row and wave instruction.  Rounding: the Gram form loses relative accuracy for near-coincident points, not absolute:
-// |error(sq)| <~ 4 eps max(|x_i|^2, |x_j|^2), i.e. <= 1e-15 d in K~ at the synthetic workloads' scales (K~ tolerance 1e-13); the diagonal
-// is exact (sq = 0 by construction), sq is clamped at 0.
+// line per matrix row and wave instruction.  Rounding: the Gram form's error scales with the squared distance of the points from the
+// origin of the coordinates it is formed in, |error(sq)| <~ 4 eps max(|x_i - x_0|^2, |x_j - x_0|^2).  So every tile forms it relative to
+// a local origin x_0 = row 64 bi of its own row block, subtracted while the rows are staged (the squared norms are summed from the same
+// LDS images): the bound is then 4 eps (spread of the data)^2, whatever the features' offset (SST in kelvin, years), and the build is
+// translation-invariant -- exactly so when X and X + o are exact.  <= 1e-15 d in K~ at unit-variance features (K~ tolerance 1e-13); the
+// diagonal is exact (sq = 0 by construction), sq is clamped at 0.
 template <typename TO, int DC>
 __global__ __launch_bounds__(256) void kbuild_mfma_kernel(const double* __restrict__ X, long strideX, int dp, int d, int n,
                                                           TO* __restrict__ Mat, long strideM, long ld,
@@ -238,12 +245,8 @@ __global__ __launch_bounds__(256) void kbuild_mfma_kernel(const double* __restri
   __shared__ __attribute__((aligned(16))) double nI[KB_TM], nJ[KB_TN];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
   const int dq = (d + 3) & ~3;                                     // (X is zero-padded to dp >= dq features)
-  if (tid < KB_TM + KB_TN) {                                       // squared norms of the tile's rows, one thread per row
-    const double* xr = X + (long)(tid < KB_TM ? bi * KB_TM + tid : bj * KB_TN + tid - KB_TM) * dp;
-    double sacc = 0.0;
-    for (int p = 0; p < dq; p += 2) { const d2 v = *(const d2*)(xr + p); sacc = fma(v.x, v.x, sacc); sacc = fma(v.y, v.y, sacc); }
-    if (tid < KB_TM) nI[tid] = sacc; else nJ[tid - KB_TM] = sacc;
-  }
+  const double* x0 = X + (long)bi * KB_TM * dp;                    // the local origin (zero features stay zero: x0 is padded alike)
+  double sacc = 0.0;                                               // squared norm of staged row tid (tid < 192), from the LDS images
   d4 acc[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t)
@@ -252,12 +255,15 @@ __global__ __launch_bounds__(256) void kbuild_mfma_kernel(const double* __restri
   const int sig = 4 * (lr & 3) + (lr >> 2);                        // the column fed as MFMA row lr
   for (int p0 = 0; p0 < dq; p0 += DC) {
     const int pc = min(DC, dq - p0);                               // multiple of 4
+    const int h = pc >> 1, q = (tid % h) * 2, rstep = 256 / h;     // 16-byte pieces, lanes along the features of a row: a thread keeps its
+    const d2 o = *(const d2*)(x0 + p0 + q);                        // feature pair q (and its piece of x0) for every row it stages
     __syncthreads();
-    for (int idx = tid; idx < (KB_TM + KB_TN) * (pc >> 1); idx += 256) {      // 16-byte pieces, lanes along the features of a row
-      const int row = idx / (pc >> 1), q = (idx - row * (pc >> 1)) * 2;
-      const d2 v = *(const d2*)(X + (long)(row < KB_TM ? bi * KB_TM + row : bj * KB_TN + row - KB_TM) * dp + p0 + q);
-      double* dst = row < KB_TM ? Xi + row * LP + q : Xj + (row - KB_TM) * LP + q;
-      *(d2*)dst = v;
+    if (tid < rstep * h) {
+      for (int row = tid / h; row < KB_TM + KB_TN; row += rstep) {
+        const d2 v = *(const d2*)(X + (long)(row < KB_TM ? bi * KB_TM + row : bj * KB_TN + row - KB_TM) * dp + p0 + q);
+        double* dst = row < KB_TM ? Xi + row * LP + q : Xj + (row - KB_TM) * LP + q;
+        *(d2*)dst = v - o;
+      }
     }
     __syncthreads();
     const double* bI = Xi + (16 * wave + lr) * LP + lq;
@@ -267,7 +273,13 @@ __global__ __launch_bounds__(256) void kbuild_mfma_kernel(const double* __restri
 #pragma unroll
       for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aJ[16 * t * LP + kk], b, acc[t], 0, 0, 0);
     }
+    if (tid < KB_TM + KB_TN) {                                     // (the chunk stays in LDS until the next iteration's first barrier)
+      const double* xr = tid < KB_TM ? Xi + tid * LP : Xj + (tid - KB_TM) * LP;
+      for (int p = 0; p < pc; p += 2) { const d2 u = *(const d2*)(xr + p); sacc = fma(u.x, u.x, sacc); sacc = fma(u.y, u.y, sacc); }
+    }
   }
+  if (tid < KB_TM) nI[tid] = sacc; else if (tid < KB_TM + KB_TN) nJ[tid - KB_TM] = sacc;
+  __syncthreads();
   const int gi = bi * KB_TM + 16 * wave + lr;
   const double ni = nI[16 * wave + lr];
 #pragma unroll

@@ -549,8 +549,8 @@ int gemm_sub_auto(sigp_handle* h, hipStream_t st, GemmArgsT<T> g /* in 128-units
 KParams make_kparams(int kernel_id, double ell, double sn, int ds) {
   KParams kp;
   kp.kernel_id = kernel_id; kp.ds = ds;
-  kp.c_rbf = -0.5 / (ell * ell);
-  kp.inv_ell = 1.0 / ell;
+  kp.c_rbf = std::fmax(-0.5 / (ell * ell), -std::numeric_limits<double>::max());   // finite for every l > 0 (l^2 underflows below 1e-162): c_rbf * 0 = 0, not NaN
+  kp.inv_ell = std::fmin(1.0 / ell, std::numeric_limits<double>::max());
   kp.sn = sn;
   return kp;
 }
