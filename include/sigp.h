@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -199,6 +199,32 @@ int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const d
  * north/retrospective_forecasts/September1st_retro.py:176-248).  grad_mode 0 (value only; grad may be NULL) or 2.
  * nlml [count], grad [count][2]; a non-SPD member gets +inf in both (the reference's except branch :254-256). */
 int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int grad_mode, double* nlml, double* grad);
+
+/* Leave-one-out cross-validation with the hyper-parameters held (Rasmussen & Williams 5.4.2): what the block north/June1st.py:264-277
+ * returns for training point i when it is fitted on the other n - 1 points and asked to predict point i, for every i, from ONE
+ * factorisation:  g_i = [K~^-1]_ii,  mean_i = y_i - A~_i / g_i,  var_i = s_i / g_i (includes the noise, like fvar
+ * :273, :277) with s_i = (y^T A~ - A~_i^2 / g_i) / (n - 1) (SIGP_LOO_REFIT: sigma_f re-profiled without point i, :267-268 on n - 1 points)
+ * or s_i = sigma_f (SIGP_LOO_FIXED: R&W eq. 5.12);  score [2] = nlpd = sum_i log(2 pi var_i)/2 + (y_i - mean_i)^2 / (2 var_i)  and
+ * sse = sum_i (y_i - mean_i)^2, each added in a fixed order (the same bits on every run).  Cost on top of a fit: L~^-T (n^3/3 flops) and one
+ * pass over its triangle (4 n^2 bytes); no K~^-1.  Device work is accounted under SIGP_KC_MLII (two entries per call or lockstep group:
+ * the triangular inversion and the row pass).  n = 1 has no leave-one-out: SIGP_BAD_ARG.  fp64 engine only; after a sharded fit
+ * (sigp_dist_fit) or on an fp32 handle: SIGP_BAD_ARG.
+ * sigp_loo: after sigp_fit / sigp_fit_predict on this handle; mean [n], var [n], score [2].  The factor and the fit's state are only
+ * read: sigp_predict / sigp_get_alpha afterwards return what they returned before. */
+enum { SIGP_LOO_REFIT = 0, SIGP_LOO_FIXED = 1 };
+int sigp_loo(sigp_handle* h, int sigma_mode, double* mean, double* var, double* score);
+/* Lockstep groups (sigp_set_option "group") on the data sets resident after sigp_batch_upload, like sigp_nlml_grad_batch (RBF / Matern;
+ * any other kernel_id: SIGP_BAD_ARG -- the reference kernel's batch is sigp_small_run_loo): fit i uses data set (first + i) % batch with
+ * (ell[i], sn_tilde[i]); mean / var [count][nstride >= n] (both may be NULL: scores only), score [count][2].  A non-SPD member gets
+ * +inf scores and NaN rows (north/June1st.py:254-256); the other members are not affected. */
+int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde,
+                   int sigma_mode, double* mean, double* var, int64_t nstride, double* score);
+/* sigp_small_run with the leave-one-out cross-validation of every fit in the SAME single launch (L~^-1 formed in LDS over L~ as in
+ * sigp_small_run_grad): out6 [nprob][6] = sigma_f, nlML, info, sigma_n, nlpd, sse; mean / var as in sigp_small_run;
+ * loo_mean / loo_var [nprob][nstride >= largest n of the upload], entries beyond a set's n = NaN.  info > 0: nlpd = sse = +inf and NaN rows.
+ * A fit that names a data set of one point: SIGP_BAD_ARG. */
+int sigp_small_run_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode,
+                       double* out6, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride);
 
 /* One large fit sharded over the GPUs of a node (BASELINE configs[3] fp64, configs[4] fp32 + fp64 refinement): 1-D block-cyclic
  * ownership of outer panels (W column blocks of 128; panel q belongs to rank q % nranks), OWNER-ONLY storage -- a rank allocates,

@@ -13,6 +13,7 @@ OK, NOT_SPD, BAD_ARG, HIP_ERROR = 0, 1, 2, 3
 KERNEL_IDS = {"netdiffusion": 0, "rbf": 1, "matern52": 2}
 KCLASS = {"kbuild": 0, "diag": 1, "trsm": 2, "update_small": 3, "syrk128": 4, "epilogue": 5, "small": 6, "mlii": 7}
 MAX_RIDE = 127
+LOO_MODES = {"refit": 0, "fixed": 1}       # SIGP_LOO_REFIT / SIGP_LOO_FIXED
 
 _dp = C.POINTER(C.c_double)
 _i64 = C.c_int64
@@ -55,6 +56,9 @@ SIGNATURES = {
     "sigp_get_matrix": (C.c_int, [_h, C.c_int, _dp, _i64]),
     "sigp_nlml_grad": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _i64, C.c_int, C.POINTER(C.c_double), _dp]),
     "sigp_nlml_grad_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, C.c_int, _dp, _dp]),
+    "sigp_loo": (C.c_int, [_h, C.c_int, _dp, _dp, _dp]),
+    "sigp_loo_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _i64, _dp]),
+    "sigp_small_run_loo": (C.c_int, [_h, _i64, _ip64, _dp, _dp, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_dist_unique_id": (C.c_int, [C.c_void_p]),
     "sigp_dist_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),
     "sigp_dist_init_transport": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),

@@ -643,6 +643,63 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ Mx, l
   }
 }
 
+// Leave-one-out pass (Rasmussen & Williams 5.4.2) over U = L~^-T (upper triangular, row-major, as trtri_levels leaves it): one
+// WAVE per training point i like rowdot_kernel's kmode 2 -- row i from its diagonal on, 16-byte loads, entries left of the
+// diagonal and beyond column n never used (the pair that holds U_ii may bring U_i,i-1 along: selected away) -- summing in ONE
+// pass over the row
+//     g_i = [K~^-1]_ii = sum_{k >= i} U_ik^2          a_i = A~_i = sum_{k >= i} U_ik z_k      (z = L~^-1 y, the solved ride row)
+// and lane 0 closes the point:  mean_i = y_i - a_i / g_i,  var_i = s_i / g_i  with  s_i = (q - a_i^2 / g_i) / (n - 1)  (mode 0,
+// "refit": sigma_f re-profiled without point i) or  q / n  (mode 1, "fixed"),  q = y^T A~ = z.z read from *q (the fit's epilogue
+// left it on the device).  out [member][4][ldo]: mean, var, the point's nlpd term log(2 pi var)/2 + (y - mean)^2 / (2 var), its
+// squared error.  blockIdx.y = lockstep member (strides sU, sZ, sQ, sO; its y is data set kps[member].ds of stride sY).  No atomics: the terms are added by loo_sum_kernel.
+__global__ __launch_bounds__(256) void loo_rows_kernel(const double* __restrict__ U, long ld, int n, const double* __restrict__ z,
+                                                       const double* __restrict__ y, const double* __restrict__ q, int mode,
+                                                       double* __restrict__ out, long ldo, long sU = 0, long sZ = 0, long sY = 0,
+                                                       long sQ = 0, long sO = 0, const KParams* __restrict__ kps = nullptr) {
+  U += (long)blockIdx.y * sU; z += (long)blockIdx.y * sZ; y += (long)(kps ? kps[blockIdx.y].ds : (int)blockIdx.y) * sY; q += (long)blockIdx.y * sQ; out += (long)blockIdx.y * sO;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + wave;
+  if (i >= n) return;
+  const double* row = U + (long)i * ld;
+  double g = 0.0, a = 0.0;
+  for (int k0 = (i / 128) * 128; k0 < n; k0 += 128) {
+    const int k = k0 + lane * 2;
+    if (k >= n || k + 2 <= i) continue;
+    const d2 u = *(const d2*)(row + k);
+    const d2 zz = *(const d2*)(z + k);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const bool in = (k + e >= i) && (k + e < n);
+      const double ue = in ? u[e] : 0.0;
+      g = fma(ue, ue, g);
+      a = fma(ue, in ? zz[e] : 0.0, a);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { g += __shfl_down(g, off, 64); a += __shfl_down(a, off, 64); }
+  if (lane == 0) {
+    const double r = a / g;                                       // y_i - mean_i
+    const double s = mode == 0 ? (*q - a * r) / (double)(n - 1) : *q / (double)n;
+    const double v = s / g;
+    out[i] = y[i] - r;
+    out[ldo + i] = v;
+    out[2 * ldo + i] = 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
+    out[3 * ldo + i] = r * r;
+  }
+}
+// score [member][2] = nlpd, sse: the n terms loo_rows_kernel left in rows 2 and 3 of out, added in a fixed order (one block per member)
+__global__ __launch_bounds__(256) void loo_sum_kernel(const double* __restrict__ out, long ldo, long sO, int n, double* __restrict__ score) {
+  __shared__ double sh[4];
+  out += (long)blockIdx.x * sO;
+  double s2[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < n; i += 256) { s2[0] += out[2 * ldo + i]; s2[1] += out[3 * ldo + i]; }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const double v = block_reduce_sum(s2[c], sh);
+    if (threadIdx.x == 0) score[2 * blockIdx.x + c] = v;
+  }
+}
+
 // "column-dot":  Zout[r][j] -= sum_{k < K} Zin[r][k] * Mx[k*ld + j]   for the columns j < ncols (the rows of Mx are
 // contiguous in j).  A workgroup owns 16 x (16 B) consecutive columns and splits k over its 16 thread rows; the 16 partial
 // sums meet in LDS in a fixed order (deterministic).

@@ -115,6 +115,7 @@ struct sigp_handle {
   double* sm_dlam = nullptr; long cap_sm_dlam = 0; long sm_lam_len = 0; bool sm_has_dlam = false;   // lam_mode 1: derivative weights
   SmallProb* sm_probs = nullptr; long cap_sm_probs = 0;
   double* sm_out = nullptr; long cap_sm_out = 0;   // [nprob][4 + 2*mstride]
+  double* sm_loo_host = nullptr; long cap_sm_loo_host = 0;   // pinned [2][nprob][nstride]: the leave-one-out rows on their way to the caller
   int sm_ch = 32, sm_mmax = 0, sm_nmax = 0; long sm_lds = 0;
   int opt_small_nt64 = 0;                     // measurement switch: one wavefront per fit at orders <= 64
   // one large fit sharded over the GPUs of a node (sigp_dist_fit): this rank's block columns only
@@ -1234,7 +1235,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 500; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2
+int sigp_version(void) { return 510; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -1275,6 +1276,7 @@ int sigp_destroy(sigp_handle* h) {
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
   if (h->sm_probs) (void)hipFree(h->sm_probs);
+  if (h->sm_loo_host) (void)hipHostFree(h->sm_loo_host);
   if (h->pred_kps) (void)hipFree(h->pred_kps);
   if (h->gKps) (void)hipFree(h->gKps);
   if (h->kq) (void)hipFree(h->kq);
@@ -2182,6 +2184,108 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
       const double sf = out[0], Td = sums[(size_t)b * 4], Qd = sums[(size_t)b * 4 + 1], trKinv = sums[(size_t)b * 4 + 2], aa = sums[(size_t)b * 4 + 3];
       grad[2 * i] = 0.5 * Td - Qd / (2.0 * sf);                      // d/dlog l   of the profiled nlML
       grad[2 * i + 1] = snt[(size_t)b] * (0.5 * trKinv - aa / (2.0 * sf));   // d/dlog sn~
+    }
+  }
+  h->built = h->factored = h->fitted = false;
+  return SIGP_OK;
+}
+
+// ---- leave-one-out cross-validation (Rasmussen & Williams 5.4.2) ---------------------------------------------------
+// With (ell, sn~) held, all n leave-one-out predictions follow from the factor the fit left behind: U = L~^-T by
+// trtri_levels (n^3/3, as sigp_nlml_grad's first step; P parks in gK), then ONE pass over U's upper triangle
+// (loo_rows_kernel: g_i = [K~^-1]_ii and A~_i = (U z)_i per row, 4 n^2 bytes) and a fixed-order sum of the n score terms.
+// No U U^T, no dK~, no gD.  The factor, the ride rows and the fit's results are only read: sigp_predict / sigp_get_alpha
+// afterwards see what they saw before.  Profile class: SIGP_KC_MLII (trtri_levels and the row pass, one entry each).
+static int loo_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD,
+                      const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, int G) {
+  const long ld = n_pad;
+  const int T = (int)(n_pad / NB);
+  int rc;
+  {
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
+    if ((rc = trtri_levels<double>(h, st, Lm, ld, dinvp, h->gU, h->gK, ld, T, T, nb, sL, sD, n_pad * n_pad))) return rc;
+  }
+  {
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * 2.0 * n * n, nb * 4.0 * n * n);
+    hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4), (unsigned)nb), dim3(256), 0, st, (const double*)h->gU, ld, (int)n, Lm + n_pad * ld, y, q, mode,
+                       h->gPart, n_pad, n_pad * n_pad, sL, sY, sQ, 4 * n_pad, kps);
+    HIPCHK(h, hipGetLastError());
+  }
+  hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)h->gPart, n_pad, 4 * n_pad, (int)n, h->gPart + (long)G * 4 * n_pad);
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
+
+int sigp_loo(sigp_handle* h, int sigma_mode, double* mean, double* var, double* score) {
+  if (!h || !mean || !var || !score) return fail(h, SIGP_BAD_ARG, "loo: bad argument (mean [n], var [n], score [2] required)");
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "loo: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "loo: fp64 engine only (the fp32 engine keeps the inverses of its 2048-column diagonal blocks, not L~^-T)");
+  if (!h->fitted) return fail(h, SIGP_BAD_ARG, "loo: call sigp_fit / sigp_fit_predict first (a sharded fit leaves no single-GPU factor: sigp_loo does not apply)");
+  if (h->n < 2) return fail(h, SIGP_BAD_ARG, "loo: leave-one-out needs n >= 2 training points");
+  HIPCHK(h, hipSetDevice(h->device));
+  Slot& s = h->slots[0];
+  hipStream_t st = s.s_upd;
+  const long n = h->n, n_pad = h->n_pad;
+  int rc;
+  if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad + 4))) return rc;
+  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~ (host copy of the fit's epilogue: s.res may have moved on)
+  HIPCHK(h, hipMemcpyAsync(tail + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
+  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1))) return rc;
+  HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(score, tail, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  return sync_slot(h, s);
+}
+
+// The same for lockstep groups of RBF / Matern fits on the resident batch data: build, blocked Cholesky, epilogue (q stays on
+// the device in the slot's result rows), L~^-T for every member at once, the row pass with blockIdx.y = member.
+int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde, int sigma_mode,
+                   double* mean, double* var, int64_t nstride, double* score) {
+  if (!h || h->b_count == 0 || first < 0 || count < 1 || !ell || !sn_tilde || !score) return fail(h, SIGP_BAD_ARG, "loo_batch: bad argument (sigp_batch_upload first)");
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "loo_batch: fp64 engine only");
+  if (kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "loo_batch: RBF / MATERN52 only (the reference kernel's batch is sigp_small_run_loo)");
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "loo_batch: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if ((mean == nullptr) != (var == nullptr)) return fail(h, SIGP_BAD_ARG, "loo_batch: mean and var come together (both NULL: scores only)");
+  if (mean && nstride < h->b_n) return fail(h, SIGP_BAD_ARG, "loo_batch: mean / var [count][nstride >= %ld] required", h->b_n);
+  if (h->b_n < 2) return fail(h, SIGP_BAD_ARG, "loo_batch: leave-one-out needs n >= 2 training points");
+  for (int64_t i = 0; i < count; ++i)
+    if (!(ell[i] > 0) || !std::isfinite(ell[i]) || !(sn_tilde[i] >= 0) || !std::isfinite(sn_tilde[i])) return fail(h, SIGP_BAD_ARG, "loo_batch: finite ell > 0 and sn_tilde >= 0 required");
+  HIPCHK(h, hipSetDevice(h->device));
+  const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad;
+  const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
+  const double inf = std::numeric_limits<double>::infinity(), qnan = std::nan("");
+  Slot& s = h->slots[0];
+  hipStream_t st = s.s_upd;
+  int rc;
+  if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
+  if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4)))) return rc;
+  std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
+  for (long g0 = 0; g0 < count; g0 += G) {
+    const int nb = (int)std::min<long>(G, count - g0);
+    for (int b = 0; b < nb; ++b) s.kps_host[b] = make_kparams(kernel_id, ell[g0 + b], sn_tilde[g0 + b], (int)((first + g0 + b) % h->b_count));
+    if ((rc = upload_kparams(h, s, nb))) return rc;
+    if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
+    if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
+    if ((rc = epilogue_slot(h, s, nb, n, n_pad, 0))) return rc;
+    // y of member b is data set kps[b].ds = (first + g0 + b) % batch (the parameters uploaded above stay put until the next group's)
+    if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G))) return rc;
+    if (mean) HIPCHK(h, hipMemcpy2DAsync(mv.data(), (size_t)2 * n_pad * sizeof(double), h->gPart, (size_t)4 * n_pad * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(sc.data(), h->gPart + (long)G * 4 * n_pad, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = sync_slot(h, s))) return rc;
+    for (int b = 0; b < nb; ++b) {
+      const long i = g0 + b;
+      const bool ok = s.info_host[b] == 0;
+      score[2 * i] = ok ? sc[(size_t)2 * b] : inf;
+      score[2 * i + 1] = ok ? sc[(size_t)2 * b + 1] : inf;
+      if (!mean) continue;
+      for (long j = 0; j < n; ++j) {
+        mean[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + j] : qnan;
+        var[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + n_pad + j] : qnan;
+      }
     }
   }
   h->built = h->factored = h->fitted = false;

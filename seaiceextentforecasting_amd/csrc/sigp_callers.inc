@@ -58,20 +58,25 @@ int sigp_small_set_dweights(sigp_handle* h, const double* dlam_pool, int64_t cou
 }
 
 static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out,
-                          double* mean, double* var, int64_t mstride, bool grad) {
+                          double* mean, double* var, int64_t mstride, bool grad, int loo_mode = -1, double* loo_mean = nullptr,
+                          double* loo_var = nullptr, int64_t nstride = 0) {
   if (!h || h->sm_sets.empty()) return fail(h, SIGP_BAD_ARG, "small_run: call sigp_small_upload first");
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
+  const bool loo = loo_mode >= 0;
+  if (loo && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_loo: loo_mean / loo_var [nprob][nstride >= %d] required", h->sm_nmax);
   if (h->sm_mmax > 0 && (!mean || !var || mstride < h->sm_mmax)) return fail(h, SIGP_BAD_ARG, "small_run: mean / var [nprob][mstride >= %d] required", h->sm_mmax);
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<SmallProb> probs((size_t)nprob);
   for (int64_t i = 0; i < nprob; ++i) {
     if (set_index[i] < 0 || set_index[i] >= (int64_t)h->sm_sets.size()) return fail(h, SIGP_BAD_ARG, "small_run: fit %ld names data set %ld of %zu", (long)i, (long)set_index[i], h->sm_sets.size());
     if (!(sn_tilde[i] >= 0) || !std::isfinite(ell[i])) return fail(h, SIGP_BAD_ARG, "small_run: finite ell and sn_tilde >= 0 required");
+    if (loo && h->sm_sets[(size_t)set_index[i]].n < 2) return fail(h, SIGP_BAD_ARG, "small_run_loo: fit %ld names a data set of one point; leave-one-out needs n >= 2", (long)i);
     probs[(size_t)i] = SmallProb{(int)set_index[i], 0, ell[i], sn_tilde[i]};
   }
   const long ms = std::max<int64_t>(mstride, 1);
-  const long ow = grad ? 8 : 4;
-  const long per = ow + 2 * ms;
+  const long ns = loo ? (long)nstride : 0;
+  const long ow = grad ? 8 : loo ? 6 : 4;
+  const long per = ow + 2 * ms + 2 * ns;
   if (h->cap_sm_probs < nprob) {
     if (h->sm_probs) HIPCHK(h, hipFree(h->sm_probs));
     h->sm_probs = nullptr; h->cap_sm_probs = 0;
@@ -90,18 +95,28 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   double* d_out = h->sm_out;
   double* d_mean = h->sm_out + nprob * ow;
   double* d_var = d_mean + nprob * ms;
+  double* d_lmean = d_var + nprob * ms;        // [nprob][ns] each; NaN beyond a set's n (the memset above)
+  double* d_lvar = d_lmean + nprob * ns;
+  if (loo) {
+    static AttrOnce attr256l;
+    HIPCHK(h, attr256l.set(h->device, (const void*)smallgp_kernel<256, false, true>, 160 * 1024 - 64));
+  }
   {
     double fl = 0;
     for (const auto& pb : probs) {
       const SmallSet& s = h->sm_sets[(size_t)pb.set];
       fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n * (1 + s.m);
       if (grad) fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.N;      // X = L~^-1, X A, A^T a~
+      if (loo) fl += (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n;                                 // X = L~^-1, its column norms and X^T z
     }
     ProfScope ps(h, st, SIGP_KC_SMALL, fl, 0.0);
     // orders up to 64 (the reference's n <= 45): one wavefront per fit; larger: four
     // measured on the reference-size grid (48 000 fits, n = 6 .. 45): four wavefronts per fit 1.02 ms, one wavefront per fit 1.71 ms
     const double* d_dlam = h->sm_has_dlam ? h->sm_dlam : nullptr;
-    if (grad)
+    if (loo)
+      hipLaunchKernelGGL((smallgp_kernel<256, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y,
+                         h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode);
+    else if (grad)
       hipLaunchKernelGGL((smallgp_kernel<256, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y,
                          h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam);
     else if (h->sm_nmax <= 64 && h->opt_small_nt64)
@@ -118,7 +133,23 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
     HIPCHK(h, hipMemcpyAsync(mean, d_mean, (size_t)nprob * ms * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(var, d_var, (size_t)nprob * ms * sizeof(double), hipMemcpyDeviceToHost, st));
   }
+  if (loo) {
+    // tens of MB for a retro grid: through pinned memory of the handle's own (a pageable destination of that size makes the
+    // runtime pin and unpin the caller's pages: 25 ms around a 1 ms launch), then one host copy into the caller's arrays
+    const long tot = 2 * nprob * ns;
+    if (h->cap_sm_loo_host < tot) {
+      if (h->sm_loo_host) HIPCHK(h, hipHostFree(h->sm_loo_host));
+      h->sm_loo_host = nullptr; h->cap_sm_loo_host = 0;
+      HIPCHK(h, hipHostMalloc((void**)&h->sm_loo_host, (size_t)tot * sizeof(double)));
+      h->cap_sm_loo_host = tot;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->sm_loo_host, d_lmean, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(h, hipStreamSynchronize(st));
+  if (loo) {
+    memcpy(loo_mean, h->sm_loo_host, (size_t)nprob * ns * sizeof(double));
+    memcpy(loo_var, h->sm_loo_host + nprob * ns, (size_t)nprob * ns * sizeof(double));
+  }
   return SIGP_OK;
 }
 
@@ -130,6 +161,13 @@ int sigp_small_run(sigp_handle* h, int64_t nprob, const int64_t* set_index, cons
 int sigp_small_run_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out8,
                         double* mean, double* var, int64_t mstride) {
   return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, true);
+}
+
+// sigp_small_run with the leave-one-out cross-validation of every fit in the same single launch (smallgp_kernel<256, false, true>)
+int sigp_small_run_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode,
+                       double* out6, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_loo: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, loo_mean, loo_var, nstride);
 }
 
 // ---- ComplexNetworks tau(): cell-to-cell correlation matrix + thresholded mean (ComplexNetworks.py:31-47) ------------

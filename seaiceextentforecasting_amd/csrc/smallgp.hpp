@@ -73,13 +73,20 @@ __device__ inline double smallgp_allsum(double v, double* sh) {
 // barrier of the column loop a wave-local no-op) is kept as a measurement switch ("small_nt64") -- on the reference-size grid it
 // is SLOWER (1.71 vs 1.02 ms for 48 000 fits of n = 6 .. 45): the rank-1 updates have ~n^2/2 elements, enough for four waves,
 // and one resident wave per fit leaves the LDS pipeline idle between dependent steps.
-template <int NT, bool GRAD = false>
+// LOO = true (OW = 6; never together with GRAD): leave-one-out cross-validation of the fit (Rasmussen & Williams 5.4.2) from the same
+// in-LDS X = L~^-1 and a~:  g_i = [K~^-1]_ii = sum_{k >= i} X(k,i)^2,  loo_mean_i = y_i - a~_i / g_i,  loo_var_i = s_i / g_i with
+// s_i = (zz - a~_i^2 / g_i) / (n - 1) (loo_fixed = 0: sigma_f re-profiled without point i, what a refit on the other n - 1 points
+// returns) or sigma_f (loo_fixed = 1);  out[4] = nlpd = sum_i log(2 pi var_i)/2 + (y_i - mean_i)^2 / (2 var_i),  out[5] = sse;
+// loo_mean / loo_var [nprob][nstride].  A non-SPD K~ gives +inf in both scores (the rows stay as the caller initialised them).
+template <int NT, bool GRAD = false, bool LOO = false>
 __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict__ sets, const SmallProb* __restrict__ probs,
                                                       const double* __restrict__ Apool, const double* __restrict__ ypool,
                                                       const double* __restrict__ lampool, int ch, double* __restrict__ out,
                                                       double* __restrict__ mean, double* __restrict__ var, int mstride,
-                                                      const double* __restrict__ dlampool) {
-  constexpr int OW = GRAD ? 8 : 4;
+                                                      const double* __restrict__ dlampool, double* __restrict__ loo_mean = nullptr,
+                                                      double* __restrict__ loo_var = nullptr, int nstride = 0, int loo_fixed = 0) {
+  static_assert(!(GRAD && LOO), "one launch forms the MLII gradients or the leave-one-out predictions");
+  constexpr int OW = GRAD ? 8 : LOO ? 6 : 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const SmallProb pb = probs[blockIdx.x];
   const SmallSet st = sets[pb.set];
@@ -179,6 +186,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     } else {
       o[0] = inf; o[1] = inf; o[2] = (double)info; o[3] = inf;
       if (GRAD) { o[4] = inf; o[5] = inf; o[6] = inf; o[7] = inf; }     // north/June1st.py:254-256
+      if (LOO) { o[4] = inf; o[5] = inf; }
     }
   }
   for (int j = 0; j < m; ++j) {
@@ -193,7 +201,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     }
   }
 
-  if constexpr (GRAD) {
+  if constexpr (GRAD || LOO) {
     if (info != 0) return;           // uniform
     double* at = red + 16;           // [n] a~ = L~^-T z
     // ---- X = L~^-1 in place, row by row: X(i,j) = -X(i,i) sum_{k=j}^{i-1} L(i,k) X(k,j); rows above i are complete, row i of L~ is
@@ -221,6 +229,24 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
       }
       if (tid == 0) Kp[i * ldk + i] = xii;
       __syncthreads();
+    }
+    if constexpr (LOO) {
+      // column i of X: a~_i and g_i in one walk (odd pitch: the lanes' columns fall in different banks)
+      double tn = 0.0, ts = 0.0;
+      for (int i = tid; i < n; i += NT) {
+        double a = 0.0, g = 0.0;
+        for (int k = i; k < n; ++k) { const double x = Kp[k * ldk + i]; a = fma(x, z[k], a); g = fma(x, x, g); }
+        const double r = a / g;                                    // y_i - loo_mean_i
+        const double v = (loo_fixed ? sf : (zz - a * r) / (double)(n - 1)) / g;
+        loo_mean[(long)blockIdx.x * nstride + i] = ypool[st.y_off + i] - r;
+        loo_var[(long)blockIdx.x * nstride + i] = v;
+        tn += 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
+        ts = fma(r, r, ts);
+      }
+      const double nlpd = smallgp_allsum<NT>(tn, red);
+      const double sse = smallgp_allsum<NT>(ts, red);
+      if (tid == 0) { out[(long)blockIdx.x * OW + 4] = nlpd; out[(long)blockIdx.x * OW + 5] = sse; }
+      return;
     }
     for (int i = tid; i < n; i += NT) {
       double a = 0.0;

@@ -186,6 +186,77 @@ class GPR:
         self._check(self._lib.sigp_predict(self._h, L.ptr(Xs), m, Xs.shape[1], L.ptr(mean), L.ptr(var)), "predict")
         return mean, var
 
+    # ---- leave-one-out cross-validation ----------------------------------------------------------
+    def loo(self, sigma_f="refit"):
+        """Leave-one-out cross-validation of the current fit with (l, sn~) (and, for the reference kernel, M and the feature
+        columns) held: what ``fit`` on the other n - 1 points followed by ``predict`` of the left-out point returns, for every
+        point, from the factor already on the device (``sigp_loo``: L~^-T and one pass over it; about the price of a second fit).
+
+        sigma_f='refit'  the signal variance is re-profiled without the left-out point (north/June1st.py:267-268 on n - 1 points):
+                         identical to n real refits;
+        sigma_f='fixed'  the full fit's sigma_f is kept (Rasmussen & Williams eq. 5.12).  The means do not depend on the mode.
+
+        Returns dict(mean [n], var [n] (includes the noise, like fvar), nlpd, sse, mse, skill) with
+        skill = 1 - sse / sum((y - mean(y))^2).  The fit stays as it is: ``predict`` afterwards works unchanged."""
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if not self._fitted:
+            raise RuntimeError("loo: call fit() first")
+        mean, var, score = np.zeros(self.n), np.zeros(self.n), np.zeros(2)
+        self._check(self._lib.sigp_loo(self._h, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), L.ptr(score)), "loo")
+        nlpd, sse = float(score[0]), float(score[1])
+        return dict(mean=mean, var=var, nlpd=nlpd, sse=sse, mse=sse / self.n, skill=1.0 - sse / float(np.sum((self._y - self._y.mean()) ** 2)))
+
+    def loo_batch(self, ell, sn_tilde, first=0, sigma_f="refit", group=8, predictions=True):
+        """``loo`` for many (data set, l, sn~) on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern), in
+        lockstep groups of ``group`` fits (``sigp_loo_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F])
+        and, with ``predictions``, mean [F, n], var [F, n]; a non-SPD member gets +inf / NaN (north/June1st.py:254-256)."""
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if self.kernel == "netdiffusion":
+            raise ValueError("loo_batch covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(loo=...)")
+        ell = L.f64(np.atleast_1d(ell), 1)
+        sn = L.f64(np.atleast_1d(sn_tilde), 1)
+        F = len(ell)
+        if len(sn) != F:
+            raise ValueError("ell and sn_tilde must have the same length")
+        n = getattr(self, "_batch_n", None)
+        if n is None:
+            raise RuntimeError("loo_batch: stage the data sets with upload_batch() first")
+        self.set_option("group", group)
+        score = np.zeros((F, 2))
+        mean = np.zeros((F, n)) if predictions else None
+        var = np.zeros((F, n)) if predictions else None
+        self._check(self._lib.sigp_loo_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                             L.ptr(score)), "loo_batch")
+        self._fitted = False
+        res = dict(nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
+        if predictions:
+            res["mean"], res["var"] = mean, var
+        return res
+
+    def loo_grid(self, X, y, ells, sns, sigma_f="refit", group=8, M=None):
+        """The leave-one-out scores on the (l, sn~) grid for one data set, shaped like ``nlml_grid``: dict(nlpd, sse), each
+        [len(ells), len(sns)], +inf where K~ is not SPD.  Reference kernel (n <= 128): one launch, one workgroup per grid point."""
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        ells = np.asarray(ells, dtype=np.float64).reshape(-1)
+        sns = np.asarray(sns, dtype=np.float64).reshape(-1)
+        E, S = np.meshgrid(ells, sns, indexing="ij")
+        if self.kernel == "netdiffusion":
+            from .smallbatch import SmallBatch
+            sb = SmallBatch(self)
+            ds = sb.add_dataset(X, y, None, M)
+            for e, s_ in zip(E.reshape(-1), S.reshape(-1)):
+                sb.add_fit(ds, e, s_, expm=self._expm)
+            r = sb.run(loo=sigma_f)
+            nlpd, sse = r["loo_nlpd"], r["loo_sse"]
+        else:
+            self.upload_batch(L.f64(X, 2), y, None, group=group)
+            r = self.loo_batch(E.reshape(-1), S.reshape(-1), sigma_f=sigma_f, group=group, predictions=False)
+            nlpd, sse = r["nlpd"], r["sse"]
+        return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
+
     # ---- MLII (north/June1st.py:235-257) -------------------------------------------------------
     def nlml(self, theta, grad="ref"):
         """``MLII(hyperparameters)``: theta = (log l, log sn~) -> (nlML, grad[2]).
@@ -338,7 +409,7 @@ class GPR:
         if len(sn) != F:
             raise ValueError("ell and sn_tilde must have the same length")
         self._check(self._lib.sigp_batch_upload(self._h, B, L.ptr(Xb), n * d, L.ptr(yb), n, L.ptr(Xsb), m * d, n, d, m), "batch_upload")
-        self._batch_m = m
+        self._batch_m, self._batch_n = m, n
         return self.run_batch(0, F, ell, sn, concurrency, group)
 
     def predict_batch(self, X, y, Xs, ell, sn_tilde, **kw):
@@ -427,7 +498,7 @@ class GPR:
             Xsb = Xsb[None] if Xsb.ndim == 2 else Xsb
             m = Xsb.shape[1]
         self._check(self._lib.sigp_batch_upload(self._h, B, L.ptr(Xb), n * d, L.ptr(yb), n, L.ptr(Xsb), m * d, n, d, m), "batch_upload")
-        self._batch_m = m
+        self._batch_m, self._batch_n = m, n
         self._check(self._lib.sigp_batch_reserve(self._h, int(group), int(concurrency)), "batch_reserve")
 
     def run_batch(self, first, count, ell, sn_tilde, concurrency=2, group=8):

@@ -82,11 +82,23 @@ def retro_forecast(script, SIC, SIEs_dt, SIEs_trend, fmin, fmax, SST=None, gp=No
             gp.close()
 
 
-def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sns=SGRID, gp=None):
+_CRITERIA = {"nlml": (None, "nlml"), "loo_nlpd": ("refit", "loo_nlpd"), "loo_sse": ("refit", "loo_sse")}
+
+
+def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sns=SGRID, gp=None, criterion="nlml"):
     """The hyper-parameter search the reference's tables imply (north/June1st.py:210-211: indices into
     ``logspace(-7,2,20) x logspace(-3,9,20)``): nlML (north/June1st.py:246) of every (region, year) of the retro loop at
     every grid point -- 3 x years x 400 fits in one device launch, one eigendecomposition of M per (region, year).
-    Returns {region: nlml [n_years, len(ells), len(sns)]} (+inf where K~ is not positive definite)."""
+    Returns {region: nlml [n_years, len(ells), len(sns)]} (+inf where K~ is not positive definite).
+
+    ``criterion`` = "nlml" (default: the marginal likelihood, as above), "loo_nlpd" or "loo_sse": the same dict with the
+    leave-one-out negative log predictive density / sum of squared errors of every fit instead (to be minimised like nlML;
+    ``SmallBatch.run(loo="refit")``, still one launch).  What this leave-one-out holds fixed: the selected features, their
+    standardisation and M are those of the FULL training set of the (region, year); only the GP -- with (l, sn~) held and
+    sigma_f re-profiled -- is cross-validated.  Features are not re-selected per left-out year."""
+    if criterion not in _CRITERIA:
+        raise ValueError("criterion must be one of %s" % sorted(_CRITERIA))
+    loo, key = _CRITERIA[criterion]
     tab = SCRIPT_TABLE[script]
     own = gp is None
     gp = gp or GPR(kernel="netdiffusion")
@@ -102,7 +114,7 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
                 for e in ells:
                     for s_ in sns:
                         sb.add_fit(ds, e, s_, expm="eigh")
-        nl = sb.run()["nlml"].reshape(len(tab["regions"]), ny, len(ells), len(sns))
+        nl = (sb.run() if loo is None else sb.run(loo=loo))[key].reshape(len(tab["regions"]), ny, len(ells), len(sns))
         return {region: nl[k] for k, region in enumerate(tab["regions"])}
     finally:
         if own:

@@ -124,10 +124,20 @@ class SmallBatch:
         self._fits = []
         self._packed = None
 
-    def run(self, grad=False):
+    def run(self, grad=False, loo=None):
         """All queued fits in one launch -> dict(sigma_f, nlml, info, sigma_n, mean [F, mmax], var [F, mmax]); with ``grad=True``
         also grad_ref [F, 2] (the reference's MLII formulae, north/June1st.py:248-252) and grad_exact [F, 2] (the derivative of the
-        profiled nlML w.r.t. (log l, log sn~)); +inf where K~ is not positive definite (:254-256)."""
+        profiled nlML w.r.t. (log l, log sn~)); +inf where K~ is not positive definite (:254-256).
+
+        ``loo="refit"`` / ``"fixed"``: the same single launch also cross-validates every fit leave-one-out with (l, sn~) held
+        (``sigp_small_run_loo``; "refit" re-profiles sigma_f without the left-out point -- what a fit on the other n - 1 points
+        returns --, "fixed" keeps the full fit's sigma_f): loo_mean, loo_var [F, nmax] (NaN beyond a data set's n), loo_nlpd,
+        loo_sse [F] (+inf / NaN rows where K~ is not positive definite).  One launch forms the gradients or the leave-one-out
+        predictions: ``grad=True`` together with ``loo`` raises ValueError."""
+        if loo is not None and loo not in L.LOO_MODES:
+            raise ValueError("loo must be None, 'refit' or 'fixed'")
+        if loo is not None and grad:
+            raise ValueError("one launch forms the MLII gradients or the leave-one-out predictions: run(grad=True) and run(loo=...) separately")
         if self._uploaded != len(self._sets):
             self.upload()
         F = len(self._fits)
@@ -138,6 +148,15 @@ class SmallBatch:
         ms = max(self._mmax, 1)
         out = np.zeros((F, 8 if grad else 4)); mean = np.full((F, ms), np.nan); var = np.full((F, ms), np.nan)
         gp = self.gp
+        if loo is not None:
+            nmax = max(s[1].shape[0] for s in self._sets)
+            out = np.zeros((F, 6)); lmean = np.full((F, nmax), np.nan); lvar = np.full((F, nmax), np.nan)
+            gp._check(gp._lib.sigp_small_run_loo(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), L.LOO_MODES[loo], L.ptr(out), L.ptr(mean), L.ptr(var), ms,
+                                                 L.ptr(lmean), L.ptr(lvar), nmax), "small_run_loo")
+            gp._fitted = False
+            return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
+                        mean=mean[:, :self._mmax], var=var[:, :self._mmax], loo_mean=lmean, loo_var=lvar,
+                        loo_nlpd=out[:, 4].copy(), loo_sse=out[:, 5].copy())
         fn = gp._lib.sigp_small_run_grad if grad else gp._lib.sigp_small_run
         gp._check(fn(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), L.ptr(out), L.ptr(mean), L.ptr(var), ms), "small_run")
         gp._fitted = False
