@@ -593,502 +593,7 @@ int build_cov(sigp_handle* h, Slot& s, int nb, const double* X, long strideX, co
   return SIGP_OK;
 }
 
-// ---- a panel as a latency chain ---------------------------------------------------------------------------------------------
-// Block columns [J0, J0 + Wp) of nb lockstep members (already up to date), right-looking and column by column, arranged around the
-// chain  diagonal block c -> what diagonal block c+1 needs -> diagonal block c+1:
-//   fused link (panel_chain bit 2, chain_link.hpp): ONE launch between two diagonal blocks -- its first 36 workgroups form
-//     L[c+1, c] and apply it to block (c+1, c+1); the column solve of the rows below rides in the same launch, the update of every
-//     other block (column c+1 below its diagonal block, the panel's columns c+2..) rides in the launch of diagonal block c+1;
-//   otherwise (and for columns with so many rows below that their solve is chip-filling work for the LDS-DMA kernel): column solve
-//     (all rows), update of column c+1 (all rows), diagonal block c+1 with the update of the columns c+2.. riding.
-// Same k order per tile as the binary recursion either way: bit-identical factors.
-// Mm = (virtual) origin of the storage the panel's columns live in, row stride ld, member stride matStride: a slot's square
-// matrices, or one rank's block columns of a sharded factor (origin shifted so that GLOBAL block indices land in it).
-// rlim = one past the last row block touched (R for a whole panel, J0 + Wp for the top block of a strip-solved panel).
-// on_col (may be null): called once block column c is final in the matrix (the sharded fit streams it to the other ranks).
-template <typename Real>
-int chain_panel(sigp_handle* h, Slot& s, hipStream_t sp, Real* Mm, long ld, long matStride, Real* dinvp, long dinvStride, int nb, int J0, int Wp, int rlim,
-                const std::function<int(int)>* on_col = nullptr) {
-  constexpr int diag_lds = diag_lds_bytes<Real>();
-  constexpr int du_lds = std::max(diag_lds, 2 * gemm_lds_bytes<Real, 64, 64, false>());   // (fp32: the two update engines need more than the block)
-  static AttrOnce du_attr, d_attr, l_attr;
-  HIPCHK(h, du_attr.set(h->device, (const void*)diag_update_kernel<Real>, du_lds));
-  HIPCHK(h, d_attr.set(h->device, (const void*)potrf_diag_kernel<Real>, diag_lds));
-  HIPCHK(h, l_attr.set(h->device, (const void*)chain_link_kernel<Real>, link_lds_bytes<Real>()));
-  const int flags = h->opt_diag_prio ? 0 : 32;
-  Real* lk = (Real*)s.lk;
-  auto upd_args = [&](int kc, int ccol0, int c0, int c1) {   // columns ccol0 + [c0, c1) -= (column kc)(column kc)^T, rows from each column's diagonal block to rlim
-    const long o = (long)ccol0 * NB;
-    GemmArgsT<Real> g{};
-    g.A = Mm + o * ld + (long)kc * NB; g.lda = ld;
-    g.B = g.A; g.ldb = ld;
-    g.C = Mm + o * ld + o; g.ldc = ld;
-    g.batch = nb; g.sA = g.sB = g.sC = matStride;
-    g.K = NB; g.r0 = 0; g.r1 = rlim - ccol0; g.c0 = c0; g.c1 = c1; g.lower = 1; g.patch = 0;
-    return g;
-  };
-  // diagonal block of column c (factor + inverse); gu (64-tile units) = an update whose tiles ride in the launch; linked: the launch follows
-  // a fused link of column c - 1 (B operand of block column c from the scratch block, which is also copied into the matrix)
-  auto diag = [&](int c, const GemmArgsT<Real>* gu, bool linked) -> int {
-    const int ntile = gu ? gemm_grid_size(gu->r0, gu->r1, gu->c0, gu->c1, gu->lower, 0) : 0;
-    const double uflops = gu ? nb * (double)ntile * 2.0 * 64 * 64 * gu->K : 0.0;
-    ProfScope ps(h, sp, SIGP_KC_DIAG, nb * 2.0 * NB * NB * NB / 3 + uflops, nb * 3.0 * NB * NB * 8 + nb * (double)ntile * 2.0 * 64 * 64 * sizeof(Real));
-    Real* Ac = Mm + (long)c * NB * ld + (long)c * NB;
-    if (ntile > 0 || linked) {
-      // tile pairs per riding workgroup: in lockstep batches so many that about four riders per CU are left (see diag_update_kernel)
-      const int pairs = (ntile + 1) / 2;
-      const long want = h->opt_ride_reps > 0 ? h->opt_ride_reps : (h->opt_ride_reps < 0 ? ((long)nb * pairs + 4L * h->ncu - 1) / (4L * h->ncu) : 1);
-      const int reps = (int)std::max<long>(1, std::min<long>(want, 32));
-      const int wgs = (pairs + reps - 1) / reps;
-      GemmArgsT<Real> g0{};
-      hipLaunchKernelGGL(diag_update_kernel<Real>, dim3(nb + nb * wgs + (linked ? nb : 0)), dim3(DIAG_THREADS), du_lds, sp, Ac, ld, dinvp + (long)c * NB * NB, s.info,
-                         c * NB, flags, matStride, dinvStride, nb, gu ? *gu : g0, ntile, wgs, linked ? (const Real*)lk : (const Real*)nullptr, (long)NB * NB,
-                         linked ? Ac - NB : (Real*)nullptr, reps);
-    } else {
-      hipLaunchKernelGGL(potrf_diag_kernel<Real>, dim3(nb), dim3(DIAG_THREADS), diag_lds, sp, Ac, ld, dinvp + (long)c * NB * NB, s.info, c * NB, flags, matStride,
-                         dinvStride);
-    }
-    HIPCHK(h, hipGetLastError());
-    return SIGP_OK;
-  };
-  // rows below the diagonal block of column c:  L[c+1.., c] = A[c+1.., c] inv(L_cc)^T
-  auto solve_column = [&](int c) -> int {
-    const long o = (long)(c + 1) * NB;
-    const int rows_below = rlim - (c + 1);
-    if (rows_below <= 0) return SIGP_OK;
-    GemmArgsT<Real> g{};
-    g.A = Mm + o * ld + (long)c * NB; g.lda = ld;
-    g.B = dinvp + (long)c * NB * NB; g.ldb = NB;
-    g.C = Mm + o * ld + (long)c * NB; g.ldc = ld;
-    g.batch = nb; g.sA = g.sC = matStride; g.sB = dinvStride;
-    g.K = NB; g.r0 = 0; g.c0 = 0; g.c1 = 1; g.lower = 0;
-    ProfScope ps(h, sp, SIGP_KC_TRSM, nb * 2.0 * rows_below * NB * NB * NB, nb * 2.0 * rows_below * NB * NB * 8);
-    if (rows_below * nb >= h->opt_trsm128) {   // enough 128-row tiles to fill the chip: the LDS-DMA kernel
-      g.r1 = rows_below;
-      return launch_syrk128_t<Real, true>(h, sp, g);
-    }
-    g.r1 = rows_below * 4;                     // few rows: 32-row tiles for parallelism
-    return launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, sp, g);
-  };
-  int rc = diag(J0, nullptr, false);
-  if (rc) return rc;
-  for (int i = 0; i < Wp; ++i) {
-    const int c = J0 + i;
-    const int rows_below = rlim - (c + 1);
-    const bool last = i + 1 >= Wp;
-    // (the link's ride solves any number of rows, 16 per workgroup; beyond link_rows 128-row blocks x members the stand-alone LDS-DMA solve is the better kernel)
-    const bool fused = !last && (h->opt_panel_chain & 4) != 0 && rows_below >= 1 && (long)rows_below * nb < h->opt_link_rows;
-    if (!fused) {
-      if ((rc = solve_column(c))) return rc;
-      if (on_col && (rc = (*on_col)(c))) return rc;
-      if (last) break;
-      if ((rc = gemm_sub_auto(h, sp, upd_args(c, c + 1, 0, 1)))) return rc;
-      const int rest = Wp - i - 2;                             // columns c+2 .. J0+Wp-1
-      if (rest > 0) {
-        GemmArgsT<Real> gu = upd_args(c, c + 1, 1, 1 + rest);
-        gu.r0 *= 2; gu.r1 *= 2; gu.c0 *= 2; gu.c1 *= 2;
-        rc = diag(c + 1, &gu, false);
-      } else {
-        rc = diag(c + 1, nullptr, false);
-      }
-      if (rc) return rc;
-      continue;
-    }
-    {
-      LinkArgsT<Real> a{};
-      a.Acol = Mm + (long)(c + 1) * NB * ld + (long)c * NB; a.ld = ld;
-      a.Linv = dinvp + (long)c * NB * NB;
-      a.Cdiag = Mm + (long)(c + 1) * NB * ld + (long)(c + 1) * NB;
-      a.scratch = lk;
-      a.sM = matStride; a.sL = dinvStride; a.sS = (long)NB * NB;
-      a.rows_ride = rows_below - 1;
-      ProfScope ps(h, sp, SIGP_KC_TRSM, nb * (2.0 * rows_below * NB * NB * NB + (double)NB * NB * NB), nb * 2.0 * rows_below * NB * NB * 8);
-      hipLaunchKernelGGL(chain_link_kernel<Real>, dim3((unsigned)(LINK_CHAIN_WGS + 8 * a.rows_ride), (unsigned)nb), dim3(256), link_lds_bytes<Real>(), sp, a);
-      HIPCHK(h, hipGetLastError());
-    }
-    GemmArgsT<Real> gu = upd_args(c, c + 1, 0, Wp - i - 1);    // columns c+1 .. J0+Wp-1 from row block c+2 down (block (c+1, c+1) is done)
-    gu.r0 = 2; gu.r1 *= 2; gu.c0 *= 2; gu.c1 *= 2;
-    if ((rc = diag(c + 1, &gu, true))) return rc;
-    if (on_col && (rc = (*on_col)(c))) return rc;              // (block row c+1 of column c reached the matrix in that launch)
-  }
-  return SIGP_OK;
-}
-
-// ---- blocked Cholesky of the nb lockstep members of slot s (each augmented with its ride rows) --------
-// Every launch covers the same step of all nb factorisations (grid.y / grid.x = member), so launches stay
-// GPU-filling as the trailing matrices shrink and the per-step latency chain is paid once per nb fits.
-// block columns per outer panel
-// (a single fit of at most 24 block columns, unless the caller chose: ONE panel -- no panel boundary (each is a trailing update in series with the
-//  chain), and the right-looking rides of such a panel still fit beside its diagonal blocks: n = 2048 0.670 ms (16) vs 0.715 (8), n = 3072 1.082
-//  (24) vs 1.126 (16) / 1.122 (8).  From there on the rides of the first columns outlast the diagonal block: n = 4096 1.653 (8) / 1.675 (16) / 1.755 (32);
-//  tools/single_sweep.py)
-// (fp32 fits from 192 block columns on: the fp32 update runs its K = 1024 tile in half the time of the fp64 one, so the tile's C read +
-//  write weighs twice as much -- K = 2048 instead: n = 32768 102.95 vs 104.4 ms (12: 103.3, 24: 104.1, 32: 106.3); n = 16384 19.2 vs 19.05: not there)
-inline int outer_width(const sigp_handle* h, int nb, int T, bool f32 = false) {
-  if (!h->outer_set && f32 && T >= 192) return 16;             // (a lockstep group of 4 at n = 32768: 97.7 vs 98.6-99.0 ms per fit)
-  return (!h->outer_set && nb == 1 && T <= 24 && (h->opt_panel_chain & 4)) ? std::max(1, T) : std::max(1, h->opt_outer);
-}
-template <typename Real>
-int potrf_core(sigp_handle* h, Slot& s, Real* M, long matStride, Real* dinvp, long dinvStride, int nb, long n_pad, bool head_on_panel = false,
-               int ride_rows = RIDE) {
-  const long ld = n_pad;
-  const int T = (int)(n_pad / NB);   // column blocks
-  const int R = T + 1;               // row blocks including the ride block
-  // ride_rows: rows of the ride-along block in use (y + the test points; the rest are zero rows).  Up to 16: the block row's tiles in the
-  // trailing updates multiply their first 16-row sub-tile only (syrk128_tile's RD form)
-  const bool ride16 = h->opt_ride_tiles && h->opt_diag_tiles && ride_rows <= 16;     // (the RD form lives in the kernel instantiation that has the DG form)
-  const int W = outer_width(h, nb, T, std::is_same<Real, float>::value);
-  constexpr int diag_lds = diag_lds_bytes<Real>();
-  if (std::is_same<Real, double>::value && (h->opt_panel_mode == 1 || (h->opt_panel_mode == 2 && (long)R * nb >= h->opt_strip_min))) {
-    int rcm = slot_ensure_mt(h, s, nb);
-    if (rcm) return rcm;
-  }
-  static AttrOnce diag_attr;
-  HIPCHK(h, diag_attr.set(h->device, (const void*)potrf_diag_kernel<Real>, diag_lds));
-  const bool la = h->opt_lookahead != 0;
-  hipStream_t sp = la ? s.s_pan : s.s_upd;   // panel stream
-  hipStream_t su = s.s_upd;
-  // head_on_panel (lockstep batches, head pipelining): the covariance build of this group was enqueued on the PANEL stream and
-  // the update stream starts with a wait for the previous group, so the build and the first panel run while the previous
-  // group is still updating; nothing of this group's head may then be ordered behind the update stream
-  const bool head = head_on_panel && la;
-  HIPCHK(h, hipMemsetAsync(s.info, 0, (size_t)nb * sizeof(int), head ? sp : su));
-  if (la && !head) {   // panel stream starts after the build on the update stream
-    HIPCHK(h, hipEventRecord(s.ev_la, su));
-    HIPCHK(h, hipStreamWaitEvent(sp, s.ev_la, 0));
-  }
-
-  // lower-trapezoid update  C[cols ccol0.., rows >= col .. R) -= P P^T,  P = L[:, kcol0 .. kcol0+kw)
-  auto update_args = [&](int kcol0, int kw, int ccol0, int c0, int c1, int rlim) -> GemmArgsT<Real> {
-    const long o = (long)ccol0 * NB;
-    GemmArgsT<Real> g{};
-    g.A = M + o * ld + (long)kcol0 * NB; g.lda = ld;
-    g.B = g.A; g.ldb = ld;
-    g.C = M + o * ld + o; g.ldc = ld;
-    g.batch = nb; g.sA = g.sB = g.sC = matStride;
-    g.K = kw * NB; g.r0 = 0; g.r1 = rlim - ccol0; g.c0 = c0; g.c1 = c1; g.lower = 1; g.patch = h->opt_patch;
-    if (ride16 && rlim == R) { g.ride_bi1 = R - ccol0; g.ride_rows = ride_rows; }     // (block row R - 1 of the matrix = row R - 1 - ccol0 of this tile space)
-    return g;
-  };
-  auto update = [&](hipStream_t st, int kclass, int kcol0, int kw, int ccol0, int c0, int c1, int rlim) -> int {
-    (void)kclass;
-    return gemm_sub_auto(h, st, update_args(kcol0, kw, ccol0, c0, c1, rlim));
-  };
-  // diagonal block of column c (factor + inverse); `gu` (64-tile units) = an update whose tiles ride in the same launch
-  auto diag_block = [&](int c, const GemmArgsT<Real>* gu) -> int {
-    const int ntile = gu ? gemm_grid_size(gu->r0, gu->r1, gu->c0, gu->c1, gu->lower, 0) : 0;
-    const double uflops = gu ? nb * (double)ntile * 2.0 * 64 * 64 * gu->K : 0.0;
-    ProfScope ps(h, sp, SIGP_KC_DIAG, nb * 2.0 * NB * NB * NB / 3 + uflops, nb * 3.0 * NB * NB * 8 + nb * (double)ntile * 2.0 * 64 * 64 * sizeof(Real));
-    Real* Ac = M + (long)c * NB * ld + (long)c * NB;
-    const int flags = h->opt_diag_prio ? 0 : 32;
-    if (ntile > 0) {
-      static AttrOnce du_attr;
-      constexpr int du_lds = std::max(diag_lds, 2 * gemm_lds_bytes<Real, 64, 64, false>());   // (fp32: the two update engines need more than the block)
-      HIPCHK(h, du_attr.set(h->device, (const void*)diag_update_kernel<Real>, du_lds));
-      const int pairs = (ntile + 1) / 2;
-      const long want = h->opt_ride_reps > 0 ? h->opt_ride_reps : (h->opt_ride_reps < 0 ? ((long)nb * pairs + 4L * h->ncu - 1) / (4L * h->ncu) : 1);
-      const int reps = (int)std::max<long>(1, std::min<long>(want, 32));
-      const int wgs = (pairs + reps - 1) / reps;
-      hipLaunchKernelGGL(diag_update_kernel<Real>, dim3(nb + nb * wgs), dim3(DIAG_THREADS), du_lds, sp, Ac, ld, dinvp + (long)c * NB * NB, s.info,
-                         c * NB, flags, matStride, dinvStride, nb, *gu, ntile, wgs, (const Real*)nullptr, 0L, (Real*)nullptr, reps);
-    } else {
-      hipLaunchKernelGGL(potrf_diag_kernel<Real>, dim3(nb), dim3(DIAG_THREADS), diag_lds, sp, Ac, ld, dinvp + (long)c * NB * NB, s.info, c * NB,
-                         flags, matStride, dinvStride);
-    }
-    HIPCHK(h, hipGetLastError());
-    return SIGP_OK;
-  };
-  // rows below the diagonal block of column c:  L[c+1.., c] = A[c+1.., c] inv(L_cc)^T
-  auto solve_column = [&](int c, int rlim) -> int {
-    const long o = (long)(c + 1) * NB;
-    const int rows_below = rlim - (c + 1);   // 128-row blocks below the diagonal block (ride block included when rlim = R)
-    if (rows_below <= 0) return SIGP_OK;
-    GemmArgsT<Real> g{};
-    g.A = M + o * ld + (long)c * NB; g.lda = ld;
-    g.B = dinvp + (long)c * NB * NB; g.ldb = NB;
-    g.C = M + o * ld + (long)c * NB; g.ldc = ld;
-    g.batch = nb; g.sA = g.sC = matStride; g.sB = dinvStride;
-    g.K = NB; g.r0 = 0; g.c0 = 0; g.c1 = 1; g.lower = 0;
-    ProfScope ps(h, sp, SIGP_KC_TRSM, nb * 2.0 * rows_below * NB * NB * NB, nb * 2.0 * rows_below * NB * NB * 8);
-    if (rows_below * nb >= h->opt_trsm128) {   // enough 128-row tiles to fill the chip: the LDS-DMA kernel
-      g.r1 = rows_below;
-      return launch_syrk128_t<Real, true>(h, sp, g);
-    }
-    g.r1 = rows_below * 4;                     // few rows: 32-row tiles for parallelism
-    return launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, sp, g);
-  };
-  // factor block columns [J0, J0+Wp) (already up to date) by binary recursion: the left half, a rank-(half) update
-  // of the right half's columns, then the right half.
-  // rlim = one past the last row block the recursion touches: R for the whole panel, J0+Wp for its top block only
-  std::function<int(int, int, int)> panel_rec = [&](int J0, int Wp, int rlim) -> int {
-    if (Wp == 1) {
-      int rc1 = diag_block(J0, nullptr);
-      return rc1 ? rc1 : solve_column(J0, rlim);
-    }
-    if (h->opt_panel_ll && Wp <= h->opt_panel_ll) {
-      // left-looking inside a (sub)panel: column block c is updated once with all earlier columns of the panel
-      // (K = 128 (c-J0)), then factored: each panel column is read/written once and the average K doubles
-      for (int i = 0; i < Wp; ++i) {
-        int rc;
-        if (i > 0 && (rc = update(sp, SIGP_KC_UPDATE_SMALL, J0, i, J0 + i, 0, 1, rlim))) return rc;
-        if ((rc = panel_rec(J0 + i, 1, rlim))) return rc;
-      }
-      return SIGP_OK;
-    }
-    if (Wp == 2 && (h->opt_panel_chain & 8) && rlim - J0 >= 2)   // the recursion's leaf pairs through the fused link: D, link, D + riding update of the second column, solve
-      return chain_panel<Real>(h, s, sp, M, ld, matStride, dinvp, dinvStride, nb, J0, 2, rlim);
-    const int hw = Wp / 2;
-    int rc = panel_rec(J0, hw, rlim);
-    if (rc) return rc;
-    if ((rc = update(sp, SIGP_KC_UPDATE_SMALL, J0, hw, J0 + hw, 0, Wp - hw, rlim))) return rc;
-    return panel_rec(J0 + hw, Wp - hw, rlim);
-  };
-  // The same panel as a latency chain (chain_panel above): right-looking column by column, bit-identical to the recursion.
-  auto panel_chain = [&](int J0, int Wp, int rlim) -> int {
-    return chain_panel<Real>(h, s, sp, M, ld, matStride, dinvp, dinvStride, nb, J0, Wp, rlim);
-  };
-  // top = the top block of a strip-solved panel.  A whole panel takes the chain form only while its riding updates (K = 128, 64x64
-  // tiles: 4 flop per operand byte) stay shorter than the diagonal block they ride beside: up to chain_rows (80) 128-row blocks x
-  // members below the panel's first column (n = 32768 in fp32 is 4 % faster with the recursion's K = 256 / 512 updates)
-  auto chain_form = [&](int J0, int Wp, int rlim, bool top) -> bool {
-    return Wp > 2 && (top ? (h->opt_panel_chain & 2) != 0 : ((h->opt_panel_chain & 1) != 0 && (long)(rlim - J0) * nb <= h->opt_chain_rows));
-  };
-  auto panel_any = [&](int J0, int Wp, int rlim, bool top) -> int {
-    return chain_form(J0, Wp, rlim, top) ? panel_chain(J0, Wp, rlim) : panel_rec(J0, Wp, rlim);
-  };
-  // factor block columns [J0, J0+Wp): panel_top = everything on the panel stream up to the strip solve (the whole panel when it
-  // is not strip-solved); panel_strips = the Mt products + strip kernel for the rows below the top block (no-op otherwise)
-  auto use_strips = [&](int J0, int Wp) -> bool {
-    const int below = R - (J0 + Wp);             // row blocks under the panel's top block (the ride block is one of them)
-    return std::is_same<Real, double>::value && Wp > 1 && Wp <= MT_W && below > 0 &&
-           (h->opt_panel_mode == 1 || (h->opt_panel_mode == 2 && (long)below * nb >= h->opt_strip_min));
-  };
-  auto panel_top = [&](int J0, int Wp) -> int {
-    if (!use_strips(J0, Wp)) return panel_any(J0, Wp, R, false);
-    // panel_mode 1: recursion on the top Wp x Wp block only, then every 128-row strip below it is solved by one
-    // workgroup walking the panel's columns (panel_strip_kernel): the lower rows are read and written once
-    return panel_any(J0, Wp, J0 + Wp, true);
-  };
-  auto panel_strips = [&](int J0, int Wp) -> int {
-    if (!use_strips(J0, Wp)) return SIGP_OK;
-    const int below = R - (J0 + Wp);
-    int rc;
-    Real* mt = (Real*)s.mt;
-    const long mtStride = MT_LD * MT_LD;
-    {
-      ProfScope ps(h, sp, SIGP_KC_UPDATE_SMALL, nb * 2.0 * NB * NB * NB * (Wp * (Wp - 1) / 2), nb * 3.0 * NB * NB * 8 * (Wp * (Wp + 1) / 2));
-      hipLaunchKernelGGL(mt_diag_kernel<Real>, dim3(Wp, nb), dim3(256), 0, sp, dinvp + (long)J0 * NB * NB, dinvStride, mt, MT_LD, mtStride);
-      HIPCHK(h, hipGetLastError());
-      for (int j = 1; j < Wp; ++j) {             // Mt[j, 0:j] = -inv(L_jj) L[j, 0:j]
-        GemmArgsT<Real> g{};
-        g.A = dinvp + (long)(J0 + j) * NB * NB; g.lda = NB; g.sA = dinvStride;
-        g.B = M + (long)(J0 + j) * NB * ld + (long)J0 * NB; g.ldb = ld; g.sB = matStride;     // K x N row-major (BT)
-        g.C = mt + (long)j * NB * MT_LD; g.ldc = MT_LD; g.sC = mtStride;
-        g.batch = nb; g.K = NB; g.r0 = 0; g.r1 = 4; g.c0 = 0; g.c1 = j; g.lower = 0;
-        if ((rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SETNEG, true>(h, sp, g))) return rc;
-      }
-    }
-    {
-      ProfScope ps(h, sp, SIGP_KC_TRSM, nb * (double)below * 2.0 * NB * NB * NB * (Wp * (Wp + 1) / 2), nb * (double)below * 2.0 * Wp * NB * NB * 8);
-      static AttrOnce strip_attr, strip_attr_full;
-      StripArgsT<Real> a{M, ld, matStride, mt, MT_LD, mtStride, J0 + Wp, J0, Wp};
-      if (h->opt_strip_tri) {
-        HIPCHK(h, strip_attr.set(h->device, (const void*)panel_strip_kernel<Real>, SY_LDS_BYTES));
-        hipLaunchKernelGGL(panel_strip_kernel<Real>, dim3(below, nb), dim3(256), SY_LDS_BYTES, sp, a);
-      } else {
-        HIPCHK(h, strip_attr_full.set(h->device, (const void*)panel_strip_kernel<Real, false>, SY_LDS_BYTES));
-        hipLaunchKernelGGL((panel_strip_kernel<Real, false>), dim3(below, nb), dim3(256), SY_LDS_BYTES, sp, a);
-      }
-      HIPCHK(h, hipGetLastError());
-    }
-    return SIGP_OK;
-  };
-  auto panel = [&](int J0, int Wp) -> int {
-    int rc = panel_top(J0, Wp);
-    return rc ? rc : panel_strips(J0, Wp);
-  };
-  auto outer = [&](hipStream_t st, int J, int Wc, int c0, int c1) -> int {
-    // persistent form (update_wgs): only for outer trailing updates, and with update_late only for the last panels, where the
-    // updates are small and the panel chain they share the chip with is what the step waits for
-    const int panels_left = (T - (J + Wc) + W - 1) / W;
-    h->persist_now = h->opt_update_wgs > 0 && (h->opt_update_late == 0 || panels_left <= h->opt_update_late);
-    const int rc_ = update(st, SIGP_KC_SYRK128, J, Wc, J + Wc, c0, c1, R);
-    h->persist_now = false;
-    return rc_;
-  };
-
-  int rc = panel(0, std::min(W, T));
-  if (rc) return rc;
-  if (h->opt_schedule == 1) {
-    // Left-looking outer schedule: panel q (columns J..J+Wq) is brought up to date in two launches,
-    //   A(q): C_q -= L[:, 0 : J-W] L[q rows, 0 : J-W]^T   (all panels but the last one: K = 128 (J-W), up to n - 2*128 W)
-    //   B(q): C_q -= P_{q-1} P_{q-1}^T                    (the panel factored last: K = 128 W)
-    // and then factored, F(q).  A(q+1) only needs panels 0..q-1, so it runs on the update stream while the panel
-    // stream does B(q), F(q).  Each C tile is read and written twice per panel instead of once per EARLIER panel,
-    // and almost all flops run at K >= 1024.  The k order of every tile's sum is the same as in the right-looking
-    // schedule (panels in order, k ascending), so the factor is bit-identical.
-    hipEvent_t evF[2] = {s.ev_pan, s.ev_done};
-    if (la) HIPCHK(h, hipEventRecord(evF[0], sp));                 // F(0)
-    int q = 1;
-    for (int J = W; J < T; J += W, ++q) {
-      const int Wq = std::min(W, T - J);
-      if (la) {
-        if (q >= 2) {
-          HIPCHK(h, hipStreamWaitEvent(su, evF[q & 1], 0));          // F(q-2) done (same parity as q)
-          if ((rc = update(su, SIGP_KC_SYRK128, 0, J - W, J, 0, Wq, R))) return rc;    // A(q)
-          HIPCHK(h, hipEventRecord(s.ev_la, su));
-          HIPCHK(h, hipStreamWaitEvent(sp, s.ev_la, 0));
-        }
-        if ((rc = update(sp, SIGP_KC_SYRK128, J - W, W, J, 0, Wq, R))) return rc;      // B(q), after F(q-1) in stream order
-        if ((rc = panel(J, Wq))) return rc;                                             // F(q)
-        HIPCHK(h, hipEventRecord(evF[q & 1], sp));
-      } else {
-        if ((rc = update(su, SIGP_KC_SYRK128, 0, J, J, 0, Wq, R))) return rc;          // A(q)+B(q) in one launch
-        if ((rc = panel(J, Wq))) return rc;
-      }
-    }
-    if (la) {
-      HIPCHK(h, hipEventRecord(s.ev_pan, sp));
-      HIPCHK(h, hipStreamWaitEvent(su, s.ev_pan, 0));
-    }
-    return SIGP_OK;
-  }
-  bool have_rest = false;                      // first_on_panel: an update of the rest of the trailing matrix is in flight on su
-  bool tail_marked = false;                    // ev_tail recorded (pipeline_head = 3)
-  for (int J = 0; J < T; J += W) {
-    const int Wc = std::min(W, T - J);
-    const int ncols = T - (J + Wc);            // trailing column blocks
-    if (ncols <= 0) break;
-    const int Wn = std::min(W, ncols);         // width of the next panel
-    if (la && !tail_marked && ncols <= h->opt_head_gate) {   // panel J is the last one before the tail: the next group's head may start behind it
-      HIPCHK(h, hipEventRecord(s.ev_tail, sp));
-      tail_marked = true;
-    }
-    if (la && (h->opt_first_on_panel == 2 || (h->opt_first_on_panel == 1 && !use_strips(J + Wc, Wn)))) {
-      // The update of the NEXT panel's columns stays on the panel stream (stream order, no inter-queue hand-off in the chain
-      // panel -> first update -> next panel: each hand-off is a barrier packet pair, 11-13 us measured); the update stream gets
-      // the rest of the trailing matrix, which the panel stream only has to see finished one panel later.
-      if (have_rest) HIPCHK(h, hipStreamWaitEvent(sp, s.ev_done, 0));   // rest(J - W) wrote these columns too
-      if ((rc = outer(sp, J, Wc, 0, Wn))) return rc;
-      HIPCHK(h, hipEventRecord(s.ev_pan, sp));            // panel J and the first update done: the rest starts behind them, so the
-      HIPCHK(h, hipStreamWaitEvent(su, s.ev_pan, 0));     // update the chain waits for has the chip to itself
-      have_rest = ncols > Wn;
-      if (have_rest) {
-        if ((rc = outer(su, J, Wc, Wn, ncols))) return rc;
-        HIPCHK(h, hipEventRecord(s.ev_done, su));
-      }
-      if (h->opt_strips_after_update && use_strips(J + Wc, Wn)) {
-        if ((rc = panel_top(J + Wc, Wn))) return rc;
-        if (have_rest) HIPCHK(h, hipStreamWaitEvent(sp, s.ev_done, 0));
-        if ((rc = panel_strips(J + Wc, Wn))) return rc;
-      } else if ((rc = panel(J + Wc, Wn))) return rc;
-    } else if (la) {
-      HIPCHK(h, hipEventRecord(s.ev_pan, sp));            // panel J done
-      HIPCHK(h, hipStreamWaitEvent(su, s.ev_pan, 0));
-      rc = outer(su, J, Wc, 0, Wn);                       // next panel's columns first
-      if (rc) return rc;
-      HIPCHK(h, hipEventRecord(s.ev_la, su));
-      HIPCHK(h, hipStreamWaitEvent(sp, s.ev_la, 0));
-      if (h->opt_strips_after_update && use_strips(J + Wc, Wn)) {
-        // only the next panel's top block (a latency chain of small launches) overlaps the rest of the update; its strip solve --
-        // MFMA work for the whole chip -- starts when that update is done instead of sharing the chip with it
-        if ((rc = panel_top(J + Wc, Wn))) return rc;
-        if ((rc = outer(su, J, Wc, Wn, ncols))) return rc;
-        HIPCHK(h, hipEventRecord(s.ev_done, su));
-        HIPCHK(h, hipStreamWaitEvent(sp, s.ev_done, 0));
-        if ((rc = panel_strips(J + Wc, Wn))) return rc;
-      } else {
-        rc = panel(J + Wc, Wn);                           // next panel overlaps the rest of the update
-        if (rc) return rc;
-        rc = outer(su, J, Wc, Wn, ncols);
-        if (rc) return rc;
-        HIPCHK(h, hipEventRecord(s.ev_done, su));         // (a later panel may take the first_on_panel form and wait for this)
-      }
-      have_rest = ncols > Wn;
-    } else {
-      rc = outer(su, J, Wc, 0, ncols);
-      if (rc) return rc;
-      rc = panel(J + Wc, Wn);
-      if (rc) return rc;
-    }
-  }
-  if (la) {   // join: the update stream is the slot's completion stream
-    if (!tail_marked) HIPCHK(h, hipEventRecord(s.ev_tail, sp));
-    HIPCHK(h, hipEventRecord(s.ev_pan, sp));
-    HIPCHK(h, hipStreamWaitEvent(su, s.ev_pan, 0));
-  }
-  return SIGP_OK;
-}
-
-int potrf_slot(sigp_handle* h, Slot& s, int nb, long n_pad, bool head_on_panel = false, int ride_rows = RIDE) {
-  return potrf_core<double>(h, s, s.mat, s.matStride, s.dinv, s.dinvStride, nb, n_pad, head_on_panel, ride_rows);
-}
-
-// stand-alone pieces of potrf_core for the multi-GPU driver (one member; Mm / dinvp = the fp64 slot matrix or the fp32 engine's)
-template <typename Real>
-int dist_update(sigp_handle* h, Real* Mm, hipStream_t st, long n_pad, int kcol0, int kw, int ccol0, int c0, int c1) {
-  const long ld = n_pad;
-  const int T = (int)(n_pad / NB), R = T + 1;
-  const long o = (long)ccol0 * NB;
-  GemmArgsT<Real> g{};
-  g.A = Mm + o * ld + (long)kcol0 * NB; g.lda = ld;
-  g.B = g.A; g.ldb = ld;
-  g.C = Mm + o * ld + o; g.ldc = ld;
-  g.batch = 1; g.sA = g.sB = g.sC = 0;
-  g.K = kw * NB; g.r0 = 0; g.r1 = R - ccol0; g.c0 = c0; g.c1 = c1; g.lower = 1; g.patch = 0;
-  return gemm_sub_auto(h, st, g);
-}
-
-// Mm = (virtual) origin of the storage the panel's columns live in, row stride ld: the slot's square matrix (ld = n_pad) or one
-// rank's block columns (sigp_dist_local_*: ld = its column count, origin shifted so that GLOBAL column indices land in it)
-// on_col (may be null): called right after the column solve of block column c has been enqueued -- that column is then final
-// (the sharded fit streams it to the other ranks while the chain goes on)
-template <typename Real>
-int dist_panel_rec(sigp_handle* h, Slot& s, Real* Mm, long ld, Real* dinvp, hipStream_t sp, long n_pad, int J0, int Wp, const std::function<int(int)>* on_col = nullptr);
-// the panel in its latency-chain form (potrf_core's panel_chain, one member): right-looking column by column, the update of the
-// columns beyond the next one riding in the next diagonal block's launch.  Same k order per tile as the recursion: bit-identical.
-template <typename Real>
-int dist_panel(sigp_handle* h, Slot& s, Real* Mm, long ld, Real* dinvp, hipStream_t sp, long n_pad, int J0, int Wp, const std::function<int(int)>* on_col = nullptr) {
-  const int T = (int)(n_pad / NB), R = T + 1;
-  if (!(h->opt_panel_chain & 1) || Wp <= 2 || (long)(R - J0) > h->opt_chain_rows) return dist_panel_rec<Real>(h, s, Mm, ld, dinvp, sp, n_pad, J0, Wp, on_col);
-  return chain_panel<Real>(h, s, sp, Mm, ld, 0L, dinvp, 0L, 1, J0, Wp, R, on_col);
-}
-
-template <typename Real>
-int dist_panel_rec(sigp_handle* h, Slot& s, Real* Mm, long ld, Real* dinvp, hipStream_t sp, long n_pad, int J0, int Wp, const std::function<int(int)>* on_col) {
-  const int T = (int)(n_pad / NB), R = T + 1;
-  if (Wp == 1) {
-    const int c = J0;
-    hipLaunchKernelGGL(potrf_diag_kernel<Real>, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, sp, Mm + (long)c * NB * ld + (long)c * NB, ld,
-                       dinvp + (long)c * NB * NB, s.info, c * NB, 0, 0L, 0L);
-    HIPCHK(h, hipGetLastError());
-    const long o = (long)(c + 1) * NB;
-    const int rows_below = R - (c + 1);
-    GemmArgsT<Real> g{};
-    g.A = Mm + o * ld + (long)c * NB; g.lda = ld;
-    g.B = dinvp + (long)c * NB * NB; g.ldb = NB;
-    g.C = Mm + o * ld + (long)c * NB; g.ldc = ld;
-    g.batch = 1; g.K = NB; g.r0 = 0; g.c0 = 0; g.c1 = 1; g.lower = 0;
-    int rc1;
-    if (rows_below >= h->opt_trsm128) { g.r1 = rows_below; rc1 = launch_syrk128_t<Real, true>(h, sp, g); }
-    else { g.r1 = rows_below * 4; rc1 = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, sp, g); }
-    if (rc1) return rc1;
-    return on_col ? (*on_col)(c) : SIGP_OK;
-  }
-  const int hw = Wp / 2;
-  int rc = dist_panel_rec<Real>(h, s, Mm, ld, dinvp, sp, n_pad, J0, hw, on_col);
-  if (rc) return rc;
-  {   // columns of the right half -= (left half)(left half)^T, rows from the right half's diagonal block down
-    const long o = (long)(J0 + hw) * NB;
-    GemmArgsT<Real> g{};
-    g.A = Mm + o * ld + (long)J0 * NB; g.lda = ld;
-    g.B = g.A; g.ldb = ld;
-    g.C = Mm + o * ld + o; g.ldc = ld;
-    g.batch = 1; g.K = hw * NB; g.r0 = 0; g.r1 = R - (J0 + hw); g.c0 = 0; g.c1 = Wp - hw; g.lower = 1;
-    if ((rc = gemm_sub_auto(h, sp, g))) return rc;
-  }
-  return dist_panel_rec<Real>(h, s, Mm, ld, dinvp, sp, n_pad, J0 + hw, Wp - hw, on_col);
-}
+#include "sigp_factor.inc"   // blocked Cholesky: panel primitives, chain_panel, panel_rec, potrf_core, the sharded fit's panel selectors
 
 // epilogue reductions on the ride blocks of slot s + async copy of results / info to pinned host memory
 int epilogue_slot(sigp_handle* h, Slot& s, int nb, long n, long n_pad, long m) {

@@ -1,4 +1,4 @@
-// fp32 engine of libsigp.so (BASELINE configs[4]): fp32 covariance build + blocked Cholesky (potrf_core<float>), block
+// fp32 engine of libsigp.so (BASELINE configs[4]): fp32 covariance build + blocked Cholesky (potrf_core<float>, sigp_factor.inc), block
 // triangular solves and the fp64 iterative refinement.  Included by sigp.hip inside its anonymous namespace (one translation unit).
 
 // ---- fp32 engine: fp32 kernel matrix + Cholesky, fp64 iterative refinement of alpha~ and w_j -----------------

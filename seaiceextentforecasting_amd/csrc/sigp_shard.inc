@@ -1,6 +1,7 @@
 // One large fit sharded over the GPUs of a node, entirely inside the library (included by sigp.hip in its anonymous namespace):
 // the transports (the library's own RCCL communicator, bound with dlopen; or a caller-supplied one), the panel loop of the
 // block-cyclic Cholesky with its look-ahead broadcast, and the sharded triangular solves + fp64 refinement of the fp32 engine.
+// A panel is factored by the same primitives as a single-GPU fit (dist_panel / dist_panel_top, sigp_factor.inc).
 // Replaces the same statements as the single-GPU path: north/June1st.py:265 (Cholesky), :266-277 (solves, predictions), :246.
 //
 // Layout.  Panel q = block columns [q W, q W + W_q) (W_q = W except for the last); rank q % world owns it: it alone stores,
@@ -453,7 +454,7 @@ int shard_build(sigp_handle* h, int kernel_id, double ell, double sn_tilde, cons
 // Row-split panel exchange: the rows below a panel's top block, `nrows` 128-row blocks of them at C (row stride ldc = the panel's width),
 // against the factored top block L11 [w 128][w 128] (row stride ldc as well) and its inverse diagonal blocks -- X = A21 L11^-T by the
 // same binary recursion over the panel's columns, the same tile kernels and the same k order as the owner's whole-panel path
-// (dist_panel_rec), restricted to these rows: bit-identical row for row.
+// (panel_rec, sigp_factor.inc), restricted to these rows: bit-identical row for row.
 template <typename Real>
 int rows_solve(sigp_handle* h, hipStream_t st, Real* Cm, long nrows, long ldc, const Real* L11, const Real* dinvb, int c0, int w) {
   if (nrows <= 0 || w <= 0) return SIGP_OK;
@@ -462,10 +463,7 @@ int rows_solve(sigp_handle* h, hipStream_t st, Real* Cm, long nrows, long ldc, c
     g.A = Cm + (long)c0 * NB; g.lda = ldc;
     g.B = dinvb + (long)c0 * NB * NB; g.ldb = NB;
     g.C = Cm + (long)c0 * NB; g.ldc = ldc;
-    g.batch = 1; g.K = NB; g.r0 = 0; g.c0 = 0; g.c1 = 1; g.lower = 0;
-    if (nrows >= h->opt_trsm128) { g.r1 = (int)nrows; return launch_syrk128_t<Real, true>(h, st, g); }
-    g.r1 = (int)nrows * 4;
-    return launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, st, g);
+    return launch_column_solve<Real>(h, st, g, nrows, 1);
   }
   const int hw = w / 2;
   int rc = rows_solve<Real>(h, st, Cm, nrows, ldc, L11, dinvb, c0, hw);
@@ -477,13 +475,6 @@ int rows_solve(sigp_handle* h, hipStream_t st, Real* Cm, long nrows, long ldc, c
   g.batch = 1; g.K = hw * NB; g.r0 = 0; g.r1 = (int)nrows; g.c0 = 0; g.c1 = w - hw; g.lower = 0;
   if ((rc = gemm_sub_auto(h, st, g))) return rc;
   return rows_solve<Real>(h, st, Cm, nrows, ldc, L11, dinvb, c0 + hw, w - hw);
-}
-
-// the top W x W block of panel [J0, J0 + Wp) only (rows below it are somebody else's work): chain form or recursion as dist_panel picks them
-template <typename Real>
-int dist_panel_top(sigp_handle* h, Slot& s, Real* Mm, long ld, Real* dinvp, hipStream_t sp, int J0, int Wp) {
-  if (Wp == 1) return chain_panel<Real>(h, s, sp, Mm, ld, 0L, dinvp, 0L, 1, J0, 1, J0 + 1);
-  return chain_panel<Real>(h, s, sp, Mm, ld, 0L, dinvp, 0L, 1, J0, Wp, J0 + Wp);
 }
 
 // ---- the panel loop -----------------------------------------------------------------------------------------------------------
@@ -761,8 +752,8 @@ int shard_factor(sigp_handle* h, bool lookahead) {
     };
     // The next panel's columns first, and on ITS OWNER'S PANEL STREAM: that update, the panel's factorisation and its segments' packs
     // are then one in-order chain (no inter-queue hand-off in it, and the diagonal-block kernel is queued before the rest of the
-    // trailing update can occupy every CU); the rest starts on the update stream once this first update is done.  (potrf_core's
-    // first_on_panel schedule, across ranks.)  When this rank is not panel p's owner the first update was applied segment by
+    // trailing update can occupy every CU); the rest starts on the update stream once this first update is done.  (The
+    // first_on_panel schedule of potrf_core, sigp_factor.inc, across ranks.)  When this rank is not panel p's owner the first update was applied segment by
     // segment above; when it is, in one launch from local storage.
     if (own_next && sp != su && split && hot > 0) {
       // row-distributed first update: this rank keeps the update of panel p + 1's TOP block, from the hot rows (the rows below it get theirs
