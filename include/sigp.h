@@ -84,6 +84,24 @@ int sigp_predict_ride(sigp_handle* h, double* mean, double* var);
 /* K9-K11 for arbitrary new test points after a fit (any m): cross-kernel build + forward solve. */
 int sigp_predict(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, double* mean, double* var);
 
+/* The JOINT posterior of m new test points after a fit: the mean and the full m x m covariance (what every GP library returns for
+ * return_cov=True; the variances of north/June1st.py:273, :277 are its diagonal).  With Z = k~(Xs, X) L~^-T (the solved rows sigp_predict
+ * reduces to their squared norms) and z = L~^-1 y:
+ *     mean_j = Z_j . z        (the same launches as sigp_predict: the same bits)
+ *     cov_ij = sigma_f (k~**(xs_i, xs_j) + [i == j and noise] sn~ - Z_i . Z_j)
+ * noise != 0: the covariance of the observations y* (sigma_n = sn~ sigma_f on the diagonal, so diag(cov) is sigp_predict's var); noise == 0:
+ * of the latent f*.  mean [m], cov [m][ldc >= m] row-major, the full matrix, bitwise symmetric.  k~** is the unit prior of the fit's
+ * kernel (RBF / Matern: diagonal exactly 1; reference kernel: Xs Sigma~ Xs^T formed on the device).  Cost: the forward solve of
+ * sigp_predict, n^2 m flops (m triangular solves), + the product Z Z^T, n m^2 flops (lower tile pairs of 128 x 128, K split over "cov_slices" slices whose
+ * partial tiles are added in a fixed order: the same bits on every run for a given slice count) + m^2 prior entries.  Device memory:
+ * 8 m_pad (n_pad + m_pad) bytes (+ 128 KiB per partial tile), m_pad = m rounded up to 128.  Device work is accounted under SIGP_KC_KBUILD
+ * (rows), SIGP_KC_TRSM (one entry per lockstep solve group) and SIGP_KC_EPILOGUE (the product and the finishing pass, one entry each).
+ * 1 <= m <= SIGP_MAX_COV.  fp64 engine, any of the three kernels, after sigp_fit / sigp_fit_predict; on an fp32 handle or after a sharded
+ * fit (sigp_dist_fit): SIGP_BAD_ARG.  The factor and the fit's state are only read: sigp_predict / sigp_get_alpha / sigp_loo afterwards
+ * return what they returned before. */
+#define SIGP_MAX_COV 8192
+int sigp_predict_cov(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, int noise, double* mean, double* cov, int64_t ldc);
+
 /* Fused hot path: build -> potrf -> fit -> predict_ride with one host synchronisation.
  * Sigma may be NULL unless kernel_id == SIGP_KERNEL_NETDIFFUSION.
  * out[4] = { sigma_f, nlml, (double)info, sigma_n };  mean/var [m_ride] may be NULL when m_ride == 0. */
@@ -175,7 +193,8 @@ double sigp_host_nanmean(const double* a, int64_t n);
 int sigp_detrend(sigp_handle* h, const double* data, int64_t P, int64_t T, int64_t ncuts, const int64_t* cut_len, double* dt_out, double* trend_out);
 
 /* named scalars of the last operation: "refine_residual" (fp32 engine: max|y - K~ alpha~| / max|y| after the last refinement
- * step), "matrix_bytes" (device bytes held by this handle's matrix / factor buffers), "dist_*" (see sigp_dist_fit). */
+ * step), "matrix_bytes" (device bytes held by this handle's matrix / factor buffers), "cov_slices" (the K slices the last sigp_predict_cov
+ * ran its covariance product with: what "cov_slices" = 0 chose), "dist_*" (see sigp_dist_fit). */
 int sigp_get_stat(sigp_handle* h, const char* name, double* value);
 
 /* K7 (explicit): alpha~ = K~^-1 y  [n]  (north/June1st.py:266; alpha of :271 is alpha~/sigma_f). */
@@ -316,6 +335,9 @@ int sigp_synchronize(sigp_handle* h);
  *                         multiply those 16 rows only (the other rows are zero rows; same results bit for bit; 0 = whole tiles, for A/B timing)
  *   strip_tri [1]         strip solves skip the zero 16-column x 16-k tile-slices of the inverse diagonal blocks (same bits; 0 = the full products, for A/B timing)
  *   group [8]             fits factorised in lockstep per launch (batch path, fp64 and fp32; 1..256)
+ *   cov_slices [0]        sigp_predict_cov: K slices of the covariance product Z Z^T (one workgroup per 128 x 128 tile pair and slice): 0 = auto, the
+ *                         smallest count that gives every CU two workgroups (capped by the n_pad / 128 block columns and by 1 GiB of partial
+ *                         tiles); 1 .. n_pad / 128 = fixed (1: no partials, one workgroup walks the whole K of its tile)
  *   small_tile_threshold [320], tiny_tile_threshold [256], trsm128_threshold [256]   tile-shape switches by tile count
  *   refine_iters [3]      fp32 engine: fp64 refinement steps at most; refine_tol_e [12]: stop once every residual is <= 1e-12 (0 = never early)
  *   refine_stored [1]     fp32 engine: the covariance build also writes K~ in fp64 (8 n^2 bytes per lockstep member, skipped above 40 GB) and the

@@ -13,6 +13,7 @@ OK, NOT_SPD, BAD_ARG, HIP_ERROR = 0, 1, 2, 3
 KERNEL_IDS = {"netdiffusion": 0, "rbf": 1, "matern52": 2}
 KCLASS = {"kbuild": 0, "diag": 1, "trsm": 2, "update_small": 3, "syrk128": 4, "epilogue": 5, "small": 6, "mlii": 7}
 MAX_RIDE = 127
+MAX_COV = 8192                            # SIGP_MAX_COV: test points of one sigp_predict_cov call
 LOO_MODES = {"refit": 0, "fixed": 1}       # SIGP_LOO_REFIT / SIGP_LOO_FIXED
 
 _dp = C.POINTER(C.c_double)
@@ -36,6 +37,7 @@ SIGNATURES = {
     "sigp_fit": (C.c_int, [_h, _dp, _dp]),
     "sigp_predict_ride": (C.c_int, [_h, _dp, _dp]),
     "sigp_predict": (C.c_int, [_h, _dp, _i64, _i64, _dp, _dp]),
+    "sigp_predict_cov": (C.c_int, [_h, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64]),
     "sigp_fit_predict": (C.c_int, [_h, C.c_int, C.c_double, C.c_double, _dp, _i64, _dp, _dp, _dp]),
     "sigp_fit_batch": (C.c_int, [_h, _i64, C.c_int, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dp, _dp,
                                  C.c_int, _dp, _dp, _dp]),

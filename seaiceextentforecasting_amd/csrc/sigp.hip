@@ -25,6 +25,7 @@
 #include "chain_link.hpp"
 #include "smallgp.hpp"
 #include "syrk128.hpp"
+#include "predcov.hpp"
 
 using namespace sigp;
 
@@ -82,6 +83,17 @@ struct sigp_handle {
   KParams* gKps = nullptr; int cap_gKps = 0;  // derivative-covariance parameters of a lockstep MLII group
   double* gSig = nullptr; long cap_gSig = 0;  // MLII gradient (reference kernel): M Sigma~ padded [dp][dp] and X (M Sigma~) [n_pad][dp] --
   double* gT = nullptr; long cap_gT = 0;      // separate from Sig / T, which sigp_predict reads after a fit
+  // sigp_predict_cov (sigp_predcov.inc): solved rows of ALL test points [m_pad][n_pad], padded test rows [m_pad][dp], result [m_pad][m_pad],
+  // split-K partials [S][P][128][128], mean reductions [m_pad/128][512]; reference kernel: Xs Sigma~ [m_pad][dp], its product with Xs^T [m_pad][m_pad]
+  double* covZ = nullptr; long cap_covZ = 0;
+  double* covXs = nullptr; long cap_covXs = 0;
+  double* covC = nullptr; long cap_covC = 0;
+  double* covPart = nullptr; long cap_covPart = 0;
+  double* covRes = nullptr; long cap_covRes = 0;
+  double* covTs = nullptr; long cap_covTs = 0;
+  double* covK = nullptr; long cap_covK = 0;
+  int cov_slices_used = 0;   // ... and the count the last call ran with (sigp_get_stat "cov_slices")
+  int opt_cov_slices = 0;    // K slices of the covariance product of sigp_predict_cov: 0 = auto (two workgroups per CU), 1 .. n_pad/128 fixed
   // fp32 engine (dtype == SIGP_F32): fp32 factor + fp64 iterative refinement (BASELINE configs[4])
   float* fmat = nullptr; float* fdinv = nullptr; float* fZ = nullptr; long cap_f_npad = 0; int cap_f_G = 0;
   float* fU = nullptr; float* fV = nullptr;  // [n_pad][n_pad] each: inverse-transposes of the factor's 2048-column diagonal blocks (fU, upper) and their
@@ -740,7 +752,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 510; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo
+int sigp_version(void) { return 520; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -777,7 +789,8 @@ int sigp_destroy(sigp_handle* h) {
   (void)hipDeviceSynchronize();
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
-  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out};
+  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
+                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
   if (h->sm_probs) (void)hipFree(h->sm_probs);
@@ -832,6 +845,12 @@ int sigp_set_option(sigp_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "c_dma")) {
     if (!DBG_MASK) return fail(h, SIGP_BAD_ARG, "c_dma is a measurement switch of libsigp_debug.so");
     h->opt_c_dma = value != 0; return SIGP_OK;
+  }
+  if (!strcmp(name, "cov_slices")) {
+    // (before any data is staged the upper end is not known yet: sigp_predict_cov checks it again)
+    if (value < 0 || value > (1 << 20) || (h->n > 0 && value > h->n_pad / NB))
+      return fail(h, SIGP_BAD_ARG, "cov_slices: 0 (auto) or 1 .. n_pad / 128 block columns of the fit required (got %lld)", (long long)value);
+    h->opt_cov_slices = (int)value; return SIGP_OK;
   }
   if (!strcmp(name, "diag_tiles")) { h->opt_diag_tiles = value != 0; return SIGP_OK; }
   if (!strcmp(name, "ride_tiles")) { h->opt_ride_tiles = value != 0; return SIGP_OK; }
@@ -1797,6 +1816,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
   return SIGP_OK;
 }
 
+#include "sigp_predcov.inc"   // sigp_predict_cov: joint predictive covariance at new points
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"
@@ -1812,6 +1832,7 @@ extern "C" {
 int sigp_get_stat(sigp_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return SIGP_BAD_ARG;
   if (!strcmp(name, "refine_residual")) { *value = h->refine_resid; return SIGP_OK; }
+  if (!strcmp(name, "cov_slices")) { *value = h->cov_slices_used; return SIGP_OK; }
   if (!strcmp(name, "matrix_bytes")) {
     double b = 0;
     for (const auto& s : h->slots) if (s.mat) b += (double)s.capB * (double)(s.cap_npad + RIDE) * (double)s.cap_npad * sizeof(double);

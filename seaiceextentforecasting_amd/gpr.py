@@ -172,8 +172,11 @@ class GPR:
         return self
 
     # ---- predict (north/June1st.py:272-277) ----------------------------------------------------
-    def predict(self, Xs):
-        """(fmean [m], fvar [m]); fvar is the variance of y*, i.e. includes sigma_n (:273, :277)."""
+    def predict(self, Xs, return_cov=False):
+        """(fmean [m], fvar [m]); fvar is the variance of y*, i.e. includes sigma_n (:273, :277).
+        ``return_cov=True``: (fmean [m], cov [m, m]) -- the joint covariance of y* at all test points (``predict_cov``), whose diagonal is fvar."""
+        if return_cov:
+            return self.predict_cov(Xs, noise=True)
         if not self._fitted:
             raise RuntimeError("predict: call fit() first")
         Xs = L.f64(np.atleast_2d(Xs), 2)
@@ -185,6 +188,50 @@ class GPR:
         mean, var = np.zeros(m), np.zeros(m)
         self._check(self._lib.sigp_predict(self._h, L.ptr(Xs), m, Xs.shape[1], L.ptr(mean), L.ptr(var)), "predict")
         return mean, var
+
+    # ---- joint posterior at new points -------------------------------------------------------------
+    def predict_cov(self, Xs, noise=True):
+        """(mean [m], cov [m, m]): the joint Gaussian posterior at the rows of ``Xs`` (``sigp_predict_cov``; 1 <= m <= 8192) from the factor on
+        the device: cov = sigma_f (k~** + [noise] sn~ I - k~* K~^-1 k~*^T).  ``noise=True``: of the observations y* (diag(cov) is ``predict``'s
+        fvar); ``noise=False``: of the latent function f*.  The mean is ``predict``'s, bit for bit; cov is exactly symmetric.  An error bar for
+        any linear function w of the forecasts is w^T cov w.  fp64 engine only.  The fit stays as it is."""
+        Xs = L.f64(np.atleast_2d(Xs), 2)
+        d = getattr(self, "d", None)
+        if d is not None and Xs.shape[1] != d:
+            raise ValueError("Xs must have %d columns" % d)
+        m = Xs.shape[0]
+        if m < 1 or m > L.MAX_COV:
+            raise ValueError("predict_cov: 1 <= m <= %d test points required (m = %d)" % (L.MAX_COV, m))
+        mean, cov = np.zeros(m), np.zeros((m, m))
+        self._check(self._lib.sigp_predict_cov(self._h, L.ptr(Xs), m, Xs.shape[1], int(bool(noise)), L.ptr(mean), L.ptr(cov), m), "predict_cov")
+        return mean, cov
+
+    def sample(self, Xs, size=1, noise=False, seed=None, z=None):
+        """``size`` coherent draws [size, m] from the joint posterior at ``Xs``: mean + chol(cov) z with z [size, m] standard normals
+        (``np.random.default_rng(seed)`` unless given).  The m x m factorisation runs on the host (``np.linalg.cholesky``).  A latent covariance
+        (``noise=False``) can be singular to rounding (repeated or nearly repeated test points): jitter * max(diag) is then added to its
+        diagonal, jitter = 1e-12, 1e-11, ... up to 1e-6, before LinAlgError is raised; the value used is left in ``sample_jitter_`` (0.0: none)."""
+        mean, cov = self.predict_cov(Xs, noise=noise)
+        m = mean.shape[0]
+        if z is None:
+            z = np.random.default_rng(seed).standard_normal((int(size), m))
+        else:
+            z = np.asarray(z, dtype=np.float64)
+            if z.ndim != 2 or z.shape[1] != m:
+                raise ValueError("z must be [size, %d]" % m)
+        scale = float(np.max(np.diag(cov)))
+        Lc = None
+        for jitter in (0.0,) + (() if noise else tuple(10.0 ** e for e in range(-12, -5))):
+            try:
+                Lc = np.linalg.cholesky(cov + (jitter * scale) * np.eye(m) if jitter else cov)
+                break
+            except np.linalg.LinAlgError:
+                pass
+        if Lc is None:
+            raise LinAlgError("sample: the %s covariance of the test points is not positive definite%s"
+                              % ("predictive" if noise else "latent", "" if noise else " even with a relative jitter of 1e-6"))
+        self.sample_jitter_ = jitter
+        return mean + z @ Lc.T
 
     # ---- leave-one-out cross-validation ----------------------------------------------------------
     def loo(self, sigma_f="refit"):
