@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -238,6 +238,26 @@ int sigp_loo(sigp_handle* h, int sigma_mode, double* mean, double* var, double* 
  * +inf scores and NaN rows (north/June1st.py:254-256); the other members are not affected. */
 int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde,
                    int sigma_mode, double* mean, double* var, int64_t nstride, double* score);
+/* The leave-one-out scores AND their exact derivatives with respect to (log ell, log sn~) (Rasmussen & Williams 5.4.2), so that an optimiser
+ * can minimise them instead of searching a grid.  With P = K~^-1, a = P y, g_i = P_ii and D = dK~/dtheta:  t = D a, b = P t, e = a^T t,
+ * c_i = [P D P]_ii;  dr_i = -b_i/g_i + a_i c_i/g_i^2;  ds_i = -e/n (FIXED) or (-e + 2 a_i b_i/g_i - a_i^2 c_i/g_i^2)/(n - 1) (REFIT);
+ * dvar_i = ds_i/g_i + s_i c_i/g_i^2;  d nlpd = sum_i dvar_i/(2 var_i) + r_i dr_i/var_i - r_i^2 dvar_i/(2 var_i^2);  d sse = sum_i 2 r_i dr_i.
+ * On top of sigp_loo's work (the same launches: mean, var and score carry the same bits): K~^-1 = U U^T (n^3/3), dK~/dlog ell from the
+ * covariance build, and the one new cubic step c = diag(K~^-1 dK~ K~^-1) as a triangular 128-tile product of n^3 flops (half of the full
+ * product); everything else is n^2 passes and fixed-order sums (no atomics: the same bits on every run).  log sn~ needs no cubic work.
+ * Device work is accounted under SIGP_KC_MLII.  Memory: 8 n_pad^2 bytes each for the factor, L~^-T, K~^-1 and dK~ PER MEMBER (the lockstep
+ * entry holds dK~ per member, which sigp_nlml_grad_batch avoids).
+ * sigp_loo_grad: after sigp_fit / sigp_fit_predict; mean / var [n] may both be NULL; score [2] as sigp_loo;
+ * grad [4] = d nlpd/d(log ell, log sn~), d sse/d(log ell, log sn~).  MSigma = M @ Sigma~ [N][ldsigma]: reference kernel only (required there,
+ * and the fit must have come from sigp_fit_predict, which is told ell: d/dlog ell = ell d/dell), else NULL.  Errors as sigp_loo (fp32 handle,
+ * sharded fit, n < 2, not fitted: SIGP_BAD_ARG).  The fit is only read: sigp_predict / sigp_get_alpha / sigp_loo afterwards return the bits
+ * they returned before.
+ * Not covered: gradients in sigp_small_run_loo (the one-workgroup kernel), sharded fits, the fp32 engine, per-feature length scales. */
+int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t ldsigma, double* mean, double* var, double* score, double* grad);
+/* Lockstep groups on the resident batch data, arguments as sigp_loo_batch (RBF / Matern only); grad [count][4].  A non-SPD member gets +inf
+ * scores and gradients and NaN rows; the other members are not affected. */
+int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde,
+                        int sigma_mode, double* mean, double* var, int64_t nstride, double* score, double* grad);
 /* sigp_small_run with the leave-one-out cross-validation of every fit in the SAME single launch (L~^-1 formed in LDS over L~ as in
  * sigp_small_run_grad): out6 [nprob][6] = sigma_f, nlML, info, sigma_n, nlpd, sse; mean / var as in sigp_small_run;
  * loo_mean / loo_var [nprob][nstride >= largest n of the upload], entries beyond a set's n = NaN.  info > 0: nlpd = sse = +inf and NaN rows.
@@ -335,6 +355,8 @@ int sigp_synchronize(sigp_handle* h);
  *                         multiply those 16 rows only (the other rows are zero rows; same results bit for bit; 0 = whole tiles, for A/B timing)
  *   strip_tri [1]         strip solves skip the zero 16-column x 16-k tile-slices of the inverse diagonal blocks (same bits; 0 = the full products, for A/B timing)
  *   group [8]             fits factorised in lockstep per launch (batch path, fp64 and fp32; 1..256)
+ *   loo_grad_tri [1]      sigp_loo_grad: the cubic step multiplies the upper triangle of dK~ only (n^3 flops; 0 = the full product, 2 n^3, for A/B timing:
+ *                         another summation order, the same result to rounding)
  *   cov_slices [0]        sigp_predict_cov: K slices of the covariance product Z Z^T (one workgroup per 128 x 128 tile pair and slice): 0 = auto, the
  *                         smallest count that gives every CU two workgroups (capped by the n_pad / 128 block columns and by 1 GiB of partial
  *                         tiles); 1 .. n_pad / 128 = fixed (1: no partials, one workgroup walks the whole K of its tile)

@@ -26,6 +26,7 @@
 #include "smallgp.hpp"
 #include "syrk128.hpp"
 #include "predcov.hpp"
+#include "loograd.hpp"
 
 using namespace sigp;
 
@@ -80,6 +81,7 @@ struct sigp_handle {
   double* gK = nullptr; long cap_gK = 0;
   double* gD = nullptr; long cap_gD = 0;
   double* gPart = nullptr; long cap_gPart = 0;
+  double* gV = nullptr; long cap_gV = 0;      // sigp_loo_grad: per-member vectors of the gradient pass (loograd.hpp: LooGradVecs)
   KParams* gKps = nullptr; int cap_gKps = 0;  // derivative-covariance parameters of a lockstep MLII group
   double* gSig = nullptr; long cap_gSig = 0;  // MLII gradient (reference kernel): M Sigma~ padded [dp][dp] and X (M Sigma~) [n_pad][dp] --
   double* gT = nullptr; long cap_gT = 0;      // separate from Sig / T, which sigp_predict reads after a fit
@@ -93,6 +95,7 @@ struct sigp_handle {
   double* covTs = nullptr; long cap_covTs = 0;
   double* covK = nullptr; long cap_covK = 0;
   int cov_slices_used = 0;   // ... and the count the last call ran with (sigp_get_stat "cov_slices")
+  int opt_loo_grad_tri = 1; // sigp_loo_grad: the product for diag(K~^-1 dK~ K~^-1) takes the triangular form D' K~^-1 (n^3 flops); 0 = the full product dK~ K~^-1 (2 n^3: A/B timing)
   int opt_cov_slices = 0;    // K slices of the covariance product of sigp_predict_cov: 0 = auto (two workgroups per CU), 1 .. n_pad/128 fixed
   // fp32 engine (dtype == SIGP_F32): fp32 factor + fp64 iterative refinement (BASELINE configs[4])
   float* fmat = nullptr; float* fdinv = nullptr; float* fZ = nullptr; long cap_f_npad = 0; int cap_f_G = 0;
@@ -752,7 +755,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 520; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov
+int sigp_version(void) { return 530; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -789,7 +792,7 @@ int sigp_destroy(sigp_handle* h) {
   (void)hipDeviceSynchronize();
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
-  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
+  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
                     h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
@@ -852,6 +855,7 @@ int sigp_set_option(sigp_handle* h, const char* name, int64_t value) {
       return fail(h, SIGP_BAD_ARG, "cov_slices: 0 (auto) or 1 .. n_pad / 128 block columns of the fit required (got %lld)", (long long)value);
     h->opt_cov_slices = (int)value; return SIGP_OK;
   }
+  if (!strcmp(name, "loo_grad_tri")) { h->opt_loo_grad_tri = value != 0; return SIGP_OK; }
   if (!strcmp(name, "diag_tiles")) { h->opt_diag_tiles = value != 0; return SIGP_OK; }
   if (!strcmp(name, "ride_tiles")) { h->opt_ride_tiles = value != 0; return SIGP_OK; }
   if (!strcmp(name, "strip_tri")) { h->opt_strip_tri = value != 0; return SIGP_OK; }
@@ -1159,6 +1163,7 @@ int sigp_fit_predict(sigp_handle* h, int kernel_id, double ell, double sn_tilde,
     if (!Sigma) return fail(h, SIGP_BAD_ARG, "fit_predict: Sigma required for the reference kernel");
     rc = sigp_kernel_build_from_sigma(h, Sigma, ldsigma, sn_tilde);
     if (rc) return rc;
+    h->ell = ell;              // the build is given Sigma~ alone; sigp_loo_grad needs l itself (d/dlog l = l d/dl)
   } else {
     if (kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "bad kernel_id");
     if (!(ell > 0) || !(sn_tilde >= 0)) return fail(h, SIGP_BAD_ARG, "ell > 0 and sn_tilde >= 0 required");
@@ -1816,6 +1821,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
   return SIGP_OK;
 }
 
+#include "sigp_loograd.inc"   // sigp_loo_grad, sigp_loo_grad_batch: exact gradients of the leave-one-out scores
 #include "sigp_predcov.inc"   // sigp_predict_cov: joint predictive covariance at new points
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 

@@ -234,7 +234,7 @@ class GPR:
         return mean + z @ Lc.T
 
     # ---- leave-one-out cross-validation ----------------------------------------------------------
-    def loo(self, sigma_f="refit"):
+    def loo(self, sigma_f="refit", grad=False):
         """Leave-one-out cross-validation of the current fit with (l, sn~) (and, for the reference kernel, M and the feature
         columns) held: what ``fit`` on the other n - 1 points followed by ``predict`` of the left-out point returns, for every
         point, from the factor already on the device (``sigp_loo``: L~^-T and one pass over it; about the price of a second fit).
@@ -244,20 +244,36 @@ class GPR:
         sigma_f='fixed'  the full fit's sigma_f is kept (Rasmussen & Williams eq. 5.12).  The means do not depend on the mode.
 
         Returns dict(mean [n], var [n] (includes the noise, like fvar), nlpd, sse, mse, skill) with
-        skill = 1 - sse / sum((y - mean(y))^2).  The fit stays as it is: ``predict`` afterwards works unchanged."""
+        skill = 1 - sse / sum((y - mean(y))^2).  The fit stays as it is: ``predict`` afterwards works unchanged.
+
+        ``grad=True`` (``sigp_loo_grad``) adds nlpd_grad [2] and sse_grad [2], the exact derivatives of the two scores with respect to
+        (log l, log sn~); every other entry carries the same bits as without."""
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
         if not self._fitted:
             raise RuntimeError("loo: call fit() first")
         mean, var, score = np.zeros(self.n), np.zeros(self.n), np.zeros(2)
-        self._check(self._lib.sigp_loo(self._h, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), L.ptr(score)), "loo")
+        g4 = None
+        if grad:
+            MSig = None
+            if self.kernel == "netdiffusion":
+                MSig = L.f64(self._sigma(self.ell_, with_derivative=True)[1], 2)
+            g4 = np.zeros(4)
+            self._check(self._lib.sigp_loo_grad(self._h, L.LOO_MODES[sigma_f], L.ptr(MSig), 0 if MSig is None else MSig.shape[1], L.ptr(mean), L.ptr(var),
+                                                L.ptr(score), L.ptr(g4)), "loo")
+        else:
+            self._check(self._lib.sigp_loo(self._h, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), L.ptr(score)), "loo")
         nlpd, sse = float(score[0]), float(score[1])
-        return dict(mean=mean, var=var, nlpd=nlpd, sse=sse, mse=sse / self.n, skill=1.0 - sse / float(np.sum((self._y - self._y.mean()) ** 2)))
+        res = dict(mean=mean, var=var, nlpd=nlpd, sse=sse, mse=sse / self.n, skill=1.0 - sse / float(np.sum((self._y - self._y.mean()) ** 2)))
+        if grad:
+            res["nlpd_grad"], res["sse_grad"] = g4[:2].copy(), g4[2:].copy()
+        return res
 
-    def loo_batch(self, ell, sn_tilde, first=0, sigma_f="refit", group=8, predictions=True):
+    def loo_batch(self, ell, sn_tilde, first=0, sigma_f="refit", group=8, predictions=True, grad=False):
         """``loo`` for many (data set, l, sn~) on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern), in
         lockstep groups of ``group`` fits (``sigp_loo_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F])
-        and, with ``predictions``, mean [F, n], var [F, n]; a non-SPD member gets +inf / NaN (north/June1st.py:254-256)."""
+        and, with ``predictions``, mean [F, n], var [F, n]; a non-SPD member gets +inf / NaN (north/June1st.py:254-256).
+        ``grad=True`` (``sigp_loo_grad_batch``) adds nlpd_grad [F, 2] and sse_grad [F, 2] with respect to (log l, log sn~)."""
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
         if self.kernel == "netdiffusion":
@@ -274,10 +290,17 @@ class GPR:
         score = np.zeros((F, 2))
         mean = np.zeros((F, n)) if predictions else None
         var = np.zeros((F, n)) if predictions else None
-        self._check(self._lib.sigp_loo_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
-                                             L.ptr(score)), "loo_batch")
+        if grad:
+            g4 = np.zeros((F, 4))
+            self._check(self._lib.sigp_loo_grad_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                                      L.ptr(score), L.ptr(g4)), "loo_batch")
+        else:
+            self._check(self._lib.sigp_loo_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                                 L.ptr(score)), "loo_batch")
         self._fitted = False
         res = dict(nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
+        if grad:
+            res["nlpd_grad"], res["sse_grad"] = g4[:, :2].copy(), g4[:, 2:].copy()
         if predictions:
             res["mean"], res["var"] = mean, var
         return res
@@ -348,15 +371,55 @@ class GPR:
         self._check(rc, "nlml")
         return np.float64(val.value), (None if grad is None else g)
 
-    def optimize(self, theta0, method="L-BFGS-B", grad="exact", **kw):
+    def loo_objective(self, theta, criterion="loo_nlpd", sigma_f="refit"):
+        """A leave-one-out score as an optimiser's objective: theta = (log l, log sn~) -> (value, grad[2]) with value = the
+        leave-one-out negative log predictive density (``criterion='loo_nlpd'``) or sum of squared errors (``'loo_sse'``) of the fit at
+        exp(theta), and its exact gradient (``loo(grad=True)``).  A non-SPD K~ or an overflowing exp(theta) gives ``(inf, [inf, inf])``,
+        like ``nlml``.  Afterwards the handle is fitted at exp(theta)."""
+        if criterion not in L.LOO_CRITERIA:
+            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if not self._has_data:
+            raise RuntimeError("loo_objective: no data staged; call fit() or set_data() first")
+        theta = np.asarray(theta, dtype=np.float64).reshape(2)
+        inf2 = (np.inf, np.asarray([np.inf, np.inf]))
+        with np.errstate(over="ignore"):
+            ell, sn = float(np.exp(theta[0])), float(np.exp(theta[1]))
+        if not (np.isfinite(ell) and np.isfinite(sn) and ell > 0):
+            return inf2
+        try:
+            with np.errstate(over="raise", invalid="raise"):
+                self.refit(ell, sn)
+                r = self.loo(sigma_f, grad=True)
+        except (LinAlgError, OverflowError, FloatingPointError):
+            return inf2
+        key = L.LOO_CRITERIA[criterion]
+        if not (np.isfinite(r[key]) and np.all(np.isfinite(r[key + "_grad"]))):
+            return inf2
+        return np.float64(r[key]), r[key + "_grad"]
+
+    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", **kw):
         """The reference's commented-out optimiser call (north/June1st.py:259-262:
         ``minimize(MLII, x0=[log l0, log sn0], method='CG', jac=True)``) against the device engine.
         ``grad='exact'`` (default) feeds the true derivative of the profiled nlML; ``grad='ref'`` reproduces the
         reference's MLII contract verbatim (its "gradient" is not the derivative, so CG stalls as in SURVEY App. C-7).
-        Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
+        ``criterion='loo_nlpd'`` / ``'loo_sse'`` minimises that leave-one-out score instead (``loo_objective`` with ``sigma_f``; grad
+        'exact' or None).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
         from scipy.optimize import minimize
 
-        if grad is None:                  # value only: scipy differences it numerically
+        if criterion != "nlml":
+            if criterion not in L.LOO_CRITERIA:
+                raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+            if grad not in (None, "exact"):
+                raise ValueError("a leave-one-out criterion takes grad='exact' or None")
+
+            def fun(th):
+                v, g = self.loo_objective(th, criterion, sigma_f)
+                return (float(v), np.asarray(g, dtype=np.float64)) if grad is not None else float(v)
+
+            res = minimize(fun, np.asarray(theta0, dtype=np.float64), method=method, jac=grad is not None, **kw)
+        elif grad is None:                  # value only: scipy differences it numerically
             res = minimize(lambda th: float(self.nlml(th, grad=None)[0]), np.asarray(theta0, dtype=np.float64), method=method, jac=False, **kw)
         else:
             def fun(th):
@@ -620,7 +683,22 @@ class GPR:
         self._fitted = False
         return val, (g if grad is not None else None)
 
-    def optimize_batch(self, X, y, theta0, group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0, M=None, expm="eigh", method=None):
+    def _loo_objective_batch(self, theta, criterion, sigma_f, group):
+        """(value [F], grad [F, 2]) of a leave-one-out score for theta [F, 2] on the staged data sets, one device call (``loo_batch``)."""
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        with np.errstate(over="ignore"):
+            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
+        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
+        r = self.loo_batch(np.where(ok, ell, 1.0), np.where(ok, sn, 1.0), sigma_f=sigma_f, group=group, predictions=False, grad=True)
+        key = L.LOO_CRITERIA[criterion]
+        f, g = r[key].copy(), r[key + "_grad"].copy()
+        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
+        f[~ok] = np.inf
+        g[~ok] = np.inf
+        return f, g
+
+    def optimize_batch(self, X, y, theta0, group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0, M=None, expm="eigh", method=None,
+                       criterion="nlml", sigma_f="refit"):
         """The reference's commented-out ``minimize(MLII, x0, method='CG', jac=True)`` (north/June1st.py:259-262) for EVERY data set
         of a retrospective run at once: X [B, n, d], y [B, n], theta0 [B, 2] (or [2]) -> dict(x [B, 2], fun [B], nit [B],
         converged [B], nfev = device calls).  The state of every data set lives on the host and each round is ONE device call for all
@@ -633,6 +711,11 @@ class GPR:
         extra points are free there each round carries several step lengths and their finite-difference neighbours: a modified-Newton
         iteration with the line search inside the launch."""
         from .optim import bfgs_lockstep, newton_lockstep
+        if criterion != "nlml" and criterion not in L.LOO_CRITERIA:
+            raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+        if criterion != "nlml" and self.kernel == "netdiffusion":
+            raise ValueError("optimize_batch: the leave-one-out criteria cover the RBF / Matern kernels; the reference kernel's batch runs one workgroup per "
+                             "fit (sigp_small_run_loo), which has no gradients -- optimise its data sets one at a time with optimize(criterion=...)")
         if self.kernel == "netdiffusion":
             self.upload_batch(X, y, None, M=M)
             B = len(self._small_ids)
@@ -647,6 +730,8 @@ class GPR:
         B = X.shape[0]
         self.upload_batch(X, y, None, group=group, concurrency=1)
         th0 = np.broadcast_to(np.asarray(theta0, dtype=np.float64), (B, 2))
+        if criterion != "nlml":   # the same lockstep BFGS on a leave-one-out score: one sigp_loo_grad_batch call per round
+            return bfgs_lockstep(lambda t: self._loo_objective_batch(t, criterion, sigma_f, group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
         return bfgs_lockstep(lambda t: self.nlml_batch(t, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
 
     def nlml_grid(self, X, y, ells, sns, concurrency=2, group=8, M=None):
