@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -265,6 +265,41 @@ int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
 int sigp_small_run_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode,
                        double* out6, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride);
 
+/* Leave-block-out cross-validation with the hyper-parameters held: K-fold / h-block / hv-block folds of CONSECUTIVE rows (the rows are
+ * consecutive years; leaving one year out keeps its serially correlated neighbours in the training set), from ONE factorisation.
+ * block >= 1, gap >= 0: fold f SCORES the rows [c0, c1) = [f block, min(n, (f + 1) block)) and REMOVES the window
+ * S_f = [max(0, c0 - gap), min(n, c1 + gap)) from training (the gap rows are removed but not scored); every row is scored by exactly one
+ * fold, windows overlap when gap > 0, and their sizes differ at the two ends and in the last fold.  With P = K~^-1 and A~ = P y
+ * (DESIGN.md section 2):  y_S - mean_S = P_SS^-1 A~_S,  Cov_S = s_S P_SS^-1 (includes the noise, like fvar),
+ * s_S = (y^T A~ - A~_S^T P_SS^-1 A~_S) / (n - |S|) (SIGP_LOO_REFIT: sigma_f re-profiled without S -- what a real refit without the rows of S
+ * returns) or y^T A~ / n (SIGP_LOO_FIXED).  mean [n], var [n] (var_i = s_S [P_SS^-1]_ii, the marginal variance; no joint block density is
+ * defined), score [2] = nlpd, sse as sigp_loo's, added in a fixed order.  block = 1, gap = 0 is leave-one-out.  A shuffled K-fold is the
+ * same call after the caller permutes the rows before the fit.
+ * Limits: block + 2 gap <= SIGP_CV_MAX_WINDOW (one diagonal block; SIGP_CV_SMALL_MAX_WINDOW in sigp_small_run_cv), and every fold must leave
+ * a training row (n - |S_f| >= 1): otherwise SIGP_BAD_ARG, as for an fp32 handle, a sharded fit, no fit, or n < 2.
+ * Cost on top of sigp_loo's L~^-T: the strip products P_SS = U_S U_S^T of the rows U[S, min S .. n) (2 |S|^2 (n - min S) flops per fold on
+ * the fp64 matrix pipe, split over "cv_slices" K slices and added in a fixed order: no atomics, the same bits on every run), a |S| x |S|
+ * Cholesky per fold by the factorisation's own diagonal-block kernel, and two short solves.  Device work is accounted under SIGP_KC_MLII
+ * (the triangular inversion, then four entries per pass of at most 1024 (member, fold) pairs).  Memory on top of sigp_loo: per pair of a
+ * pass the partials (slices x (window rounded up to 16)^2 doubles) and 2 x 8 x 128^2 bytes.
+ * sigp_cv: after sigp_fit / sigp_fit_predict, every kernel.  The fit is only read: sigp_predict / sigp_get_alpha / sigp_loo afterwards return
+ * the bits they returned before.  A fold whose P_SS fails its pivot test leaves NaN in its rows and +inf in both scores. */
+enum { SIGP_CV_MAX_WINDOW = 128, SIGP_CV_SMALL_MAX_WINDOW = 32 };
+int sigp_cv(sigp_handle* h, int64_t block, int64_t gap, int sigma_mode, double* mean, double* var, double* score);
+/* Lockstep groups on the resident batch data, argument conventions of sigp_loo_batch (RBF / Matern only; mean / var [count][nstride >= n]
+ * may both be NULL; score [count][2]).  A member with a non-SPD K~, or one of whose P_SS fails its pivot test, gets +inf scores and NaN
+ * rows; the other members are not affected. */
+int sigp_cv_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde, int64_t block,
+                  int64_t gap, int sigma_mode, double* mean, double* var, int64_t nstride, double* score);
+/* sigp_small_run with the leave-block-out cross-validation of every fit in the SAME single launch (the reference kernel's batch; L~^-1 in
+ * LDS as in sigp_small_run_loo, then per fold P_SS from its columns, a |S| x |S| Cholesky and the solves in LDS): out6 [nprob][6] =
+ * sigma_f, nlML, info, sigma_n, nlpd, sse; cv_mean / cv_var [nprob][nstride >= largest n of the upload], NaN beyond a set's n.
+ * block + 2 gap <= SIGP_CV_SMALL_MAX_WINDOW; every fold of every named data set must leave a training row.  info > 0 or a failed pivot of
+ * a P_SS: nlpd = sse = +inf and NaN rows. */
+int sigp_small_run_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block,
+                      int64_t gap, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var,
+                      int64_t nstride);
+
 /* One large fit sharded over the GPUs of a node (BASELINE configs[3] fp64, configs[4] fp32 + fp64 refinement): 1-D block-cyclic
  * ownership of outer panels (W column blocks of 128; panel q belongs to rank q % nranks), OWNER-ONLY storage -- a rank allocates,
  * builds and updates only the block columns of its own panels (per-rank matrix bytes ~ 1/nranks) -- and the block-row panel
@@ -360,6 +395,9 @@ int sigp_synchronize(sigp_handle* h);
  *   cov_slices [0]        sigp_predict_cov: K slices of the covariance product Z Z^T (one workgroup per 128 x 128 tile pair and slice): 0 = auto, the
  *                         smallest count that gives every CU two workgroups (capped by the n_pad / 128 block columns and by 1 GiB of partial
  *                         tiles); 1 .. n_pad / 128 = fixed (1: no partials, one workgroup walks the whole K of its tile)
+ *   cv_slices [0]         sigp_cv / sigp_cv_batch: K slices of the strip product U_S U_S^T (one workgroup per fold, slice and member): 0 = auto, the
+ *                         smallest count that gives every CU two workgroups from one member's folds (at most 32; the same for a fit and for a lockstep group); otherwise the count, clipped to the 32-column stages
+ *                         of the fit (1: one workgroup walks the whole strip); sigp_get_stat "cv_slices" = what the last call ran with
  *   small_tile_threshold [320], tiny_tile_threshold [256], trsm128_threshold [256]   tile-shape switches by tile count
  *   refine_iters [3]      fp32 engine: fp64 refinement steps at most; refine_tol_e [12]: stop once every residual is <= 1e-12 (0 = never early)
  *   refine_stored [1]     fp32 engine: the covariance build also writes K~ in fp64 (8 n^2 bytes per lockstep member, skipped above 40 GB) and the

@@ -15,6 +15,7 @@ KCLASS = {"kbuild": 0, "diag": 1, "trsm": 2, "update_small": 3, "syrk128": 4, "e
 MAX_RIDE = 127
 MAX_COV = 8192                            # SIGP_MAX_COV: test points of one sigp_predict_cov call
 LOO_MODES = {"refit": 0, "fixed": 1}       # SIGP_LOO_REFIT / SIGP_LOO_FIXED
+CV_MAX_WINDOW, CV_SMALL_MAX_WINDOW = 128, 32   # SIGP_CV_MAX_WINDOW / SIGP_CV_SMALL_MAX_WINDOW: widest window block + 2 gap of a fold
 LOO_CRITERIA = {"loo_nlpd": "nlpd", "loo_sse": "sse"}   # optimiser criteria -> keys of GPR.loo's result
 
 _dp = C.POINTER(C.c_double)
@@ -64,6 +65,9 @@ SIGNATURES = {
     "sigp_loo_grad": (C.c_int, [_h, C.c_int, _dp, _i64, _dp, _dp, _dp, _dp]),
     "sigp_loo_grad_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _i64, _dp, _dp]),
     "sigp_small_run_loo": (C.c_int, [_h, _i64, _ip64, _dp, _dp, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
+    "sigp_cv": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _dp]),
+    "sigp_cv_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64, _dp]),
+    "sigp_small_run_cv": (C.c_int, [_h, _i64, _ip64, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_dist_unique_id": (C.c_int, [C.c_void_p]),
     "sigp_dist_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),
     "sigp_dist_init_transport": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),

@@ -27,6 +27,7 @@
 #include "syrk128.hpp"
 #include "predcov.hpp"
 #include "loograd.hpp"
+#include "blockcv.hpp"
 
 using namespace sigp;
 
@@ -94,6 +95,12 @@ struct sigp_handle {
   double* covRes = nullptr; long cap_covRes = 0;
   double* covTs = nullptr; long cap_covTs = 0;
   double* covK = nullptr; long cap_covK = 0;
+  // sigp_cv / sigp_cv_batch (sigp_blockcv.inc): split-K partials of the strip products, the fold blocks P_SS and their inverse factors, a_S + info
+  double* cvPart = nullptr; long cap_cvPart = 0;
+  double* cvBlk = nullptr; long cap_cvBlk = 0;
+  double* cvVec = nullptr; long cap_cvVec = 0;
+  int opt_cv_slices = 0;     // K slices of the strip product of sigp_cv: 0 = auto (two workgroups per CU, at most 32), otherwise the count (clipped to the 32-column stages of the fit)
+  int cv_slices_used = 0;    // ... and the count the last call ran with (sigp_get_stat "cv_slices")
   int cov_slices_used = 0;   // ... and the count the last call ran with (sigp_get_stat "cov_slices")
   int opt_loo_grad_tri = 1; // sigp_loo_grad: the product for diag(K~^-1 dK~ K~^-1) takes the triangular form D' K~^-1 (n^3 flops); 0 = the full product dK~ K~^-1 (2 n^3: A/B timing)
   int opt_cov_slices = 0;    // K slices of the covariance product of sigp_predict_cov: 0 = auto (two workgroups per CU), 1 .. n_pad/128 fixed
@@ -755,7 +762,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 530; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch
+int sigp_version(void) { return 540; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -793,7 +800,7 @@ int sigp_destroy(sigp_handle* h) {
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
   double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
-                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK};
+                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
   if (h->sm_probs) (void)hipFree(h->sm_probs);
@@ -854,6 +861,10 @@ int sigp_set_option(sigp_handle* h, const char* name, int64_t value) {
     if (value < 0 || value > (1 << 20) || (h->n > 0 && value > h->n_pad / NB))
       return fail(h, SIGP_BAD_ARG, "cov_slices: 0 (auto) or 1 .. n_pad / 128 block columns of the fit required (got %lld)", (long long)value);
     h->opt_cov_slices = (int)value; return SIGP_OK;
+  }
+  if (!strcmp(name, "cv_slices")) {
+    if (value < 0 || value > 4096) return fail(h, SIGP_BAD_ARG, "cv_slices: 0 (auto) or 1 .. 4096 slices required (got %lld)", (long long)value);
+    h->opt_cv_slices = (int)value; return SIGP_OK;
   }
   if (!strcmp(name, "loo_grad_tri")) { h->opt_loo_grad_tri = value != 0; return SIGP_OK; }
   if (!strcmp(name, "diag_tiles")) { h->opt_diag_tiles = value != 0; return SIGP_OK; }
@@ -1823,6 +1834,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 
 #include "sigp_loograd.inc"   // sigp_loo_grad, sigp_loo_grad_batch: exact gradients of the leave-one-out scores
 #include "sigp_predcov.inc"   // sigp_predict_cov: joint predictive covariance at new points
+#include "sigp_blockcv.inc"   // sigp_cv, sigp_cv_batch: leave-block-out cross-validation
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"
@@ -1839,6 +1851,7 @@ int sigp_get_stat(sigp_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return SIGP_BAD_ARG;
   if (!strcmp(name, "refine_residual")) { *value = h->refine_resid; return SIGP_OK; }
   if (!strcmp(name, "cov_slices")) { *value = h->cov_slices_used; return SIGP_OK; }
+  if (!strcmp(name, "cv_slices")) { *value = h->cv_slices_used; return SIGP_OK; }
   if (!strcmp(name, "matrix_bytes")) {
     double b = 0;
     for (const auto& s : h->slots) if (s.mat) b += (double)s.capB * (double)(s.cap_npad + RIDE) * (double)s.cap_npad * sizeof(double);

@@ -1,0 +1,171 @@
+// sigp_cv, sigp_cv_batch: leave-block-out cross-validation (K-fold / h-block / hv-block folds of consecutive rows) from one factorisation.
+// Included inside extern "C" of sigp.hip.  Kernels and the closed form: blockcv.hpp.
+//
+//   U = L~^-T                      trtri_levels, as sigp_loo (n^3/3)
+//   per fold f, window S_f:        P_SS = U_S U_S^T  (2 |S|^2 (n - min S) flops, split over K slices), a_S = U_S z;
+//                                  P_SS = M M^T and X = M^-1 by the factorisation's own diagonal-block kernel; the closing solves
+//   score                          loo_sum_kernel over the n terms
+//
+// Only reads the factor, the ride rows and the fit's state.  Folds are worked off in passes of at most CV_PASS_BLOCKS (member, fold) pairs,
+// which bounds the workspaces whatever n / block is (doubles): cvPart pairs S (wp^2 + wp), cvBlk 2 pairs 128^2, cvVec pairs (128 + 1).
+
+constexpr long CV_PASS_BLOCKS = 1024;
+
+static const char* cv_check_folds(long n, int64_t block, int64_t gap, int64_t maxw) {
+  if (block < 1 || gap < 0) return "block >= 1 and gap >= 0 required";
+  if (block > maxw || gap > maxw || block + 2 * gap > maxw) return "the window block + 2 gap exceeds the widest one supported";
+  const long F = (n + block - 1) / block;
+  for (long f = 0; f < F; ++f) {
+    int r0, r1, c0, c1;
+    cv_window((int)n, (int)block, (int)gap, (int)f, r0, r1, c0, c1);
+    if (n - (r1 - r0) < 1) return "a fold leaves no training row (its window covers the whole data set)";
+  }
+  return nullptr;
+}
+
+// K slices of the strip product: 0 (auto) = enough to give every CU two workgroups from ONE member's folds (at most 32), at most one per
+// stage of the longest strip.  The count does not depend on the lockstep group, so a member of a group adds its slices in the order its
+// single fit does: the same bits from sigp_cv and sigp_cv_batch.
+static int cv_slices(const sigp_handle* h, long folds, long n) {
+  const long nch = (n + CV_KC - 1) / CV_KC;
+  long S = h->opt_cv_slices > 0 ? h->opt_cv_slices : std::min<long>(32, (2L * h->ncu + folds - 1) / folds);
+  return (int)std::max(1L, std::min(S, nch));
+}
+
+// the launcher the single and the lockstep entry points share (arguments as loo_launch); results in h->gPart laid out as loo_launch leaves them
+static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD,
+                     const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, int G, int block, int gap) {
+  const long ld = n_pad;
+  const int T = (int)(n_pad / NB);
+  const long F = (n + block - 1) / block;
+  const int wmax = (int)std::min<long>(n, (long)block + 2L * gap), wp = (int)round_up(wmax, 16);
+  const long FP = std::max<long>(1, std::min<long>(F, CV_PASS_BLOCKS / nb)), blocks = FP * nb;
+  const int S = cv_slices(h, std::min<long>(F, CV_PASS_BLOCKS), n);
+  h->cv_slices_used = S;
+  int rc;
+  if ((rc = ensure(h, &h->cvPart, &h->cap_cvPart, blocks * S * ((long)wp * wp + wp)))) return rc;
+  if ((rc = ensure(h, &h->cvBlk, &h->cap_cvBlk, 2 * blocks * CV_MAXW * CV_MAXW))) return rc;
+  if ((rc = ensure(h, &h->cvVec, &h->cap_cvVec, blocks * (CV_MAXW + 1)))) return rc;
+  double* part = h->cvPart;
+  double* apart = part + blocks * S * (long)wp * wp;
+  double* Pb = h->cvBlk;
+  double* Xb = Pb + blocks * CV_MAXW * CV_MAXW;
+  double* av = h->cvVec;
+  int* info = (int*)(av + blocks * CV_MAXW);
+  {
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
+    if ((rc = trtri_levels<double>(h, st, Lm, ld, dinvp, h->gU, h->gK, ld, T, T, nb, sL, sD, n_pad * n_pad))) return rc;
+  }
+  static AttrOnce d_attr;
+  HIPCHK(h, d_attr.set(h->device, (const void*)potrf_diag_kernel<double>, DIAG_LDS_BYTES));
+  const double* z = Lm + n_pad * ld;
+  for (long f0 = 0; f0 < F; f0 += FP) {
+    const unsigned nf = (unsigned)std::min<long>(FP, F - f0);
+    const double wf = (double)nb * nf;
+    {
+      ProfScope ps(h, st, SIGP_KC_MLII, wf * 2.0 * wmax * wmax * (n - 0.5 * (2 * f0 + nf) * block), wf * 8.0 * wmax * n);
+      hipLaunchKernelGGL(cv_strip_partial_kernel, dim3(nf, (unsigned)S, (unsigned)nb), dim3((unsigned)cv_strip_threads(wp)), 0, st, (const double*)h->gU, ld,
+                         n_pad * n_pad, z, sL, (int)n, block, gap, (int)f0, wp, part, apart);
+      HIPCHK(h, hipGetLastError());
+    }
+    {
+      ProfScope ps(h, st, SIGP_KC_MLII, wf * S * wmax * wmax, wf * 8.0 * (CV_MAXW * CV_MAXW + (double)S * wmax * wmax));
+      hipLaunchKernelGGL(cv_strip_finish_kernel, dim3(nf, (unsigned)nb), dim3(256), 0, st, (const double*)part, (const double*)apart, S, wp, (int)n, block, gap,
+                         (int)f0, Pb, av, info);
+      HIPCHK(h, hipGetLastError());
+    }
+    {
+      ProfScope ps(h, st, SIGP_KC_MLII, wf * 2.0 * NB * NB * NB / 3, wf * 3.0 * NB * NB * 8);
+      hipLaunchKernelGGL(potrf_diag_kernel<double>, dim3(nf * (unsigned)nb), dim3(DIAG_THREADS), DIAG_LDS_BYTES, st, Pb, (long)CV_MAXW, Xb, info, 0,
+                         h->opt_diag_prio ? 0 : 32, (long)CV_MAXW * CV_MAXW, (long)CV_MAXW * CV_MAXW);
+      HIPCHK(h, hipGetLastError());
+    }
+    {
+      ProfScope ps(h, st, SIGP_KC_MLII, wf * 2.0 * wmax * wmax, wf * 8.0 * wmax * wmax);
+      hipLaunchKernelGGL(cv_close_kernel, dim3(nf, (unsigned)nb), dim3(256), 0, st, (const double*)Xb, (const double*)av, (const int*)info, y, sY, kps, q, sQ, mode,
+                         (int)n, block, gap, (int)f0, h->gPart, n_pad, 4 * n_pad);
+      HIPCHK(h, hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)h->gPart, n_pad, 4 * n_pad, (int)n, h->gPart + (long)G * 4 * n_pad);
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
+
+int sigp_cv(sigp_handle* h, int64_t block, int64_t gap, int sigma_mode, double* mean, double* var, double* score) {
+  if (!h || !mean || !var || !score) return fail(h, SIGP_BAD_ARG, "cv: bad argument (mean [n], var [n], score [2] required)");
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "cv: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "cv: fp64 engine only (the fp32 engine keeps the inverses of its 2048-column diagonal blocks, not L~^-T)");
+  if (!h->fitted) return fail(h, SIGP_BAD_ARG, "cv: call sigp_fit / sigp_fit_predict first (a sharded fit leaves no single-GPU factor: sigp_cv does not apply)");
+  if (h->n < 2) return fail(h, SIGP_BAD_ARG, "cv: cross-validation needs n >= 2 training points");
+  if (const char* why = cv_check_folds(h->n, block, gap, SIGP_CV_MAX_WINDOW))
+    return fail(h, SIGP_BAD_ARG, "cv: %s (block = %lld, gap = %lld, n = %ld, SIGP_CV_MAX_WINDOW = %d)", why, (long long)block, (long long)gap, h->n, SIGP_CV_MAX_WINDOW);
+  HIPCHK(h, hipSetDevice(h->device));
+  Slot& s = h->slots[0];
+  hipStream_t st = s.s_upd;
+  const long n = h->n, n_pad = h->n_pad;
+  int rc;
+  if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad + 4))) return rc;
+  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~ (host copy of the fit's epilogue, as sigp_loo)
+  HIPCHK(h, hipMemcpyAsync(tail + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
+  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1, (int)block, (int)gap))) return rc;
+  HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(score, tail, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  return sync_slot(h, s);
+}
+
+int sigp_cv_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde, int64_t block, int64_t gap,
+                  int sigma_mode, double* mean, double* var, int64_t nstride, double* score) {
+  if (!h || h->b_count == 0 || first < 0 || count < 1 || !ell || !sn_tilde || !score) return fail(h, SIGP_BAD_ARG, "cv_batch: bad argument (sigp_batch_upload first)");
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "cv_batch: fp64 engine only");
+  if (kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "cv_batch: RBF / MATERN52 only (the reference kernel's batch is sigp_small_run_cv)");
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "cv_batch: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if ((mean == nullptr) != (var == nullptr)) return fail(h, SIGP_BAD_ARG, "cv_batch: mean and var come together (both NULL: scores only)");
+  if (mean && nstride < h->b_n) return fail(h, SIGP_BAD_ARG, "cv_batch: mean / var [count][nstride >= %ld] required", h->b_n);
+  if (h->b_n < 2) return fail(h, SIGP_BAD_ARG, "cv_batch: cross-validation needs n >= 2 training points");
+  if (const char* why = cv_check_folds(h->b_n, block, gap, SIGP_CV_MAX_WINDOW))
+    return fail(h, SIGP_BAD_ARG, "cv_batch: %s (block = %lld, gap = %lld, n = %ld, SIGP_CV_MAX_WINDOW = %d)", why, (long long)block, (long long)gap, h->b_n, SIGP_CV_MAX_WINDOW);
+  for (int64_t i = 0; i < count; ++i)
+    if (!(ell[i] > 0) || !std::isfinite(ell[i]) || !(sn_tilde[i] >= 0) || !std::isfinite(sn_tilde[i])) return fail(h, SIGP_BAD_ARG, "cv_batch: finite ell > 0 and sn_tilde >= 0 required");
+  HIPCHK(h, hipSetDevice(h->device));
+  const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad;
+  const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
+  const double inf = std::numeric_limits<double>::infinity(), qnan = std::nan("");
+  Slot& s = h->slots[0];
+  hipStream_t st = s.s_upd;
+  int rc;
+  if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
+  if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
+  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4)))) return rc;
+  std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
+  for (long g0 = 0; g0 < count; g0 += G) {
+    const int nb = (int)std::min<long>(G, count - g0);
+    for (int b = 0; b < nb; ++b) s.kps_host[b] = make_kparams(kernel_id, ell[g0 + b], sn_tilde[g0 + b], (int)((first + g0 + b) % h->b_count));
+    if ((rc = upload_kparams(h, s, nb))) return rc;
+    if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
+    if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
+    if ((rc = epilogue_slot(h, s, nb, n, n_pad, 0))) return rc;
+    if ((rc = cv_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G, (int)block, (int)gap))) return rc;
+    if (mean) HIPCHK(h, hipMemcpy2DAsync(mv.data(), (size_t)2 * n_pad * sizeof(double), h->gPart, (size_t)4 * n_pad * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(sc.data(), h->gPart + (long)G * 4 * n_pad, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = sync_slot(h, s))) return rc;
+    for (int b = 0; b < nb; ++b) {
+      const long i = g0 + b;
+      // a member whose K~ is not SPD, or one of whose P_SS failed its pivot test (+inf terms in its sums): +inf scores, NaN rows
+      const bool ok = s.info_host[b] == 0 && std::isfinite(sc[(size_t)2 * b]) && std::isfinite(sc[(size_t)2 * b + 1]);
+      score[2 * i] = ok ? sc[(size_t)2 * b] : inf;
+      score[2 * i + 1] = ok ? sc[(size_t)2 * b + 1] : inf;
+      if (!mean) continue;
+      for (long j = 0; j < n; ++j) {
+        mean[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + j] : qnan;
+        var[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + n_pad + j] : qnan;
+      }
+    }
+  }
+  h->built = h->factored = h->fitted = false;
+  return SIGP_OK;
+}

@@ -59,18 +59,28 @@ int sigp_small_set_dweights(sigp_handle* h, const double* dlam_pool, int64_t cou
 
 static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out,
                           double* mean, double* var, int64_t mstride, bool grad, int loo_mode = -1, double* loo_mean = nullptr,
-                          double* loo_var = nullptr, int64_t nstride = 0) {
+                          double* loo_var = nullptr, int64_t nstride = 0, int64_t cv_block = 0, int64_t cv_gap = 0) {
   if (!h || h->sm_sets.empty()) return fail(h, SIGP_BAD_ARG, "small_run: call sigp_small_upload first");
+  const bool cv = cv_block != 0 || cv_gap != 0;       // leave-block-out: rows and scores travel like the leave-one-out ones
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
   const bool loo = loo_mode >= 0;
-  if (loo && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_loo: loo_mean / loo_var [nprob][nstride >= %d] required", h->sm_nmax);
+  if (loo && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_%s: %s_mean / %s_var [nprob][nstride >= %d] required", cv ? "cv" : "loo", cv ? "cv" : "loo", cv ? "cv" : "loo", h->sm_nmax);
+  constexpr long SM_LDS_MAX = 160 * 1024 - 64;
+  if (cv && h->sm_lds + SM_CV_EXTRA_BYTES > SM_LDS_MAX) return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes", h->sm_nmax, h->sm_mmax, SM_CV_EXTRA_BYTES);
+  std::vector<char> cv_checked(cv ? h->sm_sets.size() : 0, 0);
   if (h->sm_mmax > 0 && (!mean || !var || mstride < h->sm_mmax)) return fail(h, SIGP_BAD_ARG, "small_run: mean / var [nprob][mstride >= %d] required", h->sm_mmax);
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<SmallProb> probs((size_t)nprob);
   for (int64_t i = 0; i < nprob; ++i) {
     if (set_index[i] < 0 || set_index[i] >= (int64_t)h->sm_sets.size()) return fail(h, SIGP_BAD_ARG, "small_run: fit %ld names data set %ld of %zu", (long)i, (long)set_index[i], h->sm_sets.size());
     if (!(sn_tilde[i] >= 0) || !std::isfinite(ell[i])) return fail(h, SIGP_BAD_ARG, "small_run: finite ell and sn_tilde >= 0 required");
-    if (loo && h->sm_sets[(size_t)set_index[i]].n < 2) return fail(h, SIGP_BAD_ARG, "small_run_loo: fit %ld names a data set of one point; leave-one-out needs n >= 2", (long)i);
+    if (loo && h->sm_sets[(size_t)set_index[i]].n < 2) return fail(h, SIGP_BAD_ARG, "small_run_%s: fit %ld names a data set of one point; cross-validation needs n >= 2", cv ? "cv" : "loo", (long)i);
+    if (cv && !cv_checked[(size_t)set_index[i]]) {
+      if (const char* why = cv_check_folds(h->sm_sets[(size_t)set_index[i]].n, cv_block, cv_gap, SIGP_CV_SMALL_MAX_WINDOW))
+        return fail(h, SIGP_BAD_ARG, "small_run_cv: fit %ld: %s (block = %lld, gap = %lld, n = %d, SIGP_CV_SMALL_MAX_WINDOW = %d)", (long)i, why, (long long)cv_block, (long long)cv_gap,
+                    h->sm_sets[(size_t)set_index[i]].n, SIGP_CV_SMALL_MAX_WINDOW);
+      cv_checked[(size_t)set_index[i]] = 1;
+    }
     probs[(size_t)i] = SmallProb{(int)set_index[i], 0, ell[i], sn_tilde[i]};
   }
   const long ms = std::max<int64_t>(mstride, 1);
@@ -97,7 +107,10 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   double* d_var = d_mean + nprob * ms;
   double* d_lmean = d_var + nprob * ms;        // [nprob][ns] each; NaN beyond a set's n (the memset above)
   double* d_lvar = d_lmean + nprob * ns;
-  if (loo) {
+  if (cv) {
+    static AttrOnce attr256c;
+    HIPCHK(h, attr256c.set(h->device, (const void*)smallgp_kernel<256, false, false, true>, 160 * 1024 - 64));
+  } else if (loo) {
     static AttrOnce attr256l;
     HIPCHK(h, attr256l.set(h->device, (const void*)smallgp_kernel<256, false, true>, 160 * 1024 - 64));
   }
@@ -108,12 +121,16 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
       fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n * (1 + s.m);
       if (grad) fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.N;      // X = L~^-1, X A, A^T a~
       if (loo) fl += (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n;                                 // X = L~^-1, its column norms and X^T z
+      if (cv) fl += (double)s.n * s.n * (cv_block + 2.0 * cv_gap);                                  // the folds' P_SS from X's columns
     }
     ProfScope ps(h, st, SIGP_KC_SMALL, fl, 0.0);
     // orders up to 64 (the reference's n <= 45): one wavefront per fit; larger: four
     // measured on the reference-size grid (48 000 fits, n = 6 .. 45): four wavefronts per fit 1.02 ms, one wavefront per fit 1.71 ms
     const double* d_dlam = h->sm_has_dlam ? h->sm_dlam : nullptr;
-    if (loo)
+    if (cv)
+      hipLaunchKernelGGL((smallgp_kernel<256, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)(h->sm_lds + SM_CV_EXTRA_BYTES), st, h->sm_sets_dev, h->sm_probs,
+                         h->sm_A, h->sm_y, h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)cv_block, (int)cv_gap);
+    else if (loo)
       hipLaunchKernelGGL((smallgp_kernel<256, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y,
                          h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode);
     else if (grad)
@@ -168,6 +185,14 @@ int sigp_small_run_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, 
                        double* out6, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride) {
   if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_loo: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
   return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, loo_mean, loo_var, nstride);
+}
+
+// sigp_small_run with the leave-block-out cross-validation of every fit in the same single launch (smallgp_kernel<256, false, false, true>)
+int sigp_small_run_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block, int64_t gap, int sigma_mode,
+                      double* out6, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_cv: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (block < 1 || gap < 0) return fail(h, SIGP_BAD_ARG, "small_run_cv: block >= 1 and gap >= 0 required");
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, cv_mean, cv_var, nstride, block, gap);
 }
 
 // ---- ComplexNetworks tau(): cell-to-cell correlation matrix + thresholded mean (ComplexNetworks.py:31-47) ------------

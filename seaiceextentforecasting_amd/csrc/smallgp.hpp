@@ -19,10 +19,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "blockcv.hpp"
+
 namespace sigp {
 
 constexpr int SM_NMAX = 128;   // largest order one workgroup handles
 constexpr int SM_MMAX = 8;     // test points per fit
+constexpr int SM_CVW = 32;     // widest window (block + 2 gap) of the leave-block-out flavour
+constexpr int SM_CVP = SM_CVW + 1;   // odd pitch of its w x w scratch matrices
+// LDS of the leave-block-out flavour beyond smallgp_lds_bytes: P_SS / its factor, the factor's inverse, t  (this instantiation only)
+constexpr long SM_CV_EXTRA_BYTES = (2L * SM_CVW * SM_CVP + SM_CVW) * (long)sizeof(double);
 
 struct SmallSet {
   long a_off;      // doubles into the A pool: A [(n + m)][N] row-major
@@ -78,15 +84,21 @@ __device__ inline double smallgp_allsum(double v, double* sh) {
 // s_i = (zz - a~_i^2 / g_i) / (n - 1) (loo_fixed = 0: sigma_f re-profiled without point i, what a refit on the other n - 1 points
 // returns) or sigma_f (loo_fixed = 1);  out[4] = nlpd = sum_i log(2 pi var_i)/2 + (y_i - mean_i)^2 / (2 var_i),  out[5] = sse;
 // loo_mean / loo_var [nprob][nstride].  A non-SPD K~ gives +inf in both scores (the rows stay as the caller initialised them).
-template <int NT, bool GRAD = false, bool LOO = false>
+// CV = true (OW = 6; never together with GRAD or LOO): leave-block-out cross-validation (blockcv.hpp: folds of cv_block consecutive rows, cv_gap
+// rows removed on each side, windows of at most SM_CVW rows) from the same in-LDS X and a~, fold after fold in SM_CV_EXTRA_BYTES of LDS
+// behind the plain layout:  P_SS(i, j) = sum_{k >= max} X(k, r0 + i) X(k, r0 + j),  P_SS = M M^T column by column,  W = M^-1 (one thread per
+// column),  t = W a~_S,  r = W^T t,  h_i = sum_k W(k, i)^2;  mean = y - r,  var = s h with s = (zz - t.t) / (n - w) (loo_fixed = 0) or sigma_f;
+// outputs as LOO's, written for the scored rows of each fold.  A failed pivot of a P_SS: +inf in both scores and NaN rows.
+template <int NT, bool GRAD = false, bool LOO = false, bool CV = false>
 __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict__ sets, const SmallProb* __restrict__ probs,
                                                       const double* __restrict__ Apool, const double* __restrict__ ypool,
                                                       const double* __restrict__ lampool, int ch, double* __restrict__ out,
                                                       double* __restrict__ mean, double* __restrict__ var, int mstride,
                                                       const double* __restrict__ dlampool, double* __restrict__ loo_mean = nullptr,
-                                                      double* __restrict__ loo_var = nullptr, int nstride = 0, int loo_fixed = 0) {
-  static_assert(!(GRAD && LOO), "one launch forms the MLII gradients or the leave-one-out predictions");
-  constexpr int OW = GRAD ? 8 : LOO ? 6 : 4;
+                                                      double* __restrict__ loo_var = nullptr, int nstride = 0, int loo_fixed = 0, int cv_block = 0,
+                                                      int cv_gap = 0) {
+  static_assert(!(GRAD && LOO) && !(CV && (GRAD || LOO)), "one launch forms the MLII gradients, the leave-one-out or the leave-block-out predictions");
+  constexpr int OW = GRAD ? 8 : (LOO || CV) ? 6 : 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const SmallProb pb = probs[blockIdx.x];
   const SmallSet st = sets[pb.set];
@@ -186,7 +198,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     } else {
       o[0] = inf; o[1] = inf; o[2] = (double)info; o[3] = inf;
       if (GRAD) { o[4] = inf; o[5] = inf; o[6] = inf; o[7] = inf; }     // north/June1st.py:254-256
-      if (LOO) { o[4] = inf; o[5] = inf; }
+      if (LOO || CV) { o[4] = inf; o[5] = inf; }
     }
   }
   for (int j = 0; j < m; ++j) {
@@ -201,7 +213,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     }
   }
 
-  if constexpr (GRAD || LOO) {
+  if constexpr (GRAD || LOO || CV) {
     if (info != 0) return;           // uniform
     double* at = red + 16;           // [n] a~ = L~^-T z
     // ---- X = L~^-1 in place, row by row: X(i,j) = -X(i,i) sum_{k=j}^{i-1} L(i,k) X(k,j); rows above i are complete, row i of L~ is
@@ -229,6 +241,86 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
       }
       if (tid == 0) Kp[i * ldk + i] = xii;
       __syncthreads();
+    }
+    if constexpr (CV) {
+      double* Pw = at + n + 24;              // [w][SM_CVP] P_SS, then its factor M (lower); behind the plain layout (smallgp_lds_bytes)
+      double* Ww = Pw + SM_CVW * SM_CVP;     // [w][SM_CVP] W = M^-1 (lower)
+      double* tv = Ww + SM_CVW * SM_CVP;     // [w] t = W a~_S
+      __shared__ int s_cvbad;
+      if (tid == 0) s_cvbad = 0;
+      for (int i = tid; i < n; i += NT) {
+        double a = 0.0;
+        for (int k = i; k < n; ++k) a = fma(Kp[k * ldk + i], z[k], a);
+        at[i] = a;
+      }
+      __syncthreads();
+      double tn = 0.0, ts = 0.0;
+      const int F = (n + cv_block - 1) / cv_block;
+      for (int f = 0; f < F; ++f) {
+        int r0, r1, c0, c1;
+        cv_window(n, cv_block, cv_gap, f, r0, r1, c0, c1);
+        const int w = r1 - r0;
+        for (int e = tid; e < w * w; e += NT) {
+          const int i = e / w, j = e - i * w;
+          if (j <= i) {
+            double p = 0.0;
+            for (int k = r0 + i; k < n; ++k) p = fma(Kp[k * ldk + r0 + i], Kp[k * ldk + r0 + j], p);
+            Pw[i * SM_CVP + j] = p;
+          }
+        }
+        __syncthreads();
+        for (int j = 0; j < w; ++j) {
+          double d = Pw[j * SM_CVP + j];
+          if (!(d > 0.0)) {
+            if (tid == 0) s_cvbad = 1;
+            d = 1.0;
+          }
+          const double sq = sqrt(d), inv = 1.0 / sq;
+          __syncthreads();
+          for (int i = j + tid; i < w; i += NT) Pw[i * SM_CVP + j] = (i == j) ? sq : Pw[i * SM_CVP + j] * inv;
+          __syncthreads();
+          for (int i = j + 1 + ty; i < w; i += TY) {
+            const double lij = Pw[i * SM_CVP + j];
+            for (int c = j + 1 + tx; c <= i; c += 16) Pw[i * SM_CVP + c] = fma(-lij, Pw[c * SM_CVP + j], Pw[i * SM_CVP + c]);
+          }
+          __syncthreads();
+        }
+        if (tid < w) {                     // column tid of W: M W = I by forward substitution
+          for (int k = tid; k < w; ++k) {
+            double acc = k == tid ? 1.0 : 0.0;
+            for (int j = tid; j < k; ++j) acc = fma(-Pw[k * SM_CVP + j], Ww[j * SM_CVP + tid], acc);
+            Ww[k * SM_CVP + tid] = acc / Pw[k * SM_CVP + k];
+          }
+        }
+        __syncthreads();
+        if (tid < w) {
+          double t = 0.0;
+          for (int i = 0; i <= tid; ++i) t = fma(Ww[tid * SM_CVP + i], at[r0 + i], t);
+          tv[tid] = t;
+        }
+        __syncthreads();
+        if (tid < w) {
+          double tt = 0.0, r = 0.0, hh = 0.0;
+          for (int k = 0; k < w; ++k) tt = fma(tv[k], tv[k], tt);
+          for (int k = tid; k < w; ++k) { const double x = Ww[k * SM_CVP + tid]; r = fma(x, tv[k], r); hh = fma(x, x, hh); }
+          const int gi = r0 + tid;
+          if (gi >= c0 && gi < c1) {
+            const double v = (loo_fixed ? sf : (zz - tt) / (double)(n - w)) * hh;
+            loo_mean[(long)blockIdx.x * nstride + gi] = ypool[st.y_off + gi] - r;
+            loo_var[(long)blockIdx.x * nstride + gi] = v;
+            tn += 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
+            ts = fma(r, r, ts);
+          }
+        }
+        __syncthreads();
+      }
+      const double nlpd = smallgp_allsum<NT>(tn, red);
+      const double sse = smallgp_allsum<NT>(ts, red);
+      const bool bad = s_cvbad != 0;
+      if (tid == 0) { out[(long)blockIdx.x * OW + 4] = bad ? inf : nlpd; out[(long)blockIdx.x * OW + 5] = bad ? inf : sse; }
+      if (bad)
+        for (int i = tid; i < n; i += NT) { loo_mean[(long)blockIdx.x * nstride + i] = qnan; loo_var[(long)blockIdx.x * nstride + i] = qnan; }
+      return;
     }
     if constexpr (LOO) {
       // column i of X: a~_i and g_i in one walk (odd pitch: the lanes' columns fall in different banks)

@@ -327,6 +327,105 @@ class GPR:
             nlpd, sse = r["nlpd"], r["sse"]
         return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
 
+    # ---- leave-block-out cross-validation --------------------------------------------------------
+    @staticmethod
+    def cv_folds(n, block, gap=0):
+        """The folds of ``cv``: an [F, 4] int array of (r0, r1, c0, c1) -- fold f scores the rows [c0, c1) = [f block, min(n, (f + 1) block))
+        and removes the window [r0, r1) = [max(0, c0 - gap), min(n, c1 + gap)) from training."""
+        c0 = np.arange(0, int(n), int(block), dtype=np.int64)
+        c1 = np.minimum(c0 + int(block), int(n))
+        return np.stack([np.maximum(c0 - int(gap), 0), np.minimum(c1 + int(gap), int(n)), c0, c1], axis=1)
+
+    @staticmethod
+    def _cv_args(block, gap, sigma_f, max_window=L.CV_MAX_WINDOW, n=None):
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if int(block) != block or int(gap) != gap or block < 1 or gap < 0:
+            raise ValueError("block >= 1 and gap >= 0 (integers) required")
+        if block + 2 * gap > max_window:
+            raise ValueError("the window block + 2 gap = %d exceeds %d rows" % (block + 2 * gap, max_window))
+        if n is not None:
+            f = GPR.cv_folds(n, block, gap)
+            if n < 2 or np.any(n - (f[:, 1] - f[:, 0]) < 1):
+                raise ValueError("every fold must leave a training row (n = %d, block = %d, gap = %d)" % (n, block, gap))
+        return int(block), int(gap)
+
+    def cv(self, block, gap=0, sigma_f="refit"):
+        """Leave-block-out (K-fold, h-block, hv-block) cross-validation of the current fit with (l, sn~) (and, for the reference kernel, M and
+        the feature columns) held -- for ordered rows such as consecutive years, where leaving ONE row out keeps its serially correlated
+        neighbours in the training set and makes ``loo`` optimistic.  Fold f scores the rows [f block, (f + 1) block) and removes them, plus
+        ``gap`` rows on each side (removed but not scored), from training: what ``fit`` on the remaining rows followed by ``predict`` of the scored
+        rows returns, for every fold, from the factor already on the device (``sigp_cv``: L~^-T as ``loo``, then per fold the |S| x |S| block
+        of K~^-1, its Cholesky factor and two short solves).  block + 2 gap <= 128, and every fold must leave a training row.  ``cv(1)`` is
+        ``loo()``.  An arbitrary (shuffled) K-fold is the same call after the rows are permuted before ``fit``.
+
+        sigma_f='refit'  the signal variance is re-profiled without the removed window (divisor n - |S_f| per fold): identical to real refits;
+        sigma_f='fixed'  the full fit's sigma_f is kept.  The means do not depend on the mode.
+
+        Returns dict(mean [n], var [n] (marginal, includes the noise, like fvar), nlpd, sse, mse, skill, folds [F, 4] = (r0, r1, c0, c1) as
+        ``cv_folds``).  The fit stays as it is."""
+        n = getattr(self, "n", None) if self._fitted else None
+        block, gap = self._cv_args(block, gap, sigma_f, n=n)
+        if self.dtype != "f64":
+            raise ValueError("cv: fp64 engine only")
+        if not self._fitted:
+            raise RuntimeError("cv: call fit() first")
+        mean, var, score = np.zeros(self.n), np.zeros(self.n), np.zeros(2)
+        self._check(self._lib.sigp_cv(self._h, block, gap, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), L.ptr(score)), "cv")
+        nlpd, sse = float(score[0]), float(score[1])
+        return dict(mean=mean, var=var, nlpd=nlpd, sse=sse, mse=sse / self.n, skill=1.0 - sse / float(np.sum((self._y - self._y.mean()) ** 2)),
+                    folds=self.cv_folds(self.n, block, gap))
+
+    def cv_batch(self, ell, sn_tilde, block, gap=0, first=0, sigma_f="refit", group=8, predictions=True):
+        """``cv`` for many (data set, l, sn~) on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern), in lockstep groups
+        of ``group`` fits (``sigp_cv_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F]) and, with
+        ``predictions``, mean [F, n], var [F, n]; a member whose K~ (or one of whose blocks of K~^-1) is not SPD gets +inf / NaN."""
+        n = getattr(self, "_batch_n", None)
+        block, gap = self._cv_args(block, gap, sigma_f, n=n)
+        if self.kernel == "netdiffusion":
+            raise ValueError("cv_batch covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(cv=...)")
+        ell = L.f64(np.atleast_1d(ell), 1)
+        sn = L.f64(np.atleast_1d(sn_tilde), 1)
+        F = len(ell)
+        if len(sn) != F:
+            raise ValueError("ell and sn_tilde must have the same length")
+        if n is None:
+            raise RuntimeError("cv_batch: stage the data sets with upload_batch() first")
+        self.set_option("group", group)
+        score = np.zeros((F, 2))
+        mean = np.zeros((F, n)) if predictions else None
+        var = np.zeros((F, n)) if predictions else None
+        self._check(self._lib.sigp_cv_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), block, gap, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                            L.ptr(score)), "cv_batch")
+        self._fitted = False
+        res = dict(nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
+        if predictions:
+            res["mean"], res["var"] = mean, var
+        return res
+
+    def cv_grid(self, X, y, ells, sns, block, gap=0, sigma_f="refit", group=8, M=None):
+        """The leave-block-out scores on the (l, sn~) grid for one data set, shaped like ``loo_grid``: dict(nlpd, sse), each
+        [len(ells), len(sns)], +inf where K~ is not SPD.  Reference kernel (n <= 128, block + 2 gap <= 32): one launch, one workgroup per
+        grid point (``SmallBatch.run(cv=...)``); the other kernels go through ``cv_batch``."""
+        small = self.kernel == "netdiffusion"
+        block, gap = self._cv_args(block, gap, sigma_f, max_window=L.CV_SMALL_MAX_WINDOW if small else L.CV_MAX_WINDOW, n=np.shape(X)[0])
+        ells = np.asarray(ells, dtype=np.float64).reshape(-1)
+        sns = np.asarray(sns, dtype=np.float64).reshape(-1)
+        E, S = np.meshgrid(ells, sns, indexing="ij")
+        if small:
+            from .smallbatch import SmallBatch
+            sb = SmallBatch(self)
+            ds = sb.add_dataset(X, y, None, M)
+            for e, s_ in zip(E.reshape(-1), S.reshape(-1)):
+                sb.add_fit(ds, e, s_, expm=self._expm)
+            r = sb.run(cv=dict(block=block, gap=gap, sigma_f=sigma_f))
+            nlpd, sse = r["cv_nlpd"], r["cv_sse"]
+        else:
+            self.upload_batch(L.f64(X, 2), y, None, group=group)
+            r = self.cv_batch(E.reshape(-1), S.reshape(-1), block, gap=gap, sigma_f=sigma_f, group=group, predictions=False)
+            nlpd, sse = r["nlpd"], r["sse"]
+        return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
+
     # ---- MLII (north/June1st.py:235-257) -------------------------------------------------------
     def nlml(self, theta, grad="ref"):
         """``MLII(hyperparameters)``: theta = (log l, log sn~) -> (nlML, grad[2]).

@@ -82,10 +82,10 @@ def retro_forecast(script, SIC, SIEs_dt, SIEs_trend, fmin, fmax, SST=None, gp=No
             gp.close()
 
 
-_CRITERIA = {"nlml": (None, "nlml"), "loo_nlpd": ("refit", "loo_nlpd"), "loo_sse": ("refit", "loo_sse")}
+_CRITERIA = {"nlml": (None, "nlml"), "loo_nlpd": ("refit", "loo_nlpd"), "loo_sse": ("refit", "loo_sse"), "cv_nlpd": ("refit", "cv_nlpd"), "cv_sse": ("refit", "cv_sse")}
 
 
-def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sns=SGRID, gp=None, criterion="nlml"):
+def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sns=SGRID, gp=None, criterion="nlml", block=5, gap=0):
     """The hyper-parameter search the reference's tables imply (north/June1st.py:210-211: indices into
     ``logspace(-7,2,20) x logspace(-3,9,20)``): nlML (north/June1st.py:246) of every (region, year) of the retro loop at
     every grid point -- 3 x years x 400 fits in one device launch, one eigendecomposition of M per (region, year).
@@ -95,10 +95,21 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
     leave-one-out negative log predictive density / sum of squared errors of every fit instead (to be minimised like nlML;
     ``SmallBatch.run(loo="refit")``, still one launch).  What this leave-one-out holds fixed: the selected features, their
     standardisation and M are those of the FULL training set of the (region, year); only the GP -- with (l, sn~) held and
-    sigma_f re-profiled -- is cross-validated.  Features are not re-selected per left-out year."""
+    sigma_f re-profiled -- is cross-validated.  Features are not re-selected per left-out year.
+
+    ``criterion`` = "cv_nlpd" or "cv_sse": the leave-BLOCK-out scores instead (``SmallBatch.run(cv=dict(block=block, gap=gap))``, still one
+    launch): folds of ``block`` consecutive years, ``gap`` more years removed from training on each side of a fold but not scored
+    (block + 2 gap <= 32; every (region, year) must keep a training year in every fold) -- the remedy for the optimism of leave-one-out
+    on a serially correlated series.  The same things are held fixed as above: features, standardisation and M come from the full training
+    set of the (region, year), (l, sn~) are held, sigma_f is re-profiled per fold; features are not re-selected per left-out block.
+    ``block`` and ``gap`` are ignored by the other criteria."""
     if criterion not in _CRITERIA:
         raise ValueError("criterion must be one of %s" % sorted(_CRITERIA))
     loo, key = _CRITERIA[criterion]
+    cv = None
+    if criterion.startswith("cv_"):
+        block, gap = GPR._cv_args(block, gap, loo, max_window=32)
+        cv, loo = dict(block=block, gap=gap, sigma_f=loo), None
     tab = SCRIPT_TABLE[script]
     own = gp is None
     gp = gp or GPR(kernel="netdiffusion")
@@ -114,7 +125,7 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
                 for e in ells:
                     for s_ in sns:
                         sb.add_fit(ds, e, s_, expm="eigh")
-        nl = (sb.run() if loo is None else sb.run(loo=loo))[key].reshape(len(tab["regions"]), ny, len(ells), len(sns))
+        nl = (sb.run(cv=cv) if cv is not None else sb.run() if loo is None else sb.run(loo=loo))[key].reshape(len(tab["regions"]), ny, len(ells), len(sns))
         return {region: nl[k] for k, region in enumerate(tab["regions"])}
     finally:
         if own:

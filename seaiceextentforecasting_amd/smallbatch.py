@@ -124,7 +124,7 @@ class SmallBatch:
         self._fits = []
         self._packed = None
 
-    def run(self, grad=False, loo=None):
+    def run(self, grad=False, loo=None, cv=None):
         """All queued fits in one launch -> dict(sigma_f, nlml, info, sigma_n, mean [F, mmax], var [F, mmax]); with ``grad=True``
         also grad_ref [F, 2] (the reference's MLII formulae, north/June1st.py:248-252) and grad_exact [F, 2] (the derivative of the
         profiled nlML w.r.t. (log l, log sn~)); +inf where K~ is not positive definite (:254-256).
@@ -133,11 +133,26 @@ class SmallBatch:
         (``sigp_small_run_loo``; "refit" re-profiles sigma_f without the left-out point -- what a fit on the other n - 1 points
         returns --, "fixed" keeps the full fit's sigma_f): loo_mean, loo_var [F, nmax] (NaN beyond a data set's n), loo_nlpd,
         loo_sse [F] (+inf / NaN rows where K~ is not positive definite).  One launch forms the gradients or the leave-one-out
-        predictions: ``grad=True`` together with ``loo`` raises ValueError."""
+        predictions: ``grad=True`` together with ``loo`` raises ValueError.
+
+        ``cv=dict(block=, gap=0, sigma_f="refit")``: the same single launch cross-validates every fit leave-block-out instead
+        (``sigp_small_run_cv``; folds and modes as ``GPR.cv``, block + 2 gap <= 32, every fold of every data set must leave a training row):
+        cv_mean, cv_var [F, nmax] (NaN beyond a data set's n), cv_nlpd, cv_sse [F] (+inf / NaN rows where K~ or a fold's block of K~^-1 is
+        not positive definite).  Mutually exclusive with ``loo`` and ``grad``."""
         if loo is not None and loo not in L.LOO_MODES:
             raise ValueError("loo must be None, 'refit' or 'fixed'")
         if loo is not None and grad:
             raise ValueError("one launch forms the MLII gradients or the leave-one-out predictions: run(grad=True) and run(loo=...) separately")
+        if cv is not None:
+            if loo is not None or grad:
+                raise ValueError("one launch forms the gradients, the leave-one-out or the leave-block-out predictions: run them separately")
+            if not isinstance(cv, dict) or "block" not in cv or set(cv) - {"block", "gap", "sigma_f"}:
+                raise ValueError("cv must be dict(block=, gap=0, sigma_f='refit')")
+            from .gpr import GPR
+            cv_mode = cv.get("sigma_f", "refit")
+            cv_block, cv_gap = GPR._cv_args(cv["block"], cv.get("gap", 0), cv_mode, max_window=L.CV_SMALL_MAX_WINDOW)
+            for X, _, _, _ in self._data:
+                GPR._cv_args(cv_block, cv_gap, cv_mode, max_window=L.CV_SMALL_MAX_WINDOW, n=X.shape[0])
         if self._uploaded != len(self._sets):
             self.upload()
         F = len(self._fits)
@@ -148,6 +163,15 @@ class SmallBatch:
         ms = max(self._mmax, 1)
         out = np.zeros((F, 8 if grad else 4)); mean = np.full((F, ms), np.nan); var = np.full((F, ms), np.nan)
         gp = self.gp
+        if cv is not None:
+            nmax = max(s[1].shape[0] for s in self._sets)
+            out = np.zeros((F, 6)); cmean = np.full((F, nmax), np.nan); cvar = np.full((F, nmax), np.nan)
+            gp._check(gp._lib.sigp_small_run_cv(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), cv_block, cv_gap, L.LOO_MODES[cv_mode], L.ptr(out), L.ptr(mean), L.ptr(var), ms,
+                                                L.ptr(cmean), L.ptr(cvar), nmax), "small_run_cv")
+            gp._fitted = False
+            return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
+                        mean=mean[:, :self._mmax], var=var[:, :self._mmax], cv_mean=cmean, cv_var=cvar,
+                        cv_nlpd=out[:, 4].copy(), cv_sse=out[:, 5].copy())
         if loo is not None:
             nmax = max(s[1].shape[0] for s in self._sets)
             out = np.zeros((F, 6)); lmean = np.full((F, nmax), np.nan); lvar = np.full((F, nmax), np.nan)
