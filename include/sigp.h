@@ -216,6 +216,8 @@ int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const d
  * K~^-1 = U U^T, A~ = U z, reductions with dK~/dlog ell recomputed on the fly.  One call per optimiser iteration serves every
  * retrospective year (the call the reference left commented out, north/June1st.py:259-262, batched over the retro loop of
  * north/retrospective_forecasts/September1st_retro.py:176-248).  grad_mode 0 (value only; grad may be NULL) or 2.
+ * Any feature count d >= 1 that sigp_batch_upload accepts is supported (the gradient's reduction holds the first 64 features of its rows in
+ * LDS and reads the rest from global memory: no limit on d).
  * nlml [count], grad [count][2]; a non-SPD member gets +inf in both (the reference's except branch :254-256). */
 int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int grad_mode, double* nlml, double* grad);
 

@@ -503,17 +503,19 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restri
 // symmetric with a zero diagonal for both kernels: a^T D a = 2 sum_{j<i} a_i D_ij a_j).  kps[member] carries the *_DLOGL
 // covariance id and the data set.  part [member][rows][4] as above.
 constexpr int GR_ROWS = 4;
+constexpr int GR_DL = 64;     // features of the block's rows staged in LDS; any d is served (p ascending either way: the same bits)
 __global__ __launch_bounds__(256) void grad_reduce_cov_kernel(const double* __restrict__ Kinv, long sK, long ld, const double* __restrict__ a, long sa,
                                                               const double* __restrict__ X, long strideX, int dp, int d, int n,
                                                               const KParams* __restrict__ kps, double* __restrict__ part, long spart) {
-  __shared__ double Xi[GR_ROWS][65];
+  __shared__ double Xi[GR_ROWS][GR_DL + 1];
   __shared__ double sh[4];
   const KParams kp = kps[blockIdx.y];
   X += kp.ds * strideX;
   Kinv += (long)blockIdx.y * sK; a += (long)blockIdx.y * sa; part += (long)blockIdx.y * spart;
   const int i0 = blockIdx.x * GR_ROWS;
-  for (int idx = threadIdx.x; idx < GR_ROWS * d; idx += 256) {
-    const int r = idx / d, p = idx % d;
+  const int dl = min(d, GR_DL);                            // features held in LDS; the rest come from global memory below
+  for (int idx = threadIdx.x; idx < GR_ROWS * dl; idx += 256) {
+    const int r = idx / dl, p = idx % dl;
     Xi[r][p] = (i0 + r < n) ? X[(long)(i0 + r) * dp + p] : 0.0;
   }
   __syncthreads();
@@ -521,15 +523,23 @@ __global__ __launch_bounds__(256) void grad_reduce_cov_kernel(const double* __re
 #pragma unroll
   for (int r = 0; r < GR_ROWS; ++r) { t[r] = 0.0; q[r] = 0.0; }
   const int jmax = min(n, i0 + GR_ROWS);                   // j < i for the last row of the block
+  const double* xi[GR_ROWS];                               // rows past n are masked below: any valid row serves
+#pragma unroll
+  for (int r = 0; r < GR_ROWS; ++r) xi[r] = X + (long)min(i0 + r, n - 1) * dp;
   for (int j = threadIdx.x; j < jmax; j += 256) {
     double sq[GR_ROWS];
 #pragma unroll
     for (int r = 0; r < GR_ROWS; ++r) sq[r] = 0.0;
     const double* xj = X + (long)j * dp;
-    for (int p = 0; p < d; ++p) {
+    for (int p = 0; p < dl; ++p) {
       const double v = xj[p];
 #pragma unroll
       for (int r = 0; r < GR_ROWS; ++r) { const double u = Xi[r][p] - v; sq[r] = fma(u, u, sq[r]); }
+    }
+    for (int p = dl; p < d; ++p) {                         // d > GR_DL: the block's own rows are uniform addresses (one cached load per wave)
+      const double v = xj[p];
+#pragma unroll
+      for (int r = 0; r < GR_ROWS; ++r) { const double u = xi[r][p] - v; sq[r] = fma(u, u, sq[r]); }
     }
     const double aj = a[j];
 #pragma unroll
