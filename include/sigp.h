@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -221,6 +221,45 @@ int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const d
  * nlml [count], grad [count][2]; a non-SPD member gets +inf in both (the reference's except branch :254-256). */
 int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int grad_mode, double* nlml, double* grad);
 
+/* Per-feature (ARD) length scales for the RBF / Matern-5/2 kernels: "which features matter, and how much".  With u_i = x_i / l
+ * (element-wise, l in R^d) the ARD kernel is the isotropic one at ell = 1 on the scaled features: r^2_ij = sum_k (u_ik - u_jk)^2,
+ * k = exp(-r^2/2) (RBF), k = (1 + s + s^2/3) e^-s with s = sqrt(5) r (Matern-5/2).  So the scales live in the STAGING and nothing else changes:
+ * sigp_set_length_scales: ell [d] with finite ell[k] > 0 and d = the d of sigp_set_train (anything else: SIGP_BAD_ARG); ell = NULL returns the
+ * handle to isotropic (the raw features again, bit for bit).  From then on the training features, the ride-along rows (those staged
+ * already and those of later sigp_set_test calls) and the test points of sigp_predict / sigp_predict_cov are divided by ell[k] as they are
+ * staged -- the IEEE division x / ell[k], not a product with a reciprocal: a caller who stages X / l and Xs / l with ell = 1 gets the
+ * same bits from every call.  The ell argument of the build and fit calls stays a common multiplier (1 in ARD use).  The handle keeps
+ * the raw features and ride rows beside the scaled ones (8 (n_pad + 128) dp bytes, allocated by the first call), so new scales need no new
+ * sigp_set_train.  The call voids the fit, as sigp_set_test does; sigp_set_train clears the scales.  A handle that never sets scales
+ * runs exactly the launches it ran before.
+ * With scales set: SIGP_BAD_ARG for the reference kernel (SIGP_KERNEL_NETDIFFUSION in sigp_fit_predict, sigp_kernel_build_from_sigma)
+ * and for sigp_dist_fit / sigp_dist_predict; on an fp32 handle the call itself is SIGP_BAD_ARG.  sigp_loo, sigp_cv, sigp_predict_cov and
+ * sigp_get_alpha work on an ARD fit as on any other (they stage no features, or divide them as above).  The lockstep-batch entries
+ * (sigp_batch_upload and everything on its resident data: sigp_batch_run, sigp_nlml_grad_batch, sigp_loo_batch, sigp_loo_grad_batch,
+ * sigp_cv_batch) stage their own data and stay isotropic. */
+int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
+/* MLII with per-feature length scales: theta = (log l_1 .. log l_d, log sn~), ntheta = d + 1 (else SIGP_BAD_ARG) -> the profiled nlML
+ * (north/June1st.py:235-257) and, with grad_mode 2, its exact gradient grad [d + 1] (grad_mode 0: value only, grad may be NULL).  A grid
+ * over d + 1 parameters is out of reach; this is what an optimiser is given instead.  The call sets the scales to exp(theta[k]), fits with
+ * ell = 1 through sigp_fit_predict's own launches (nlml carries that fit's bits) and, with P = K~^-1, a = P y, sf = y^T a / n, returns
+ *     d nlML / d log l_k = sum_ij W_ij (u_ik - u_jk)^2,     W_ij = 1/2 (P_ij - a_i a_j / sf) h_ij,
+ *     d nlML / d log sn~ = sn~ (tr P / 2 - a^T a / (2 sf))                                  (as sigp_nlml_grad)
+ * with h_ij = k_ij (RBF), h_ij = (5/3)(1 + s_ij) e^-s_ij (Matern-5/2); the diagonal contributes 0, and at equal scales the d components
+ * add up to sigp_nlml_grad's d nlML / d log ell.  ALL d components come from ONE pass over K~^-1 (4 n^2 bytes; d derivative matrices
+ * through sigp_nlml_grad's reduction would move ~24 d n^2): one workgroup per 64 x 128 tile of its lower triangle forms the tile's
+ * squared distances with the covariance build's own GEMM-form code, W in the accumulator layout they arrive in, and -- on the column-
+ * centred scaled features -- the expanded square u_ik^2 rowsum(W)_i + [W (U_J o U_J)]_ik - 2 u_ik [W U_J]_ik with both products on
+ * v_mfma_f64_16x16x4_f64; per-tile partial sums, added in a fixed order (no atomics: the same bits on every run).  Any d that
+ * sigp_set_train accepts.  Cost on top of the fit: L~^-T and K~^-1 = U U^T as sigp_nlml_grad (2 n^3/3 flops), then the pass.
+ * A non-SPD K~ or an exp(theta[k]) that overflows (or underflows to 0) gives +inf in nlml and every grad entry and returns SIGP_NOT_SPD, as
+ * sigp_nlml_grad does.  fp64 engine, RBF / Matern-5/2 only; before sigp_set_train: SIGP_BAD_ARG.  Afterwards the handle is fitted at
+ * those hyper-parameters with the scales set: sigp_predict, sigp_predict_ride, sigp_loo, sigp_cv, sigp_predict_cov work on it.  Device
+ * work is accounted under SIGP_KC_MLII (the triangular inversion, U U^T, the pass: one entry each).
+ * Not covered: per-feature scales in the lockstep-batch entries, ARD gradients of the leave-one-out / leave-block-out scores
+ * (sigp_loo_grad differentiates with respect to the common multiplier), the one-workgroup kernel (sigp_small_*), the fp32 engine,
+ * sharded fits. */
+int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad);
+
 /* Leave-one-out cross-validation with the hyper-parameters held (Rasmussen & Williams 5.4.2): what the block north/June1st.py:264-277
  * returns for training point i when it is fitted on the other n - 1 points and asked to predict point i, for every i, from ONE
  * factorisation:  g_i = [K~^-1]_ii,  mean_i = y_i - A~_i / g_i,  var_i = s_i / g_i (includes the noise, like fvar
@@ -254,7 +293,8 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
  * and the fit must have come from sigp_fit_predict, which is told ell: d/dlog ell = ell d/dell), else NULL.  Errors as sigp_loo (fp32 handle,
  * sharded fit, n < 2, not fitted: SIGP_BAD_ARG).  The fit is only read: sigp_predict / sigp_get_alpha / sigp_loo afterwards return the bits
  * they returned before.
- * Not covered: gradients in sigp_small_run_loo (the one-workgroup kernel), sharded fits, the fp32 engine, per-feature length scales. */
+ * Not covered: gradients in sigp_small_run_loo (the one-workgroup kernel), sharded fits, the fp32 engine, gradients with respect to
+ * per-feature length scales (sigp_set_length_scales: the derivative is then that of the common multiplier ell). */
 int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t ldsigma, double* mean, double* var, double* score, double* grad);
 /* Lockstep groups on the resident batch data, arguments as sigp_loo_batch (RBF / Matern only); grad [count][4].  A non-SPD member gets +inf
  * scores and gradients and NaN rows; the other members are not affected. */

@@ -195,6 +195,53 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const double* __restrict__ 
   }
 }
 
+// The distance part of kbuild_mfma_kernel below (its comment explains the form), shared with ard_grad_partial_kernel (ardgrad.hpp): stages the
+// 64 rows of row tile bi and the 128 rows of column tile bj relative to the local origin, forms their inner products on the matrix pipe and
+// leaves the squared norms in nI / nJ (published by the closing barrier).  The squared distance of (row 16 wave + lr, column 16 t + 4 lq + c)
+// is then kb_gram_sq(acc[t][c], nI[16 wave + lr], nJ[16 t + 4 lq + c]).  Xi [64][DC + 2], Xj [128][DC + 2], 16-byte aligned.
+__device__ __forceinline__ double kb_gram_sq(double g, double ni, double nj) { return fmax(fma(-2.0, g, ni + nj), 0.0); }
+template <int DC>
+__device__ __forceinline__ void kb_gram_tile(const double* X, int dp, int d, int bi, int bj, double* Xi, double* Xj, double* nI, double* nJ,
+                                             d4 (&acc)[8]) {
+  constexpr int LP = DC + 2;                                       // conflict-free 8-byte fragment reads (row = lane & 15, k = lane >> 4)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int dq = (d + 3) & ~3;                                     // (X is zero-padded to dp >= dq features)
+  const double* x0 = X + (long)bi * KB_TM * dp;                    // the local origin (zero features stay zero: x0 is padded alike)
+  double sacc = 0.0;                                               // squared norm of staged row tid (tid < 192), from the LDS images
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
+  const int sig = 4 * (lr & 3) + (lr >> 2);                        // the column fed as MFMA row lr
+  for (int p0 = 0; p0 < dq; p0 += DC) {
+    const int pc = min(DC, dq - p0);                               // multiple of 4
+    const int h = pc >> 1, q = (tid % h) * 2, rstep = 256 / h;     // 16-byte pieces, lanes along the features of a row: a thread keeps its
+    const d2 o = *(const d2*)(x0 + p0 + q);                        // feature pair q (and its piece of x0) for every row it stages
+    __syncthreads();
+    if (tid < rstep * h) {
+      for (int row = tid / h; row < KB_TM + KB_TN; row += rstep) {
+        const d2 v = *(const d2*)(X + (long)(row < KB_TM ? bi * KB_TM + row : bj * KB_TN + row - KB_TM) * dp + p0 + q);
+        double* dst = row < KB_TM ? Xi + row * LP + q : Xj + (row - KB_TM) * LP + q;
+        *(d2*)dst = v - o;
+      }
+    }
+    __syncthreads();
+    const double* bI = Xi + (16 * wave + lr) * LP + lq;
+    const double* aJ = Xj + sig * LP + lq;
+    for (int kk = 0; kk < pc; kk += 4) {
+      const double b = bI[kk];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aJ[16 * t * LP + kk], b, acc[t], 0, 0, 0);
+    }
+    if (tid < KB_TM + KB_TN) {                                     // (the chunk stays in LDS until the next iteration's first barrier)
+      const double* xr = tid < KB_TM ? Xi + tid * LP : Xj + (tid - KB_TM) * LP;
+      for (int p = 0; p < pc; p += 2) { const d2 u = *(const d2*)(xr + p); sacc = fma(u.x, u.x, sacc); sacc = fma(u.y, u.y, sacc); }
+    }
+  }
+  if (tid < KB_TM) nI[tid] = sacc; else if (tid < KB_TM + KB_TN) nJ[tid - KB_TM] = sacc;
+  __syncthreads();
+}
+
 // The same tiles with the squared distances in GEMM form on the matrix pipe (SURVEY 8d counts the build that way):
 //     |x_i - x_j|^2 = |x_i|^2 + |x_j|^2 - 2 x_i . x_j,      the inner products by v_mfma_f64_16x16x4_f64
 // from LDS images of the tile's 64 + 128 rows of X (feature chunks of DC).  kbuild_kernel spends 2 d fp64 VALU instructions per element
@@ -239,47 +286,13 @@ __global__ __launch_bounds__(256) void kbuild_mfma_kernel(const double* __restri
   const KParams kp = kps[blockIdx.z];
   X += kp.ds * strideX;
   Mat += blockIdx.z * strideM;
-  constexpr int LP = DC + 2;                                       // conflict-free 8-byte fragment reads (row = lane & 15, k = lane >> 4)
+  constexpr int LP = DC + 2;
   __shared__ __attribute__((aligned(16))) double Xi[KB_TM * LP];
   __shared__ __attribute__((aligned(16))) double Xj[KB_TN * LP];
   __shared__ __attribute__((aligned(16))) double nI[KB_TM], nJ[KB_TN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  const int dq = (d + 3) & ~3;                                     // (X is zero-padded to dp >= dq features)
-  const double* x0 = X + (long)bi * KB_TM * dp;                    // the local origin (zero features stay zero: x0 is padded alike)
-  double sacc = 0.0;                                               // squared norm of staged row tid (tid < 192), from the LDS images
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
   d4 acc[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
-  const int sig = 4 * (lr & 3) + (lr >> 2);                        // the column fed as MFMA row lr
-  for (int p0 = 0; p0 < dq; p0 += DC) {
-    const int pc = min(DC, dq - p0);                               // multiple of 4
-    const int h = pc >> 1, q = (tid % h) * 2, rstep = 256 / h;     // 16-byte pieces, lanes along the features of a row: a thread keeps its
-    const d2 o = *(const d2*)(x0 + p0 + q);                        // feature pair q (and its piece of x0) for every row it stages
-    __syncthreads();
-    if (tid < rstep * h) {
-      for (int row = tid / h; row < KB_TM + KB_TN; row += rstep) {
-        const d2 v = *(const d2*)(X + (long)(row < KB_TM ? bi * KB_TM + row : bj * KB_TN + row - KB_TM) * dp + p0 + q);
-        double* dst = row < KB_TM ? Xi + row * LP + q : Xj + (row - KB_TM) * LP + q;
-        *(d2*)dst = v - o;
-      }
-    }
-    __syncthreads();
-    const double* bI = Xi + (16 * wave + lr) * LP + lq;
-    const double* aJ = Xj + sig * LP + lq;
-    for (int kk = 0; kk < pc; kk += 4) {
-      const double b = bI[kk];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aJ[16 * t * LP + kk], b, acc[t], 0, 0, 0);
-    }
-    if (tid < KB_TM + KB_TN) {                                     // (the chunk stays in LDS until the next iteration's first barrier)
-      const double* xr = tid < KB_TM ? Xi + tid * LP : Xj + (tid - KB_TM) * LP;
-      for (int p = 0; p < pc; p += 2) { const d2 u = *(const d2*)(xr + p); sacc = fma(u.x, u.x, sacc); sacc = fma(u.y, u.y, sacc); }
-    }
-  }
-  if (tid < KB_TM) nI[tid] = sacc; else if (tid < KB_TM + KB_TN) nJ[tid - KB_TM] = sacc;
-  __syncthreads();
+  kb_gram_tile<DC>(X, dp, d, bi, bj, Xi, Xj, nI, nJ, acc);
   const int gi = bi * KB_TM + 16 * wave + lr;
   const double ni = nI[16 * wave + lr];
 #pragma unroll
@@ -291,7 +304,7 @@ __global__ __launch_bounds__(256) void kbuild_mfma_kernel(const double* __restri
     KbOut4<double> o64;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      double sq = fmax(fma(-2.0, acc[t][c], ni + njv[c]), 0.0);
+      double sq = kb_gram_sq(acc[t][c], ni, njv[c]);
       if (gi == gj + c) sq = 0.0;
       double v;
       if (gi >= n) v = (gi == gj + c && !full) ? 1.0 : 0.0;
@@ -352,13 +365,16 @@ __global__ void diag_fix_kernel(double* __restrict__ Mat, long ld, int n, int n_
   if (i < n) Mat[(long)i * ld + i] += sn; else Mat[(long)i * ld + i] = 1.0;
 }
 
-// zero-padded copy  dst[rows_pad][dp] <- src[rows][d] (row stride lds)
+// zero-padded copy  dst[rows_pad][dp] <- src[rows][d] (row stride lds); div [d] (optional): column p is divided by div[p] on the way
+// (per-feature length scales, sigp_set_length_scales: an IEEE division, the bits of x / l_p)
 __global__ void pad_copy_kernel(const double* __restrict__ src, long lds, int rows, int d, double* __restrict__ dst,
-                                int rows_pad, int dp) {
+                                int rows_pad, int dp, const double* __restrict__ div = nullptr) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)rows_pad * dp) return;
   const int r = (int)(idx / dp), p = (int)(idx % dp);
-  dst[idx] = (r < rows && p < d) ? src[(long)r * lds + p] : 0.0;
+  double v = (r < rows && p < d) ? src[(long)r * lds + p] : 0.0;
+  if (div != nullptr && p < d) v = v / div[p];
+  dst[idx] = v;
 }
 
 __device__ inline double block_reduce_sum(double v, double* sh) {

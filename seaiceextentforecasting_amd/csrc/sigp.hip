@@ -28,6 +28,7 @@
 #include "predcov.hpp"
 #include "loograd.hpp"
 #include "blockcv.hpp"
+#include "ardgrad.hpp"
 
 using namespace sigp;
 
@@ -99,6 +100,14 @@ struct sigp_handle {
   double* cvPart = nullptr; long cap_cvPart = 0;
   double* cvBlk = nullptr; long cap_cvBlk = 0;
   double* cvVec = nullptr; long cap_cvVec = 0;
+  // per-feature length scales (sigp_ardgrad.inc): the raw features / ride rows beside the scaled ones in X / Xs, the divisors [dp], the
+  // centred scaled features of the gradient pass
+  bool ard_on = false;
+  std::vector<double> ard_ell;
+  double* Xraw = nullptr; long cap_Xraw = 0;
+  double* XsRaw = nullptr; long cap_XsRaw = 0;
+  double* ardDiv = nullptr; long cap_ardDiv = 0;
+  double* ardXc = nullptr; long cap_ardXc = 0;
   int opt_cv_slices = 0;     // K slices of the strip product of sigp_cv: 0 = auto (two workgroups per CU, at most 32), otherwise the count (clipped to the 32-column stages of the fit)
   int cv_slices_used = 0;    // ... and the count the last call ran with (sigp_get_stat "cv_slices")
   int cov_slices_used = 0;   // ... and the count the last call ran with (sigp_get_stat "cov_slices")
@@ -762,7 +771,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 540; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv
+int sigp_version(void) { return 550; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -800,7 +809,7 @@ int sigp_destroy(sigp_handle* h) {
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
   double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
-                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec};
+                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
   if (h->sm_probs) (void)hipFree(h->sm_probs);
@@ -947,6 +956,7 @@ int sigp_set_train(sigp_handle* h, const double* X, int64_t n, int64_t d, int64_
   HIPCHK(h, hipMemsetAsync(h->Xs, 0, (size_t)RIDE * dp * sizeof(double), st));
   HIPCHK(h, hipStreamSynchronize(st));
   h->n = n; h->d = d; h->dp = dp; h->n_pad = n_pad; h->m = 0;
+  h->ard_on = false;                     // what was staged is raw: any per-feature length scales are gone
   h->kss_unit.clear();
   h->built = h->factored = h->fitted = false;
   return SIGP_OK;
@@ -964,6 +974,12 @@ int sigp_set_test(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs) {
     const long tot = m * h->dp;
     hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->stage, (long)ldxs, (int)m, (int)h->d,
                        h->Xs, (int)m, (int)h->dp);
+    HIPCHK(h, hipGetLastError());
+  }
+  if (h->ard_on) {                       // per-feature length scales: keep the raw rows, ride with the scaled ones
+    HIPCHK(h, hipMemcpyAsync(h->XsRaw, h->Xs, (size_t)RIDE * h->dp * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((RIDE * h->dp + 255) / 256)), dim3(256), 0, st, (const double*)h->XsRaw, h->dp, RIDE, (int)h->d, h->Xs, RIDE,
+                       (int)h->dp, (const double*)h->ardDiv);
     HIPCHK(h, hipGetLastError());
   }
   HIPCHK(h, hipStreamSynchronize(st));
@@ -1093,6 +1109,7 @@ int sigp_kernel_build_from_sigma(sigp_handle* h, const double* Sigma, int64_t ld
   if (h && h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "kernel_build_from_sigma: the fp32 engine exposes the fused path only (sigp_fit_predict / batch / predict)");
 
   if (!h || h->n == 0 || !Sigma || ldsigma < h->d) return fail(h, SIGP_BAD_ARG, "kernel_build_from_sigma: bad argument");
+  if (h->ard_on) return fail(h, SIGP_BAD_ARG, "kernel_build_from_sigma: per-feature length scales are set (RBF / MATERN52 only; sigp_set_length_scales(h, NULL, 0) clears them)");
   if (!(sn_tilde >= 0)) return fail(h, SIGP_BAD_ARG, "sn_tilde >= 0 required");
   HIPCHK(h, hipSetDevice(h->device));
   h->kp = make_kparams(SIGP_KERNEL_NETDIFFUSION, 1.0, sn_tilde, 0);
@@ -1289,7 +1306,8 @@ int sigp_predict(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, doub
       const int nch = (int)((mg + RIDE - 1) / RIDE);
       HIPCHK(h, hipMemcpyAsync(h->stage, Xs + c0 * ldxs, (size_t)((mg - 1) * ldxs + h->d) * sizeof(double), hipMemcpyHostToDevice, st));
       const long tot = (long)nch * RIDE * dp;
-      hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->stage, (long)ldxs, (int)mg, (int)h->d, xs_grp, nch * RIDE, (int)dp);
+      hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->stage, (long)ldxs, (int)mg, (int)h->d, xs_grp, nch * RIDE, (int)dp,
+                         h->ard_on ? (const double*)h->ardDiv : nullptr);
       HIPCHK(h, hipGetLastError());
       hipLaunchKernelGGL(ride_build_kernel<double>, dim3((unsigned)((n_pad + 255) / 256), RIDE, (unsigned)nch), dim3(256), 0, st, h->X, 0L, xs_grp, (long)RIDE * dp,
                          (const double*)nullptr, 0L, (int)dp, (int)h->d, (int)n, (int)n_pad, (int)RIDE, 0, h->scratchZ, (long)RIDE * ld, ld, h->pred_kps, 1);
@@ -1315,7 +1333,7 @@ int sigp_predict(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, doub
     {
       const long tot = RIDE * dp;
       hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->stage, (long)ldxs, (int)mc, (int)h->d,
-                         xs_dev, RIDE, (int)dp);
+                         xs_dev, RIDE, (int)dp, h->ard_on ? (const double*)h->ardDiv : nullptr);
       HIPCHK(h, hipGetLastError());
     }
     std::vector<double> kss((size_t)mc, 1.0);
@@ -1835,6 +1853,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_loograd.inc"   // sigp_loo_grad, sigp_loo_grad_batch: exact gradients of the leave-one-out scores
 #include "sigp_predcov.inc"   // sigp_predict_cov: joint predictive covariance at new points
 #include "sigp_blockcv.inc"   // sigp_cv, sigp_cv_batch: leave-block-out cross-validation
+#include "sigp_ardgrad.inc"   // sigp_set_length_scales, sigp_nlml_grad_ard: per-feature length scales and their exact MLII gradient
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"

@@ -82,6 +82,7 @@ int sigp_dist_shutdown(sigp_handle* h) {
 int sigp_dist_fit(sigp_handle* h, int kernel_id, double ell, double sn_tilde, const double* Sigma, int64_t ldsigma, int64_t W, int lookahead,
                   double* out, double* mean, double* var) {
   if (!h || h->n == 0 || !out) return fail(h, SIGP_BAD_ARG, "dist_fit: call set_train first");
+  if (h->ard_on) return fail(h, SIGP_BAD_ARG, "dist_fit: per-feature length scales are set (single-GPU fits only)");
   if (W < 1 || W > 64) return fail(h, SIGP_BAD_ARG, "dist_fit: panel width must be 1..64 blocks");
   if (!(sn_tilde >= 0)) return fail(h, SIGP_BAD_ARG, "sn_tilde >= 0 required");
   if (h->m > 0 && (!mean || !var)) return fail(h, SIGP_BAD_ARG, "dist_fit: mean / var buffers required for the ride-along test points");
@@ -93,6 +94,7 @@ int sigp_dist_fit(sigp_handle* h, int kernel_id, double ell, double sn_tilde, co
 
 int sigp_dist_predict(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, double* mean, double* var) {
   if (!h || !Xs || m < 1 || !mean || !var || ldxs < h->d) return fail(h, SIGP_BAD_ARG, "dist_predict: bad argument");
+  if (h->ard_on) return fail(h, SIGP_BAD_ARG, "dist_predict: per-feature length scales are set (single-GPU fits only)");
   if (h->dc.dead) return fail(h, SIGP_HIP_ERROR, "dist_predict: this handle's communicator died in an earlier call (sigp_dist_shutdown, then a fresh sigp_dist_init*)");
   if (!h->dl.on || !h->dc.fit_ok) return fail(h, SIGP_BAD_ARG, "dist_predict: no successful sigp_dist_fit on this handle");
   if (h->kernel_id != SIGP_KERNEL_RBF && h->kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "dist_predict: RBF / MATERN52 fits only (the reference kernel's test points ride along the fit)");

@@ -48,7 +48,8 @@ int sigp_predict_cov(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, 
   if ((rc = ensure(h, &h->stage, &h->cap_stage, m * ldxs))) return rc;
   // test rows, zero padded to [m_pad][dp] (padding rows are ordinary points at the origin: finite everywhere, never copied out)
   HIPCHK(h, hipMemcpyAsync(h->stage, Xs, (size_t)((m - 1) * ldxs + d) * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((m_pad * dp + 255) / 256)), dim3(256), 0, st, h->stage, (long)ldxs, (int)m, (int)d, h->covXs, (int)m_pad, (int)dp);
+  hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((m_pad * dp + 255) / 256)), dim3(256), 0, st, h->stage, (long)ldxs, (int)m, (int)d, h->covXs, (int)m_pad, (int)dp,
+                     h->ard_on ? (const double*)h->ardDiv : nullptr);
   HIPCHK(h, hipGetLastError());
   constexpr int PRED_CHUNKS = 16;   // lockstep group of the forward solve, as sigp_predict
   if (refk) {

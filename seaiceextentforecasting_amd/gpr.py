@@ -11,6 +11,7 @@ All numerics run in HIP kernels behind libsigp.so (include/sigp.h).  There is no
 the library or a GPU the constructor raises.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -54,6 +55,7 @@ class GPR:
         self._has_data = False
         self._fitted = False
         self._ride = None
+        self._ard = False              # per-feature length scales are set on the handle (sigp_set_length_scales)
         if outer_blocks is not None:
             self.set_option("outer_blocks", outer_blocks)
         if lookahead is not None:
@@ -105,6 +107,7 @@ class GPR:
         self._check(self._lib.sigp_set_train(self._h, L.ptr(X), X.shape[0], X.shape[1], X.shape[1], L.ptr(y)), "set_train")
         self.n, self.d = X.shape
         self._X, self._y = X, y
+        self._ard = False              # sigp_set_train clears the scales
         self._M = None
         if self.kernel == "netdiffusion":
             self._M = laplacian_M(X) if M is None else L.f64(M, 2)
@@ -138,11 +141,33 @@ class GPR:
         self._check(self._lib.sigp_set_test(self._h, L.ptr(Xs), Xs.shape[0], Xs.shape[1]), "set_test")
         self._ride = Xs
 
+    def _set_scales(self, ell):
+        """``ell`` a sequence: per-feature length scales onto the handle, returns them as an array [d].  A scalar: clears any scales that
+        are set (no library call otherwise: scalar fits issue the calls they always did), returns None."""
+        if np.ndim(ell) == 0:
+            if self._ard:
+                self._check(self._lib.sigp_set_length_scales(self._h, None, 0), "set_length_scales")
+                self._ard = False
+            return None
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        vec = L.f64(np.asarray(ell, dtype=np.float64), 1).copy()
+        if vec.shape[0] != self.d:
+            raise ValueError("ell must be a scalar or hold one length scale per feature (%d), got %d" % (self.d, vec.shape[0]))
+        self._check(self._lib.sigp_set_length_scales(self._h, L.ptr(vec), vec.shape[0]), "set_length_scales")
+        self._ard = True
+        return vec
+
     # ---- fit (north/June1st.py:264-271) --------------------------------------------------------
     def fit(self, X, y, ell, sn_tilde, M=None, Xs=None):
         """Kernel build -> Cholesky -> A~ -> profiled sigma_f.  ``Xs`` (optional, <= 127 rows) rides along
         the factorisation so the following ``predict(Xs)`` costs nothing extra.  Raises LinAlgError
-        if K~ is not positive definite, as the reference's live block does."""
+        if K~ is not positive definite, as the reference's live block does.
+
+        ``ell``: a scalar, or a sequence of ``d`` per-feature (ARD) length scales (RBF / Matern, fp64): the library then divides
+        feature k by ``ell[k]`` wherever it stages features (training rows, ``Xs``, the points of later ``predict`` / ``predict_cov`` /
+        ``sample`` calls), so ``loo`` / ``cv`` and the predictions need no scaling by the caller; ``ell_`` becomes that array.  A scalar
+        afterwards returns the handle to the isotropic kernel."""
         self.set_data(X, y, M=M, Xs=Xs)
         return self.refit(ell, sn_tilde)
 
@@ -155,6 +180,9 @@ class GPR:
         mean = np.zeros(max(m, 1))
         var = np.zeros(max(m, 1))
         Sig = None
+        ell_vec = self._set_scales(ell)
+        if ell_vec is not None:
+            ell = 1.0                  # the common multiplier
         if self.kernel == "netdiffusion":
             Sig = L.f64(self._sigma(float(ell)), 2)
             self._Sigma_tilde = Sig
@@ -165,7 +193,7 @@ class GPR:
         if rc == L.NOT_SPD:
             raise LinAlgError("Matrix is not positive definite (pivot %d)" % self.info_, self.info_)
         self._check(rc, "fit")
-        self.ell_, self.sn_tilde_ = float(ell), float(sn_tilde)
+        self.ell_, self.sn_tilde_ = (float(ell) if ell_vec is None else ell_vec), float(sn_tilde)
         self.sigma_f_, self.nlml_, self.sigma_n_ = float(out[0]), float(out[1]), float(out[3])
         self._ride_mean, self._ride_var = mean[:m].copy(), var[:m].copy()
         self._fitted = True
@@ -449,6 +477,7 @@ class GPR:
             ell = float(np.exp(theta[0]))
         if not np.isfinite(ell) or not np.isfinite(np.exp(theta[1])):
             return inf2
+        self._set_scales(ell)          # a scalar length scale: clears per-feature scales if any are set (no library call otherwise)
         Sig = MSig = None
         if self.kernel == "netdiffusion":
             try:
@@ -468,6 +497,47 @@ class GPR:
         if rc == L.NOT_SPD:
             return inf2
         self._check(rc, "nlml")
+        return np.float64(val.value), (None if grad is None else g)
+
+    @staticmethod
+    def _exp(theta):
+        """exp of each entry by the C library's exp, which is what ``sigp_nlml_grad_ard`` applies to theta (NumPy's vectorised exp may differ
+        in the last bit): a ``refit`` at these values repeats the fit the library made, bit for bit"""
+        return np.array([math.exp(t) for t in np.asarray(theta, dtype=np.float64).reshape(-1)])
+
+    def nlml_ard(self, theta, grad="exact"):
+        """MLII with per-feature (ARD) length scales: theta = (log l_1 .. log l_d, log sn~) -> (nlML, grad [d + 1]) (``sigp_nlml_grad_ard``:
+        every component of the exact gradient from one pass over K~^-1); ``grad=None``: value only (second entry None).  A non-SPD K~ or an
+        overflowing exp(theta) gives ``(inf, [inf] * (d + 1))``, like ``nlml``.  Afterwards the handle is fitted at exp(theta) with the scales
+        set: ``predict`` / ``predict_cov`` / ``loo`` / ``cv`` work on it, and ``nlml_`` is the value returned.  RBF / Matern, fp64."""
+        if not self._has_data:
+            raise RuntimeError("nlml_ard: no data staged; call fit() or set_data() first")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
+        if theta.shape[0] != self.d + 1:
+            raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
+        val = C.c_double()
+        g = np.zeros(self.d + 1)
+        self._fitted = False
+        rc = self._lib.sigp_nlml_grad_ard(self._h, self._kid, L.ptr(theta), theta.shape[0], 0 if grad is None else 2, C.byref(val), L.ptr(g))
+        if rc == L.NOT_SPD:
+            self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
+            return np.inf, np.full(self.d + 1, np.inf)
+        self._check(rc, "nlml_ard")
+        self._ard = True
+        sf, nl = C.c_double(), C.c_double()
+        self._check(self._lib.sigp_fit(self._h, C.byref(sf), C.byref(nl)), "nlml_ard")     # the fit's scalars again (its epilogue: the same bits)
+        self.ell_, self.sn_tilde_ = self._exp(theta[:-1]), float(self._exp(theta[-1:])[0])
+        self.sigma_f_, self.nlml_, self.sigma_n_ = float(sf.value), float(val.value), float(sf.value) * self.sn_tilde_
+        m = 0 if self._ride is None else self._ride.shape[0]
+        mean, var = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        if m:
+            self._check(self._lib.sigp_predict_ride(self._h, L.ptr(mean), L.ptr(var)), "nlml_ard")
+        self._ride_mean, self._ride_var = mean[:m].copy(), var[:m].copy()
+        self._fitted = True
         return np.float64(val.value), (None if grad is None else g)
 
     def loo_objective(self, theta, criterion="loo_nlpd", sigma_f="refit"):
@@ -498,14 +568,44 @@ class GPR:
             return inf2
         return np.float64(r[key]), r[key + "_grad"]
 
-    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", **kw):
+    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", ard=False, **kw):
         """The reference's commented-out optimiser call (north/June1st.py:259-262:
         ``minimize(MLII, x0=[log l0, log sn0], method='CG', jac=True)``) against the device engine.
         ``grad='exact'`` (default) feeds the true derivative of the profiled nlML; ``grad='ref'`` reproduces the
         reference's MLII contract verbatim (its "gradient" is not the derivative, so CG stalls as in SURVEY App. C-7).
         ``criterion='loo_nlpd'`` / ``'loo_sse'`` minimises that leave-one-out score instead (``loo_objective`` with ``sigma_f``; grad
-        'exact' or None).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
+        'exact' or None).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``.
+        ``ard=True``: one length scale per feature, by ``nlml_ard``'s exact gradient -- ``theta0`` = (log l_1 .. log l_d, log sn~), or
+        (log l, log sn~) with log l broadcast to every feature; ``criterion`` must be 'nlml'; the relevance of feature k is read from
+        ``result.x[k]`` (a large log l_k: the feature does not matter).  ``bounds`` and the other keywords go to SciPy as they are."""
         from scipy.optimize import minimize
+
+        if ard:
+            if criterion != "nlml":
+                raise ValueError("ard=True: criterion must be 'nlml' (the leave-one-out scores have no per-feature gradient)")
+            if grad not in (None, "exact"):
+                raise ValueError("ard=True takes grad='exact' or None")
+            if not self._has_data:
+                raise RuntimeError("optimize: no data staged; call fit() or set_data() first")
+            th0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
+            if th0.shape[0] == 2 and self.d != 1:
+                th0 = np.concatenate([np.full(self.d, th0[0]), th0[1:]])
+            if th0.shape[0] != self.d + 1:
+                raise ValueError("theta0 must hold d + 1 = %d entries, or 2 (log l is broadcast)" % (self.d + 1))
+            if grad is None:
+                res = minimize(lambda th: float(self.nlml_ard(th, grad=None)[0]), th0, method=method, jac=False, **kw)
+            else:
+                def fun_ard(th):
+                    v, g = self.nlml_ard(th, grad="exact")
+                    return float(v), np.asarray(g, dtype=np.float64)
+
+                res = minimize(fun_ard, th0, method=method, jac=True, **kw)
+            if np.all(np.isfinite(res.x)):
+                try:
+                    self.refit(self._exp(res.x[:-1]), float(self._exp(res.x[-1:])[0]))
+                except LinAlgError:
+                    pass
+            return res
 
         if criterion != "nlml":
             if criterion not in L.LOO_CRITERIA:
@@ -575,8 +675,11 @@ class GPR:
             Sig = L.f64(self._sigma(float(ell)), 2)
             self._check(self._lib.sigp_kernel_build_from_sigma(self._h, L.ptr(Sig), Sig.shape[1], float(sn_tilde)), "kernel_build")
         else:
-            self._check(self._lib.sigp_kernel_build(self._h, self._kid, float(ell), float(sn_tilde)), "kernel_build")
-        self.ell_, self.sn_tilde_ = float(ell), float(sn_tilde)
+            ell_vec = self._set_scales(ell)        # a sequence: per-feature length scales (the build's own ell is then 1)
+            self._check(self._lib.sigp_kernel_build(self._h, self._kid, 1.0 if ell_vec is not None else float(ell), float(sn_tilde)), "kernel_build")
+            if ell_vec is not None:
+                ell = ell_vec
+        self.ell_, self.sn_tilde_ = (ell if np.ndim(ell) else float(ell)), float(sn_tilde)
         self._fitted = False
 
     def kernel_matrix(self, ell, sn_tilde):
