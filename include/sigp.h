@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard; sigp_loo's two + U U^T, the n^2 passes, the product P diag(gamma) P and the tile pass of sigp_loo_grad_ard */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -255,9 +255,8 @@ int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
  * sigp_nlml_grad does.  fp64 engine, RBF / Matern-5/2 only; before sigp_set_train: SIGP_BAD_ARG.  Afterwards the handle is fitted at
  * those hyper-parameters with the scales set: sigp_predict, sigp_predict_ride, sigp_loo, sigp_cv, sigp_predict_cov work on it.  Device
  * work is accounted under SIGP_KC_MLII (the triangular inversion, U U^T, the pass: one entry each).
- * Not covered: per-feature scales in the lockstep-batch entries, ARD gradients of the leave-one-out / leave-block-out scores
- * (sigp_loo_grad differentiates with respect to the common multiplier), the one-workgroup kernel (sigp_small_*), the fp32 engine,
- * sharded fits. */
+ * Not covered: per-feature scales in the lockstep-batch entries, ARD gradients of the leave-block-out scores (those of the leave-one-out
+ * scores: sigp_loo_grad_ard), the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits. */
 int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad);
 
 /* Leave-one-out cross-validation with the hyper-parameters held (Rasmussen & Williams 5.4.2): what the block north/June1st.py:264-277
@@ -293,13 +292,36 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
  * and the fit must have come from sigp_fit_predict, which is told ell: d/dlog ell = ell d/dell), else NULL.  Errors as sigp_loo (fp32 handle,
  * sharded fit, n < 2, not fitted: SIGP_BAD_ARG).  The fit is only read: sigp_predict / sigp_get_alpha / sigp_loo afterwards return the bits
  * they returned before.
- * Not covered: gradients in sigp_small_run_loo (the one-workgroup kernel), sharded fits, the fp32 engine, gradients with respect to
- * per-feature length scales (sigp_set_length_scales: the derivative is then that of the common multiplier ell). */
+ * Not covered: gradients in sigp_small_run_loo (the one-workgroup kernel), sharded fits, the fp32 engine.  With per-feature length scales
+ * set (sigp_set_length_scales) the derivative is that of the common multiplier ell; the per-feature derivatives are sigp_loo_grad_ard's. */
 int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t ldsigma, double* mean, double* var, double* score, double* grad);
 /* Lockstep groups on the resident batch data, arguments as sigp_loo_batch (RBF / Matern only); grad [count][4].  A non-SPD member gets +inf
  * scores and gradients and NaN rows; the other members are not affected. */
 int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde,
                         int sigma_mode, double* mean, double* var, int64_t nstride, double* score, double* grad);
+/* The leave-one-out scores and the exact derivatives of ONE of them with respect to per-feature length scales: theta = (log l_1 .. log l_d,
+ * log sn~), ntheta = d + 1, as sigp_nlml_grad_ard; criterion names the score that grad [d + 1] differentiates.  The call sets the scales
+ * to exp(theta[k]), fits with ell = 1 through sigp_fit_predict's own launches and runs sigp_loo's launches: score [2] and mean / var [n]
+ * (both may be NULL, not one alone) carry the bits sigp_loo returns on that fit.  grad = NULL: scores only, no cubic work beyond sigp_loo's.
+ * The chain rule of sigp_loo_grad is linear in the three quantities that depend on the direction D = dK~/dtheta (b = P D a, c = diag(P D P),
+ * e = a^T D a), so it is transposed into one symmetric adjoint that does not:  d score = beta^T b + gamma^T c + eps e = sum_ij G_ij D_ij,
+ *     G = 1/2 (v a^T + a v^T) + P diag(gamma) P + eps a a^T,   v = P beta,
+ *     nlpd: beta_i = -rho_i/g_i [+ 2 kappa_i a_i/(g_i^2 (n - 1))],  gamma_i = kappa_i s_i/g_i^2 + rho_i a_i/g_i^2 [- kappa_i a_i^2/(g_i^3 (n - 1))],
+ *           eps = -sum_i kappa_i/g_i / (n - 1) [REFIT; the bracketed terms too] or / n [FIXED],  kappa_i = 1/(2 var_i) - r_i^2/(2 var_i^2), rho_i = r_i/var_i;
+ *     sse:  beta_i = -2 r_i/g_i,  gamma_i = 2 r_i a_i/g_i^2,  eps = 0;
+ *     d score / d log l_k = sum_ij G_ij h_ij (u_ik - u_jk)^2  (h as sigp_nlml_grad_ard),     d score / d log sn~ = sn~ tr G.
+ * Cost on top of sigp_loo: K~^-1 = U U^T (n^3/3), ONE cubic product M = (P Gamma) P^T on the lower 128-tiles (n^3 flops, the price of
+ * sigp_loo_grad's one product -- d runs of that route would need d) and sigp_nlml_grad_ard's tile pass with 2 G o h as its weight, all d
+ * components at once; everything else is n^2 passes and fixed-order sums (no atomics: the same bits on every run).  Memory: sigp_loo_grad's
+ * single-fit buffers and the centred features of sigp_nlml_grad_ard.  Device work is accounted under SIGP_KC_MLII (sigp_loo's two entries,
+ * then U U^T, the n^2 passes, the product, the tile pass: one entry each).
+ * SIGP_BAD_ARG: the reference kernel, an fp32 handle, before sigp_set_train, n < 2, ntheta != d + 1, a bad sigma_mode or criterion.
+ * SIGP_NOT_SPD: a non-SPD K~ or an exp(theta[k]) that is not finite and positive (sn~ = 0 is allowed): +inf in score and every grad entry,
+ * NaN in mean / var.  Afterwards the handle is fitted at those hyper-parameters with the scales set, as after sigp_nlml_grad_ard.
+ * Not covered: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits, the leave-block-out scores (sigp_cv). */
+enum { SIGP_LOO_NLPD = 0, SIGP_LOO_SSE = 1 };
+int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int sigma_mode, int criterion,
+                      double* mean, double* var, double* score, double* grad);
 /* sigp_small_run with the leave-one-out cross-validation of every fit in the SAME single launch (L~^-1 formed in LDS over L~ as in
  * sigp_small_run_grad): out6 [nprob][6] = sigma_f, nlML, info, sigma_n, nlpd, sse; mean / var as in sigp_small_run;
  * loo_mean / loo_var [nprob][nstride >= largest n of the upload], entries beyond a set's n = NaN.  info > 0: nlpd = sse = +inf and NaN rows.

@@ -17,6 +17,7 @@ MAX_COV = 8192                            # SIGP_MAX_COV: test points of one sig
 LOO_MODES = {"refit": 0, "fixed": 1}       # SIGP_LOO_REFIT / SIGP_LOO_FIXED
 CV_MAX_WINDOW, CV_SMALL_MAX_WINDOW = 128, 32   # SIGP_CV_MAX_WINDOW / SIGP_CV_SMALL_MAX_WINDOW: widest window block + 2 gap of a fold
 LOO_CRITERIA = {"loo_nlpd": "nlpd", "loo_sse": "sse"}   # optimiser criteria -> keys of GPR.loo's result
+LOO_CRITERION_IDS = {"loo_nlpd": 0, "loo_sse": 1}       # SIGP_LOO_NLPD / SIGP_LOO_SSE (sigp_loo_grad_ard)
 
 _dp = C.POINTER(C.c_double)
 _i64 = C.c_int64
@@ -66,6 +67,7 @@ SIGNATURES = {
     "sigp_loo_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _i64, _dp]),
     "sigp_loo_grad": (C.c_int, [_h, C.c_int, _dp, _i64, _dp, _dp, _dp, _dp]),
     "sigp_loo_grad_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _i64, _dp, _dp]),
+    "sigp_loo_grad_ard": (C.c_int, [_h, C.c_int, _dp, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "sigp_small_run_loo": (C.c_int, [_h, _i64, _ip64, _dp, _dp, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_cv": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _dp]),
     "sigp_cv_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64, _dp]),

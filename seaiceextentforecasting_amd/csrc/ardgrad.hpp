@@ -45,11 +45,16 @@ __global__ __launch_bounds__(256) void ard_center_kernel(const double* __restric
 //     the two products on the matrix pipe (B operand: rows 16 t + 4 lq + c of U_J, 16 consecutive features per quarter wave);
 //   - the 16 x (4 waves x 4 quarter waves) partial sums of a chunk are added in a fixed order: partial[tile][k], no atomics.
 // sf = q[0] / n is read from device memory (the fit's epilogue left y^T a there): no host round trip before the pass.
-template <int DC>
+// WSEL picks the weight: ARD_W_NLML, the adjoint of the nlML above; ARD_W_LOO, the adjoint of a leave-one-out score (looard.hpp) --
+// W = (2 M_ij + v_i a_j + a_i v_j + 2 eps a_i a_j) o h with M = P diag(gamma) P read where P is read (its lower 128-tiles), v = P beta and
+// eps[0] from device memory (q is not read).  Everything after the weight is shared.
+enum { ARD_W_NLML = 0, ARD_W_LOO = 1 };
+template <int DC, int WSEL = ARD_W_NLML>
 __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __restrict__ U, const double* __restrict__ Uc, int dp, int d, int n,
                                                                int kernel_id, const double* __restrict__ P, long ld,
                                                                const double* __restrict__ a, const double* __restrict__ q,
-                                                               double* __restrict__ partial) {
+                                                               double* __restrict__ partial, const double* __restrict__ v = nullptr,
+                                                               const double* __restrict__ eps = nullptr) {
   const int u = blockIdx.x >> 1;                       // (the lower-triangle tile walk of kbuild_mfma_kernel)
   int k = (int)((sqrt(8.0 * u + 1.0) - 1.0) * 0.5);
   while ((k + 1) * (k + 2) / 2 <= u) ++k;
@@ -64,9 +69,15 @@ __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
   d4 acc[8];
   kb_gram_tile<DC>(U, dp, d, bi, bj, Xi, Xj, nI, nJ, acc);
-  const double sf = q[0] / (double)n;
   const int gi = bi * KB_TM + 16 * wave + lr;
-  const double ni = nI[16 * wave + lr], ai_sf = a[gi] / sf;
+  const double ni = nI[16 * wave + lr];
+  double ai_sf = 0.0, ai = 0.0, vi = 0.0, eps2 = 0.0;
+  if constexpr (WSEL == ARD_W_NLML) {
+    const double sf = q[0] / (double)n;
+    ai_sf = a[gi] / sf;
+  } else {
+    ai = a[gi]; vi = v[gi]; eps2 = 2.0 * eps[0];
+  }
   double rowsum = 0.0;
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
@@ -77,10 +88,19 @@ __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __r
     const double pv[4] = {p01.x, p01.y, p23.x, p23.y};
     const d2 a01 = *(const d2*)(a + gj), a23 = *(const d2*)(a + gj + 2);
     const double av[4] = {a01.x, a01.y, a23.x, a23.y};
+    double vv[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (WSEL == ARD_W_LOO) {
+      const d2 v01 = *(const d2*)(v + gj), v23 = *(const d2*)(v + gj + 2);
+      vv[0] = v01.x; vv[1] = v01.y; vv[2] = v23.x; vv[3] = v23.y;
+    }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       double w = 0.0;
-      if (gi < n && gj + c < gi) w = fma(-ai_sf, av[c], pv[c]) * ard_h_from_sq(kernel_id, kb_gram_sq(acc[t][c], ni, njv[c]));
+      if (gi < n && gj + c < gi) {
+        const double h = ard_h_from_sq(kernel_id, kb_gram_sq(acc[t][c], ni, njv[c]));
+        if constexpr (WSEL == ARD_W_NLML) w = fma(-ai_sf, av[c], pv[c]) * h;
+        else w = fma(2.0, pv[c], fma(vi, av[c], ai * fma(eps2, av[c], vv[c]))) * h;
+      }
       acc[t][c] = w;
       rowsum += w;
     }

@@ -29,6 +29,7 @@
 #include "loograd.hpp"
 #include "blockcv.hpp"
 #include "ardgrad.hpp"
+#include "looard.hpp"
 
 using namespace sigp;
 
@@ -771,7 +772,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 550; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard
+int sigp_version(void) { return 560; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -1854,6 +1855,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_predcov.inc"   // sigp_predict_cov: joint predictive covariance at new points
 #include "sigp_blockcv.inc"   // sigp_cv, sigp_cv_batch: leave-block-out cross-validation
 #include "sigp_ardgrad.inc"   // sigp_set_length_scales, sigp_nlml_grad_ard: per-feature length scales and their exact MLII gradient
+#include "sigp_looard.inc"    // sigp_loo_grad_ard: exact per-feature gradients of the leave-one-out scores
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // ride rows beside the scaled ones the builds read (pad_copy_kernel's divisor), and every later staging of test points divides alike.
 // No covariance function and no existing kernel changes; a handle that never sets scales runs the launches it ran before.
 // Out of scope: the lockstep-batch entries (their resident data is staged by sigp_batch_upload and stays isotropic), ARD gradients of
-// the leave-one-out / leave-block-out scores, the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits.
+// the leave-block-out scores (the leave-one-out scores: sigp_looard.inc), the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits.
 
 // X, Xs <- raw / l (or the raw values back); the fit is void afterwards
 static int ard_restage(sigp_handle* h, bool scaled) {

@@ -12,8 +12,8 @@
 // Memory per member: 8 n_pad^2 bytes each for the slot matrix, gU, gK and gD -- the lockstep path holds gD per member, which
 // sigp_nlml_grad_batch avoids by recomputing dK~ on the fly -- plus (5 + n_pad / 128) n_pad doubles of vectors.
 // Profile class: SIGP_KC_MLII (on top of loo_launch's two entries: U U^T, the product W' with n_pad^3 flops, and one entry for the n^2 passes).
-// Out of scope: gradients in sigp_small_run_loo (the one-workgroup LDS kernel), sharded fits, the fp32 engine, gradients with respect to
-// per-feature length scales.
+// Out of scope: gradients in sigp_small_run_loo (the one-workgroup LDS kernel), sharded fits, the fp32 engine.  Gradients with respect to
+// per-feature length scales: sigp_loo_grad_ard (sigp_looard.inc).
 
 static int loo_grad_ensure(sigp_handle* h, int G, long n_pad) {
   int rc;

@@ -527,18 +527,102 @@ class GPR:
             self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
             return np.inf, np.full(self.d + 1, np.inf)
         self._check(rc, "nlml_ard")
+        self._after_ard_call(theta, val.value, "nlml_ard")
+        return np.float64(val.value), (None if grad is None else g)
+
+    def _after_ard_call(self, theta, nlml, what):
+        """the handle's state after a library call that fitted at exp(theta) with per-feature scales: the fit's scalars (its epilogue: the
+        same bits) and the ride predictions"""
         self._ard = True
         sf, nl = C.c_double(), C.c_double()
-        self._check(self._lib.sigp_fit(self._h, C.byref(sf), C.byref(nl)), "nlml_ard")     # the fit's scalars again (its epilogue: the same bits)
+        self._check(self._lib.sigp_fit(self._h, C.byref(sf), C.byref(nl)), what)
         self.ell_, self.sn_tilde_ = self._exp(theta[:-1]), float(self._exp(theta[-1:])[0])
-        self.sigma_f_, self.nlml_, self.sigma_n_ = float(sf.value), float(val.value), float(sf.value) * self.sn_tilde_
+        self.sigma_f_, self.nlml_, self.sigma_n_ = float(sf.value), float(nl.value if nlml is None else nlml), float(sf.value) * self.sn_tilde_
         m = 0 if self._ride is None else self._ride.shape[0]
         mean, var = np.zeros(max(m, 1)), np.zeros(max(m, 1))
         if m:
-            self._check(self._lib.sigp_predict_ride(self._h, L.ptr(mean), L.ptr(var)), "nlml_ard")
+            self._check(self._lib.sigp_predict_ride(self._h, L.ptr(mean), L.ptr(var)), what)
         self._ride_mean, self._ride_var = mean[:m].copy(), var[:m].copy()
         self._fitted = True
-        return np.float64(val.value), (None if grad is None else g)
+
+    def loo_ard(self, theta, criterion="loo_nlpd", sigma_f="refit", grad="exact", predictions=False):
+        """A leave-one-out score with per-feature (ARD) length scales as an optimiser's objective: theta = (log l_1 .. log l_d, log sn~) ->
+        (value, grad [d + 1]) with value = the leave-one-out negative log predictive density (``criterion='loo_nlpd'``) or sum of squared
+        errors (``'loo_sse'``) of the fit at exp(theta) and its exact gradient (``sigp_loo_grad_ard``: one cubic product and one pass for all
+        d components); ``grad=None``: value only (second entry None, no cubic work beyond ``loo``'s).  A non-SPD K~ or an overflowing
+        exp(theta) gives ``(inf, [inf] * (d + 1))``, like ``nlml_ard``.  ``predictions=True`` returns dict(value, grad, mean [n], var [n], nlpd,
+        sse) instead: the bits ``loo(sigma_f)`` returns on that fit.  Afterwards the handle is fitted at exp(theta) with the scales set, as
+        after ``nlml_ard``.  RBF / Matern, fp64."""
+        if criterion not in L.LOO_CRITERION_IDS:
+            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        if not self._has_data:
+            raise RuntimeError("loo_ard: no data staged; call fit() or set_data() first")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
+        if theta.shape[0] != self.d + 1:
+            raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
+        score = np.zeros(2)
+        g = np.zeros(self.d + 1) if grad is not None else None
+        mean = np.zeros(self.n) if predictions else None
+        var = np.zeros(self.n) if predictions else None
+        self._fitted = False
+        rc = self._lib.sigp_loo_grad_ard(self._h, self._kid, L.ptr(theta), theta.shape[0], L.LOO_MODES[sigma_f], L.LOO_CRITERION_IDS[criterion],
+                                         L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g))
+        if rc == L.NOT_SPD:
+            self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
+            value, g = np.inf, (None if grad is None else np.full(self.d + 1, np.inf))
+        else:
+            self._check(rc, "loo_ard")
+            self._after_ard_call(theta, None, "loo_ard")
+            value = np.float64(score[L.LOO_CRITERION_IDS[criterion]])
+        if predictions:
+            return dict(value=value, grad=g, mean=mean, var=var, nlpd=float(score[0]), sse=float(score[1]))
+        return value, g
+
+    def optimize_ard(self, theta0, criterion="nlml", sigma_f="refit", method="L-BFGS-B", grad="exact", **kw):
+        """Minimise ``criterion`` over one length scale per feature and the noise: 'nlml' (``nlml_ard``; what ``optimize(ard=True)`` does),
+        'loo_nlpd' or 'loo_sse' (``loo_ard`` with ``sigma_f``) -- with d + 1 hyper-parameters and few data the marginal likelihood overfits the
+        relevance of features, and the predictive score is the honest objective.  ``theta0`` = (log l_1 .. log l_d, log sn~), or (log l, log sn~)
+        with log l broadcast to every feature; ``grad`` 'exact' or None (SciPy then differences the value).  ``bounds`` and the other keywords
+        go to SciPy as they are.  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
+        from scipy.optimize import minimize
+
+        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS:
+            raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if grad not in (None, "exact"):
+            raise ValueError("optimize_ard takes grad='exact' or None")
+        if not self._has_data:
+            raise RuntimeError("optimize_ard: no data staged; call fit() or set_data() first")
+        th0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
+        if th0.shape[0] == 2 and self.d != 1:
+            th0 = np.concatenate([np.full(self.d, th0[0]), th0[1:]])
+        if th0.shape[0] != self.d + 1:
+            raise ValueError("theta0 must hold d + 1 = %d entries, or 2 (log l is broadcast)" % (self.d + 1))
+        if criterion == "nlml":
+            objective = lambda th: self.nlml_ard(th, grad=grad)
+        else:
+            objective = lambda th: self.loo_ard(th, criterion=criterion, sigma_f=sigma_f, grad=grad)
+        if grad is None:
+            res = minimize(lambda th: float(objective(th)[0]), th0, method=method, jac=False, **kw)
+        else:
+            def fun_ard(th):
+                v, g = objective(th)
+                return float(v), np.asarray(g, dtype=np.float64)
+
+            res = minimize(fun_ard, th0, method=method, jac=True, **kw)
+        if np.all(np.isfinite(res.x)):
+            try:
+                self.refit(self._exp(res.x[:-1]), float(self._exp(res.x[-1:])[0]))
+            except LinAlgError:
+                pass
+        return res
 
     def loo_objective(self, theta, criterion="loo_nlpd", sigma_f="refit"):
         """A leave-one-out score as an optimiser's objective: theta = (log l, log sn~) -> (value, grad[2]) with value = the
@@ -576,13 +660,13 @@ class GPR:
         ``criterion='loo_nlpd'`` / ``'loo_sse'`` minimises that leave-one-out score instead (``loo_objective`` with ``sigma_f``; grad
         'exact' or None).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``.
         ``ard=True``: one length scale per feature, by ``nlml_ard``'s exact gradient -- ``theta0`` = (log l_1 .. log l_d, log sn~), or
-        (log l, log sn~) with log l broadcast to every feature; ``criterion`` must be 'nlml'; the relevance of feature k is read from
+        (log l, log sn~) with log l broadcast to every feature; ``criterion`` must be 'nlml' here (``optimize_ard`` takes the others); the relevance of feature k is read from
         ``result.x[k]`` (a large log l_k: the feature does not matter).  ``bounds`` and the other keywords go to SciPy as they are."""
         from scipy.optimize import minimize
 
         if ard:
             if criterion != "nlml":
-                raise ValueError("ard=True: criterion must be 'nlml' (the leave-one-out scores have no per-feature gradient)")
+                raise ValueError("ard=True: criterion must be 'nlml' (optimize_ard minimises the leave-one-out scores over per-feature scales)")
             if grad not in (None, "exact"):
                 raise ValueError("ard=True takes grad='exact' or None")
             if not self._has_data:
