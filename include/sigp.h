@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard; sigp_loo's two + U U^T, the n^2 passes, the product P diag(gamma) P and the tile pass of sigp_loo_grad_ard */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard; sigp_loo's two + U U^T, the n^2 passes, the product P diag(gamma) P and the tile pass of sigp_loo_grad_ard; sigp_cv's entries + per pass the fold adjoints and their assembly, then U U^T, the n^2 passes, the banded product P B, the product (P B) P and the tile pass of sigp_cv_grad_ard */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -255,8 +255,8 @@ int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
  * sigp_nlml_grad does.  fp64 engine, RBF / Matern-5/2 only; before sigp_set_train: SIGP_BAD_ARG.  Afterwards the handle is fitted at
  * those hyper-parameters with the scales set: sigp_predict, sigp_predict_ride, sigp_loo, sigp_cv, sigp_predict_cov work on it.  Device
  * work is accounted under SIGP_KC_MLII (the triangular inversion, U U^T, the pass: one entry each).
- * Not covered: per-feature scales in the lockstep-batch entries, ARD gradients of the leave-block-out scores (those of the leave-one-out
- * scores: sigp_loo_grad_ard), the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits. */
+ * Not covered: per-feature scales in the lockstep-batch entries (the ARD gradients of the leave-one-out and leave-block-out scores are
+ * sigp_loo_grad_ard's and sigp_cv_grad_ard's), the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits. */
 int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad);
 
 /* Leave-one-out cross-validation with the hyper-parameters held (Rasmussen & Williams 5.4.2): what the block north/June1st.py:264-277
@@ -318,7 +318,7 @@ int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
  * SIGP_BAD_ARG: the reference kernel, an fp32 handle, before sigp_set_train, n < 2, ntheta != d + 1, a bad sigma_mode or criterion.
  * SIGP_NOT_SPD: a non-SPD K~ or an exp(theta[k]) that is not finite and positive (sn~ = 0 is allowed): +inf in score and every grad entry,
  * NaN in mean / var.  Afterwards the handle is fitted at those hyper-parameters with the scales set, as after sigp_nlml_grad_ard.
- * Not covered: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits, the leave-block-out scores (sigp_cv). */
+ * Not covered: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits.  The leave-block-out scores: sigp_cv_grad_ard. */
 enum { SIGP_LOO_NLPD = 0, SIGP_LOO_SSE = 1 };
 int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int sigma_mode, int criterion,
                       double* mean, double* var, double* score, double* grad);
@@ -363,6 +363,31 @@ int sigp_cv_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, c
 int sigp_small_run_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block,
                       int64_t gap, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var,
                       int64_t nstride);
+/* The leave-block-out scores and the exact derivatives of ONE of them with respect to per-feature length scales: theta, ntheta = d + 1,
+ * criterion (SIGP_LOO_NLPD / SIGP_LOO_SSE) and mean / var [n] (both or neither) as sigp_loo_grad_ard; block, gap and the fold limits as
+ * sigp_cv.  The call sets the scales to exp(theta[k]), fits with ell = 1 through sigp_fit_predict's own launches and runs sigp_cv's
+ * launches: score [2], mean and var carry the bits sigp_cv returns on that fit (at the same "cv_slices").  grad = NULL: scores only.
+ * The adjoint of sigp_loo_grad_ard with a block in place of the diagonal.  Per fold f with window S (w rows), scored
+ * rows C, H = P_SS^-1, r = H A~_S, s as sigp_cv, var_i = s H_ii:  rbar_i = r_i/var_i, kappa_i = 1/(2 var_i) - r_i^2/(2 var_i^2) (nlpd) or
+ * rbar_i = 2 r_i, kappa_i = 0 (sse) on C and zero outside;  t = H rbar,  sbar = sum_C kappa_i H_ii;
+ *     beta_f = -t [+ 2 sbar r/(n - w)],  B_f = 1/2 (t r^T + r t^T) + s H diag(kappa) H [- sbar r r^T/(n - w)],  eps += -sbar/(n - w) [REFIT; the
+ *     bracketed terms too] or -sbar/n [FIXED];   beta = sum_f E_f beta_f,  B = sum_f E_f B_f E_f^T (symmetric, |i - j| < 128),
+ *     d score = sum_ij G_ij D_ij,   G = 1/2 (v a^T + a v^T) + P B P + eps a a^T,   v = P beta,
+ *     d score / d log l_k = sum_ij G_ij h_ij (u_ik - u_jk)^2,     d score / d log sn~ = sn~ tr G.
+ * block = 1, gap = 0 is sigp_loo_grad_ard's adjoint.  Cost on top of sigp_cv: per fold two products of the window's size on the fp64 matrix
+ * pipe; K~^-1 = U U^T (n^3/3); P B over B's band (6 x 128 n_pad^2 flops); ONE cubic product M = (P B) P^T on the lower 128-tiles (n^3 flops for
+ * any d and any fold layout) and sigp_nlml_grad_ard's tile pass.  Every sum has a fixed order (no atomics: the same bits on every run).
+ * Memory: sigp_loo_grad's single-fit buffers, sigp_cv's workspaces, the centred features, B in a band store (8 x 384 n_pad bytes) and
+ * B_f / beta_f of one pass of at most 1024 folds (8 (window rounded up to 16)^2 bytes per fold).  Device work is accounted under SIGP_KC_MLII
+ * (sigp_cv's entries and two more per pass -- the fold adjoints, their assembly -- then U U^T, the n^2 passes, the banded product, the
+ * product M, the tile pass: one entry each).
+ * SIGP_BAD_ARG: as sigp_loo_grad_ard, and sigp_cv's fold checks (block + 2 gap <= SIGP_CV_MAX_WINDOW, every fold leaves a training row).
+ * SIGP_NOT_SPD: a non-SPD K~, an exp(theta[k]) that is not finite and positive, or a fold whose P_SS fails its pivot test: +inf in score and
+ * every grad entry, NaN in mean / var.  Afterwards the handle is fitted at those hyper-parameters with the scales set, as after
+ * sigp_loo_grad_ard.
+ * Not covered: the lockstep-batch entries (and optimize_batch), sigp_small_*, the reference kernel, the fp32 engine, sharded fits. */
+int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int64_t block, int64_t gap, int sigma_mode,
+                     int criterion, double* mean, double* var, double* score, double* grad);
 
 /* One large fit sharded over the GPUs of a node (BASELINE configs[3] fp64, configs[4] fp32 + fp64 refinement): 1-D block-cyclic
  * ownership of outer panels (W column blocks of 128; panel q belongs to rank q % nranks), OWNER-ONLY storage -- a rank allocates,

@@ -18,6 +18,7 @@ LOO_MODES = {"refit": 0, "fixed": 1}       # SIGP_LOO_REFIT / SIGP_LOO_FIXED
 CV_MAX_WINDOW, CV_SMALL_MAX_WINDOW = 128, 32   # SIGP_CV_MAX_WINDOW / SIGP_CV_SMALL_MAX_WINDOW: widest window block + 2 gap of a fold
 LOO_CRITERIA = {"loo_nlpd": "nlpd", "loo_sse": "sse"}   # optimiser criteria -> keys of GPR.loo's result
 LOO_CRITERION_IDS = {"loo_nlpd": 0, "loo_sse": 1}       # SIGP_LOO_NLPD / SIGP_LOO_SSE (sigp_loo_grad_ard)
+CV_CRITERION_IDS = {"cv_nlpd": 0, "cv_sse": 1}          # the same ids for the leave-block-out scores (sigp_cv_grad_ard)
 
 _dp = C.POINTER(C.c_double)
 _i64 = C.c_int64
@@ -72,6 +73,7 @@ SIGNATURES = {
     "sigp_cv": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _dp]),
     "sigp_cv_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64, _dp]),
     "sigp_small_run_cv": (C.c_int, [_h, _i64, _ip64, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
+    "sigp_cv_grad_ard": (C.c_int, [_h, C.c_int, _dp, _i64, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "sigp_dist_unique_id": (C.c_int, [C.c_void_p]),
     "sigp_dist_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),
     "sigp_dist_init_transport": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),

@@ -30,6 +30,7 @@
 #include "blockcv.hpp"
 #include "ardgrad.hpp"
 #include "looard.hpp"
+#include "cvard.hpp"
 
 using namespace sigp;
 
@@ -101,6 +102,7 @@ struct sigp_handle {
   double* cvPart = nullptr; long cap_cvPart = 0;
   double* cvBlk = nullptr; long cap_cvBlk = 0;
   double* cvVec = nullptr; long cap_cvVec = 0;
+  double* cvAdj = nullptr; long cap_cvAdj = 0;   // sigp_cv_grad_ard (sigp_cvard.inc): the band store of B, B_f / beta_f of one pass, eps_f
   // per-feature length scales (sigp_ardgrad.inc): the raw features / ride rows beside the scaled ones in X / Xs, the divisors [dp], the
   // centred scaled features of the gradient pass
   bool ard_on = false;
@@ -772,7 +774,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 560; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard
+int sigp_version(void) { return 570; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -810,7 +812,7 @@ int sigp_destroy(sigp_handle* h) {
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
   double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
-                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc};
+                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->cvAdj, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
   if (h->sm_probs) (void)hipFree(h->sm_probs);
@@ -1856,6 +1858,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_blockcv.inc"   // sigp_cv, sigp_cv_batch: leave-block-out cross-validation
 #include "sigp_ardgrad.inc"   // sigp_set_length_scales, sigp_nlml_grad_ard: per-feature length scales and their exact MLII gradient
 #include "sigp_looard.inc"    // sigp_loo_grad_ard: exact per-feature gradients of the leave-one-out scores
+#include "sigp_cvard.inc"     // sigp_cv_grad_ard: exact per-feature gradients of the leave-block-out scores
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"

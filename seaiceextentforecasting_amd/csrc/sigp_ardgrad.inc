@@ -2,8 +2,8 @@
 // The ARD kernel is the isotropic one at ell = 1 on u = x / l, so the scales live in the STAGING: the handle keeps the raw features and
 // ride rows beside the scaled ones the builds read (pad_copy_kernel's divisor), and every later staging of test points divides alike.
 // No covariance function and no existing kernel changes; a handle that never sets scales runs the launches it ran before.
-// Out of scope: the lockstep-batch entries (their resident data is staged by sigp_batch_upload and stays isotropic), ARD gradients of
-// the leave-block-out scores (the leave-one-out scores: sigp_looard.inc), the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits.
+// Out of scope: the lockstep-batch entries (their resident data is staged by sigp_batch_upload and stays isotropic), the one-workgroup
+// kernel (sigp_small_*), the fp32 engine, sharded fits.  ARD gradients of the leave-one-out / leave-block-out scores: sigp_looard.inc, sigp_cvard.inc.
 
 // X, Xs <- raw / l (or the raw values back); the fit is void afterwards
 static int ard_restage(sigp_handle* h, bool scaled) {

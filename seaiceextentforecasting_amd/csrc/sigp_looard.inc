@@ -11,7 +11,7 @@
 //   the ARD pass     ard_grad_partial_kernel<., ARD_W_LOO> over M, v, a, eps, then loo_ard_finish_kernel
 // Memory: sigp_loo_grad's single-fit buffers (gU, gK, gD, gV, gPart; gPart also holds the pass's per-tile partials) plus ardXc.
 // Profile class: SIGP_KC_MLII (on top of loo_launch's two entries: U U^T, the n^2 passes, the product M, the ARD pass: one entry each).
-// Out of scope: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits, the leave-block-out scores.
+// Out of scope: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits.  The leave-block-out scores: sigp_cvard.inc.
 
 int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int sigma_mode, int criterion, double* mean, double* var, double* score,
                       double* grad) {

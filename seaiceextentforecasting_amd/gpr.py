@@ -584,20 +584,77 @@ class GPR:
             return dict(value=value, grad=g, mean=mean, var=var, nlpd=float(score[0]), sse=float(score[1]))
         return value, g
 
-    def optimize_ard(self, theta0, criterion="nlml", sigma_f="refit", method="L-BFGS-B", grad="exact", **kw):
+    def cv_ard(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit", grad="exact", predictions=False):
+        """A leave-block-out score with per-feature (ARD) length scales as an optimiser's objective: theta = (log l_1 .. log l_d, log sn~) ->
+        (value, grad [d + 1]) with value = the negative log predictive density (``criterion='cv_nlpd'``) or sum of squared errors
+        (``'cv_sse'``) of ``cv(block, gap, sigma_f)`` on the fit at exp(theta), and its exact gradient (``sigp_cv_grad_ard``: the adjoint of
+        ``loo_ard`` with a block in place of the diagonal -- one cubic product and one pass for all d components, whatever the folds);
+        ``grad=None``: value only (second entry None, no work beyond ``cv``'s).  A non-SPD K~, an overflowing exp(theta) or a fold whose block
+        of K~^-1 is not SPD gives ``(inf, [inf] * (d + 1))``.  ``predictions=True`` returns dict(value, grad, mean [n], var [n], nlpd, sse)
+        instead: the bits ``cv(block, gap, sigma_f)`` returns on that fit.  Afterwards the handle is fitted at exp(theta) with the scales set,
+        as after ``loo_ard``.  RBF / Matern, fp64; block + 2 gap <= 128 and every fold must leave a training row."""
+        if criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse'")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
+        if not self._has_data:
+            raise RuntimeError("cv_ard: no data staged; call fit() or set_data() first")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
+        if theta.shape[0] != self.d + 1:
+            raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
+        score = np.zeros(2)
+        g = np.zeros(self.d + 1) if grad is not None else None
+        mean = np.zeros(self.n) if predictions else None
+        var = np.zeros(self.n) if predictions else None
+        self._fitted = False
+        rc = self._lib.sigp_cv_grad_ard(self._h, self._kid, L.ptr(theta), theta.shape[0], block, gap, L.LOO_MODES[sigma_f], L.CV_CRITERION_IDS[criterion],
+                                        L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g))
+        if rc == L.NOT_SPD:
+            self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
+            value, g = np.inf, (None if grad is None else np.full(self.d + 1, np.inf))
+        else:
+            self._check(rc, "cv_ard")
+            self._after_ard_call(theta, None, "cv_ard")
+            value = np.float64(score[L.CV_CRITERION_IDS[criterion]])
+        if predictions:
+            return dict(value=value, grad=g, mean=mean, var=var, nlpd=float(score[0]), sse=float(score[1]))
+        return value, g
+
+    def cv_objective(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit"):
+        """A leave-block-out score as an optimiser's objective over ONE common length scale: theta = (log l, log sn~) -> (value, grad [2])
+        with value = the ``criterion`` ('cv_nlpd' | 'cv_sse') of ``cv(block, gap, sigma_f)`` on the fit at exp(theta).  It is ``cv_ard`` at equal
+        scales with d/dlog l = sum_k d/dlog l_k.  A non-SPD K~ or an overflowing exp(theta) gives ``(inf, [inf, inf])``.  Afterwards the
+        handle is fitted at exp(theta), the scales set to the common l.  RBF / Matern, fp64."""
+        if self.kernel == "netdiffusion":
+            raise ValueError("cv_objective covers the RBF / Matern kernels (the reference kernel's leave-block-out scores have no gradient: cv_grid)")
+        theta = np.asarray(theta, dtype=np.float64).reshape(2)
+        d = getattr(self, "d", None) if getattr(self, "_has_data", False) else None
+        v, g = self.cv_ard(theta if d is None else np.concatenate([np.full(d, theta[0]), theta[1:]]), block, gap=gap, criterion=criterion, sigma_f=sigma_f)
+        return v, np.array([np.sum(g[:-1]), g[-1]])
+
+    def optimize_ard(self, theta0, criterion="nlml", sigma_f="refit", method="L-BFGS-B", grad="exact", block=5, gap=0, **kw):
         """Minimise ``criterion`` over one length scale per feature and the noise: 'nlml' (``nlml_ard``; what ``optimize(ard=True)`` does),
-        'loo_nlpd' or 'loo_sse' (``loo_ard`` with ``sigma_f``) -- with d + 1 hyper-parameters and few data the marginal likelihood overfits the
-        relevance of features, and the predictive score is the honest objective.  ``theta0`` = (log l_1 .. log l_d, log sn~), or (log l, log sn~)
+        'loo_nlpd' or 'loo_sse' (``loo_ard`` with ``sigma_f``), 'cv_nlpd' or 'cv_sse' (``cv_ard`` with ``block``, ``gap`` and ``sigma_f``) -- with
+        d + 1 hyper-parameters and few data the marginal likelihood overfits the relevance of features, and the predictive score is the honest
+        objective; for ordered rows (consecutive years) the leave-block-out one, since ``loo`` keeps a row's correlated neighbours in the
+        training set.  ``theta0`` = (log l_1 .. log l_d, log sn~), or (log l, log sn~)
         with log l broadcast to every feature; ``grad`` 'exact' or None (SciPy then differences the value).  ``bounds`` and the other keywords
         go to SciPy as they are.  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
         from scipy.optimize import minimize
 
-        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS:
-            raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS and criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd' or 'cv_sse'")
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
         if grad not in (None, "exact"):
             raise ValueError("optimize_ard takes grad='exact' or None")
+        if criterion in L.CV_CRITERION_IDS:
+            block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
+            if self.kernel == "netdiffusion" or self.dtype != "f64":
+                raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
         if not self._has_data:
             raise RuntimeError("optimize_ard: no data staged; call fit() or set_data() first")
         th0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
@@ -607,6 +664,8 @@ class GPR:
             raise ValueError("theta0 must hold d + 1 = %d entries, or 2 (log l is broadcast)" % (self.d + 1))
         if criterion == "nlml":
             objective = lambda th: self.nlml_ard(th, grad=grad)
+        elif criterion in L.CV_CRITERION_IDS:
+            objective = lambda th: self.cv_ard(th, block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad=grad)
         else:
             objective = lambda th: self.loo_ard(th, criterion=criterion, sigma_f=sigma_f, grad=grad)
         if grad is None:
@@ -652,13 +711,14 @@ class GPR:
             return inf2
         return np.float64(r[key]), r[key + "_grad"]
 
-    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", ard=False, **kw):
+    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", ard=False, block=5, gap=0, **kw):
         """The reference's commented-out optimiser call (north/June1st.py:259-262:
         ``minimize(MLII, x0=[log l0, log sn0], method='CG', jac=True)``) against the device engine.
         ``grad='exact'`` (default) feeds the true derivative of the profiled nlML; ``grad='ref'`` reproduces the
         reference's MLII contract verbatim (its "gradient" is not the derivative, so CG stalls as in SURVEY App. C-7).
         ``criterion='loo_nlpd'`` / ``'loo_sse'`` minimises that leave-one-out score instead (``loo_objective`` with ``sigma_f``; grad
-        'exact' or None).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``.
+        'exact' or None); ``criterion='cv_nlpd'`` / ``'cv_sse'`` the leave-block-out score of ``cv(block, gap, sigma_f)`` (``cv_objective``;
+        RBF / Matern).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``.
         ``ard=True``: one length scale per feature, by ``nlml_ard``'s exact gradient -- ``theta0`` = (log l_1 .. log l_d, log sn~), or
         (log l, log sn~) with log l broadcast to every feature; ``criterion`` must be 'nlml' here (``optimize_ard`` takes the others); the relevance of feature k is read from
         ``result.x[k]`` (a large log l_k: the feature does not matter).  ``bounds`` and the other keywords go to SciPy as they are."""
@@ -691,9 +751,28 @@ class GPR:
                     pass
             return res
 
-        if criterion != "nlml":
+        if criterion in L.CV_CRITERION_IDS:
+            if grad not in (None, "exact"):
+                raise ValueError("a leave-block-out criterion takes grad='exact' or None")
+            if self.kernel == "netdiffusion":
+                raise ValueError("criterion 'cv_nlpd' / 'cv_sse' covers the RBF / Matern kernels (the reference kernel: cv_grid)")
+            if self.dtype != "f64":
+                raise ValueError("criterion 'cv_nlpd' / 'cv_sse': fp64 engine only")
+            block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
+            if not self._has_data:
+                raise RuntimeError("optimize: no data staged; call fit() or set_data() first")
+            th0 = np.asarray(theta0, dtype=np.float64).reshape(2)
+
+            def fun(th):
+                if grad is None:
+                    return float(self.cv_ard(np.concatenate([np.full(self.d, th[0]), th[1:]]), block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad=None)[0])
+                v, g = self.cv_objective(th, block, gap=gap, criterion=criterion, sigma_f=sigma_f)
+                return float(v), np.asarray(g, dtype=np.float64)
+
+            res = minimize(fun, th0, method=method, jac=grad is not None, **kw)
+        elif criterion != "nlml":
             if criterion not in L.LOO_CRITERIA:
-                raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+                raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd' or 'cv_sse'")
             if grad not in (None, "exact"):
                 raise ValueError("a leave-one-out criterion takes grad='exact' or None")
 
