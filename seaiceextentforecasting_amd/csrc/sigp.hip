@@ -1575,6 +1575,8 @@ static int build_xsxt(sigp_handle* h, const double* S, int64_t lds, double* D) {
   return launch_gemm_cfg<64, 64, 2, 2, GEMM_SET, false>(h, st, g2);
 }
 
+#include "sigp_scores.inc"    // the steps the score and gradient entry points below share (U = L~^-T, U U^T, a = U z, the ARD tile pass, the lockstep group fit, read-backs)
+
 int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const double* Sigma, const double* MSigma, int64_t ldsigma,
                    int grad_mode, double* nlml, double grad[2]) {
   if (!h || !theta || !nlml || h->n == 0) return fail(h, SIGP_BAD_ARG, "nlml_grad: bad argument");
@@ -1597,32 +1599,16 @@ int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const d
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad, ld = n_pad;
-  const int T = (int)(n_pad / NB);
   const double sf = out[0];
   if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
   if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
   if ((rc = ensure(h, &h->gD, &h->cap_gD, n_pad * n_pad))) return rc;
   if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad))) return rc;
   if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)RIDE * n_pad))) return rc;
-  // U = L~^-T (upper triangular, row-major in gU); P parks in gK
-  {
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * n_pad / 3, 0.0);
-    if ((rc = trtri_levels<double>(h, st, s.mat, ld, s.dinv, h->gU, h->gK, ld, T, T))) return rc;
-  }
-  // K~^-1 = U U^T on the lower 128-tiles (LDS-DMA kernel; rows of U are zero left of their diagonal block, so tile (i, j)
-  // sums k from 128 i: n^3/3 flops)
-  {
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * n_pad / 3, 0.0);
-    GemmArgs g{};
-    g.A = h->gU; g.lda = ld; g.B = h->gU; g.ldb = ld; g.C = h->gK; g.ldc = ld; g.K = (int)n_pad;
-    g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 1; g.ktri = 1;
-    if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
-  }
-  // A~ = L~^-T z = U z: one skinny product with the upper-triangular U (one wave per row, k from the diagonal) instead of a
-  // backward block solve of 2 launches per 128 columns
-  hipLaunchKernelGGL(rowdot_kernel<double>, dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, st, (const double*)h->gU, ld, (int)n_pad, (int)n_pad, 2,
-                     (const double*)(s.mat + n_pad * ld), ld, h->scratchZ, ld, 1, 0);
-  HIPCHK(h, hipGetLastError());
+  // U = L~^-T in gU, K~^-1 = U U^T on the lower 128-tiles of gK, A~ = L~^-T z = U z
+  if ((rc = inv_factor(h, st, 1, s.mat, 0, s.dinv, 0, n_pad))) return rc;
+  if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
+  if ((rc = alpha_from_U(h, st, 1, s.mat + n_pad * ld, 0, h->scratchZ, 0, n_pad))) return rc;
   // dK~_1 (full symmetric): the reference's X (M Sigma~) X^T, or d k~/d log l for RBF / Matern
   if (kernel_id == SIGP_KERNEL_NETDIFFUSION) {
     if ((rc = build_xsxt(h, MSigma, ldsigma, h->gD))) return rc;
@@ -1671,7 +1657,6 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
   if (grad_mode != 0 && !grad) return fail(h, SIGP_BAD_ARG, "nlml_grad_batch: grad buffer required");
   HIPCHK(h, hipSetDevice(h->device));
   const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad, ld = n_pad;
-  const int T = (int)(n_pad / NB);
   const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
   const double inf = std::numeric_limits<double>::infinity();
   Slot& s = h->slots[0];
@@ -1679,12 +1664,11 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
   int rc;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
   if (grad_mode != 0) {
-    if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
-    if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
-    if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4)))) return rc;
+    if ((rc = scores_ensure(h, G, n_pad))) return rc;
     if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)G * n_pad))) return rc;
   }
   std::vector<double> sums((size_t)G * 4);
+  std::vector<int> ds((size_t)G);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
     std::vector<double> ell((size_t)nb), snt((size_t)nb);
@@ -1692,41 +1676,16 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
     for (int b = 0; b < nb; ++b) {
       ell[(size_t)b] = std::exp(theta[2 * (g0 + b)]); snt[(size_t)b] = std::exp(theta[2 * (g0 + b) + 1]);
       if (!std::isfinite(ell[(size_t)b]) || !std::isfinite(snt[(size_t)b]) || !(ell[(size_t)b] > 0)) { ok[(size_t)b] = 0; ell[(size_t)b] = 1.0; snt[(size_t)b] = 1.0; }
-      s.kps_host[b] = make_kparams(kernel_id, ell[(size_t)b], snt[(size_t)b], (int)((first + g0 + b) % h->b_count));
+      ds[(size_t)b] = (int)((first + g0 + b) % h->b_count);
     }
-    if ((rc = upload_kparams(h, s, nb))) return rc;
-    if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
-    if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
-    if ((rc = epilogue_slot(h, s, nb, n, n_pad, 0))) return rc;
+    if ((rc = batch_group_fit(h, s, nb, kernel_id, ell.data(), snt.data(), first + g0))) return rc;
     if (grad_mode != 0) {
-      // U = L~^-T for every member at once, P parks in gK
-      {
-        ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
-        if ((rc = trtri_levels<double>(h, st, s.mat, ld, s.dinv, h->gU, h->gK, ld, T, T, nb, s.matStride, s.dinvStride, n_pad * n_pad))) return rc;
-      }
-      {   // K~^-1 = U U^T, lower tiles
-        ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
-        GemmArgs g{};
-        g.A = h->gU; g.lda = ld; g.B = h->gU; g.ldb = ld; g.C = h->gK; g.ldc = ld; g.K = (int)n_pad;
-        g.batch = nb; g.sA = g.sB = g.sC = n_pad * n_pad;
-        g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 1; g.ktri = 1;
-        if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
-      }
-      // A~ = U z  (z = solved ride row 0 of each member)
-      hipLaunchKernelGGL(rowdot_kernel<double>, dim3((unsigned)((n_pad + 3) / 4), (unsigned)nb), dim3(256), 0, st, (const double*)h->gU, ld, (int)n_pad, (int)n_pad, 2,
-                         (const double*)(s.mat + n_pad * ld), ld, h->scratchZ, ld, 1, 0, (const double*)nullptr, 0, 0, n_pad * n_pad, s.matStride, n_pad);
-      HIPCHK(h, hipGetLastError());
-      // derivative covariance ids for the on-the-fly dK~/dlog l (same data sets, same length scales); from pageable memory: the
-      // copy call returns once the host buffer has been staged, so the vector may go out of scope
-      std::vector<KParams> dkp((size_t)nb);
-      for (int b = 0; b < nb; ++b) { dkp[(size_t)b] = make_kparams(kernel_id, ell[(size_t)b], snt[(size_t)b], (int)((first + g0 + b) % h->b_count)); dkp[(size_t)b].kernel_id = kernel_id == SIGP_KERNEL_RBF ? KID_RBF_DLOGL : KID_MATERN52_DLOGL; }
-      if (h->cap_gKps < nb) {
-        if (h->gKps) HIPCHK(h, hipFree(h->gKps));
-        h->gKps = nullptr; h->cap_gKps = 0;
-        HIPCHK(h, hipMalloc((void**)&h->gKps, (size_t)G * sizeof(KParams)));
-        h->cap_gKps = G;
-      }
-      HIPCHK(h, hipMemcpyAsync(h->gKps, dkp.data(), (size_t)nb * sizeof(KParams), hipMemcpyHostToDevice, st));
+      // for every member at once: U = L~^-T, K~^-1 = U U^T, A~ = U z (z = solved ride row 0 of each member)
+      if ((rc = inv_factor(h, st, nb, s.mat, s.matStride, s.dinv, s.dinvStride, n_pad))) return rc;
+      if ((rc = kinv_lower(h, st, nb, n_pad))) return rc;
+      if ((rc = alpha_from_U(h, st, nb, s.mat + n_pad * ld, s.matStride, h->scratchZ, n_pad, n_pad))) return rc;
+      // the derivative covariance for the on-the-fly dK~/dlog l (same data sets, same length scales)
+      if ((rc = upload_dlogl_kparams(h, st, nb, kernel_id, ell.data(), ds.data()))) return rc;
       double* part = h->gPart;                   // [nb][n_pad][4], then [nb][4]
       hipLaunchKernelGGL(grad_reduce_cov_kernel, dim3((unsigned)((n + GR_ROWS - 1) / GR_ROWS), (unsigned)nb), dim3(256), 0, st, (const double*)h->gK, n_pad * n_pad, ld,
                          (const double*)h->scratchZ, n_pad, (const double*)h->bX, n_pad * dp, (int)dp, (int)d, (int)n, (const KParams*)h->gKps, part, 4 * n_pad);
@@ -1760,12 +1719,8 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
 static int loo_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD,
                       const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, int G) {
   const long ld = n_pad;
-  const int T = (int)(n_pad / NB);
   int rc;
-  {
-    ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
-    if ((rc = trtri_levels<double>(h, st, Lm, ld, dinvp, h->gU, h->gK, ld, T, T, nb, sL, sD, n_pad * n_pad))) return rc;
-  }
+  if ((rc = inv_factor(h, st, nb, Lm, sL, dinvp, sD, n_pad))) return rc;
   {
     ProfScope ps(h, st, SIGP_KC_MLII, nb * 2.0 * n * n, nb * 4.0 * n * n);
     hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4), (unsigned)nb), dim3(256), 0, st, (const double*)h->gU, ld, (int)n, Lm + n_pad * ld, y, q, mode,
@@ -1788,15 +1743,10 @@ int sigp_loo(sigp_handle* h, int sigma_mode, double* mean, double* var, double* 
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad;
   int rc;
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad + 4))) return rc;
-  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~ (host copy of the fit's epilogue: s.res may have moved on)
-  HIPCHK(h, hipMemcpyAsync(tail + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
-  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1))) return rc;
-  HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(score, tail, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((rc = scores_ensure(h, 1, n_pad))) return rc;
+  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
+  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, h->gPart + 4 * n_pad + 2, 0, sigma_mode, 1))) return rc;
+  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
   return sync_slot(h, s);
 }
 
@@ -1811,43 +1761,24 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
   if ((mean == nullptr) != (var == nullptr)) return fail(h, SIGP_BAD_ARG, "loo_batch: mean and var come together (both NULL: scores only)");
   if (mean && nstride < h->b_n) return fail(h, SIGP_BAD_ARG, "loo_batch: mean / var [count][nstride >= %ld] required", h->b_n);
   if (h->b_n < 2) return fail(h, SIGP_BAD_ARG, "loo_batch: leave-one-out needs n >= 2 training points");
-  for (int64_t i = 0; i < count; ++i)
-    if (!(ell[i] > 0) || !std::isfinite(ell[i]) || !(sn_tilde[i] >= 0) || !std::isfinite(sn_tilde[i])) return fail(h, SIGP_BAD_ARG, "loo_batch: finite ell > 0 and sn_tilde >= 0 required");
+  int rc;
+  if ((rc = batch_check_params(h, "loo_batch", count, ell, sn_tilde))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad;
+  const long n = h->b_n, n_pad = h->b_npad;
   const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
-  const double inf = std::numeric_limits<double>::infinity(), qnan = std::nan("");
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
-  int rc;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4)))) return rc;
+  if ((rc = scores_ensure(h, G, n_pad))) return rc;
   std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
-    for (int b = 0; b < nb; ++b) s.kps_host[b] = make_kparams(kernel_id, ell[g0 + b], sn_tilde[g0 + b], (int)((first + g0 + b) % h->b_count));
-    if ((rc = upload_kparams(h, s, nb))) return rc;
-    if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
-    if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
-    if ((rc = epilogue_slot(h, s, nb, n, n_pad, 0))) return rc;
-    // y of member b is data set kps[b].ds = (first + g0 + b) % batch (the parameters uploaded above stay put until the next group's)
+    if ((rc = batch_group_fit(h, s, nb, kernel_id, ell + g0, sn_tilde + g0, first + g0))) return rc;
     if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G))) return rc;
-    if (mean) HIPCHK(h, hipMemcpy2DAsync(mv.data(), (size_t)2 * n_pad * sizeof(double), h->gPart, (size_t)4 * n_pad * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(sc.data(), h->gPart + (long)G * 4 * n_pad, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = batch_scores_fetch(h, st, nb, G, n_pad, mean ? mv.data() : nullptr, sc.data()))) return rc;
     if ((rc = sync_slot(h, s))) return rc;
-    for (int b = 0; b < nb; ++b) {
-      const long i = g0 + b;
-      const bool ok = s.info_host[b] == 0;
-      score[2 * i] = ok ? sc[(size_t)2 * b] : inf;
-      score[2 * i + 1] = ok ? sc[(size_t)2 * b + 1] : inf;
-      if (!mean) continue;
-      for (long j = 0; j < n; ++j) {
-        mean[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + j] : qnan;
-        var[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + n_pad + j] : qnan;
-      }
-    }
+    for (int b = 0; b < nb; ++b)
+      batch_scores_scatter(g0 + b, s.info_host[b] == 0, &sc[(size_t)2 * b], mean ? &mv[(size_t)b * 2 * n_pad] : nullptr, n, n_pad, mean, var, nstride, score);
   }
   h->built = h->factored = h->fitted = false;
   return SIGP_OK;

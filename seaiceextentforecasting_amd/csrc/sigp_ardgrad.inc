@@ -4,6 +4,8 @@
 // No covariance function and no existing kernel changes; a handle that never sets scales runs the launches it ran before.
 // Out of scope: the lockstep-batch entries (their resident data is staged by sigp_batch_upload and stays isotropic), the one-workgroup
 // kernel (sigp_small_*), the fp32 engine, sharded fits.  ARD gradients of the leave-one-out / leave-block-out scores: sigp_looard.inc, sigp_cvard.inc.
+// Included inside extern "C" of sigp.hip, after sigp_scores.inc (the shared steps: sigp_nlml_grad_ard is ard_check_engine, ard_theta_fit,
+// inv_factor, kinv_lower, alpha_from_U, ard_tile_pass<ARD_W_NLML> and its own finish kernel) and sigp_blockcv.inc.
 
 // X, Xs <- raw / l (or the raw values back); the fit is void afterwards
 static int ard_restage(sigp_handle* h, bool scaled) {
@@ -57,33 +59,24 @@ int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d) {
 
 int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad) {
   if (!h || !theta || !nlml) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: bad argument");
-  if (h->n == 0) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: call set_train first");
-  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: fp64 engine only");
-  if (kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: RBF / MATERN52 only");
+  int rc;
+  if ((rc = ard_check_engine(h, "nlml_grad_ard", kernel_id))) return rc;
   if (grad_mode != 0 && grad_mode != 2) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: grad_mode 0 (value) or 2 (exact gradient)");
   if (grad_mode != 0 && !grad) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: grad buffer required");
-  if (ntheta != h->d + 1) return fail(h, SIGP_BAD_ARG, "nlml_grad_ard: theta = (log l_1 .. log l_d, log sn~): %ld entries required (got %lld)", h->d + 1, (long long)ntheta);
-  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ld = n_pad;
-  const double inf = std::numeric_limits<double>::infinity();
-  auto all_inf = [&]() -> int { *nlml = inf; if (grad) for (long k = 0; k <= d; ++k) grad[k] = inf; return SIGP_NOT_SPD; };
-  std::vector<double> ell((size_t)d);
-  for (long k = 0; k < d; ++k) ell[(size_t)k] = std::exp(theta[k]);
-  const double snt = std::exp(theta[d]);
-  for (long k = 0; k < d; ++k)
-    if (!std::isfinite(ell[(size_t)k]) || !(ell[(size_t)k] > 0)) return all_inf();
-  if (!std::isfinite(snt)) return all_inf();
-  int rc;
-  if ((rc = sigp_set_length_scales(h, ell.data(), d))) return rc;
-  double out[4];
-  rc = sigp_fit_predict(h, kernel_id, 1.0, snt, nullptr, 0, out, nullptr, nullptr);
-  if (rc == SIGP_NOT_SPD) return all_inf();
+  if ((rc = ard_check_theta(h, "nlml_grad_ard", ntheta))) return rc;
+  double snt, out[4];
+  rc = ard_theta_fit(h, kernel_id, theta, &snt, out);
+  if (rc == SIGP_NOT_SPD) {
+    *nlml = std::numeric_limits<double>::infinity();
+    if (grad) for (long k = 0; k <= h->d; ++k) grad[k] = *nlml;
+  }
   if (rc) return rc;
   *nlml = out[1];
   if (grad_mode == 0) return SIGP_OK;
 
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
-  const int T = (int)(n_pad / NB);
+  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ld = n_pad;
   const long ntiles = kbuild_tiles(n_pad);
   if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
   if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
@@ -91,33 +84,15 @@ int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64
   if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)RIDE * n_pad))) return rc;
   if ((rc = ensure(h, &h->ardXc, &h->cap_ardXc, n_pad * dp))) return rc;
   // U = L~^-T, K~^-1 = U U^T (lower 128-tiles in gK), A~ = U z: the route of sigp_nlml_grad
-  {
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * n_pad / 3, 0.0);
-    if ((rc = trtri_levels<double>(h, st, s.mat, ld, s.dinv, h->gU, h->gK, ld, T, T))) return rc;
-  }
-  {
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * n_pad / 3, 0.0);
-    GemmArgs g{};
-    g.A = h->gU; g.lda = ld; g.B = h->gU; g.ldb = ld; g.C = h->gK; g.ldc = ld; g.K = (int)n_pad;
-    g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 1; g.ktri = 1;
-    if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
-  }
-  hipLaunchKernelGGL(rowdot_kernel<double>, dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, st, (const double*)h->gU, ld, (int)n_pad, (int)n_pad, 2,
-                     (const double*)(s.mat + n_pad * ld), ld, h->scratchZ, ld, 1, 0);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = inv_factor(h, st, 1, s.mat, 0, s.dinv, 0, n_pad))) return rc;
+  if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
+  if ((rc = alpha_from_U(h, st, 1, s.mat + n_pad * ld, 0, h->scratchZ, 0, n_pad))) return rc;
   // the one pass: every tile's share of all d components, then the fixed-order sums (s.res[0] = y^T A~ of the fit just made)
   double* partial = h->gPart;
   double* gdev = h->gPart + ntiles * dp;
   {
     ProfScope ps(h, st, SIGP_KC_MLII, (double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 30), 4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp));
-    HIPCHK(h, hipMemsetAsync(h->ardXc, 0, (size_t)n_pad * dp * sizeof(double), st));
-    hipLaunchKernelGGL(ard_center_kernel, dim3((unsigned)d), dim3(256), 0, st, (const double*)h->X, (int)dp, (int)n, h->ardXc);
-    if (d <= 8)
-      hipLaunchKernelGGL(ard_grad_partial_kernel<8>, dim3((unsigned)ntiles), dim3(256), 0, st, (const double*)h->X, (const double*)h->ardXc, (int)dp, (int)d, (int)n,
-                         kernel_id == SIGP_KERNEL_RBF ? KID_RBF : KID_MATERN52, (const double*)h->gK, ld, (const double*)h->scratchZ, (const double*)s.res, partial);
-    else
-      hipLaunchKernelGGL(ard_grad_partial_kernel<32>, dim3((unsigned)ntiles), dim3(256), 0, st, (const double*)h->X, (const double*)h->ardXc, (int)dp, (int)d, (int)n,
-                         kernel_id == SIGP_KERNEL_RBF ? KID_RBF : KID_MATERN52, (const double*)h->gK, ld, (const double*)h->scratchZ, (const double*)s.res, partial);
+    if ((rc = ard_tile_pass<ARD_W_NLML>(h, st, kernel_id, h->gK, ld, h->scratchZ, s.res, nullptr, nullptr, partial))) return rc;
     hipLaunchKernelGGL(ard_grad_finish_kernel, dim3((unsigned)(d + 1)), dim3(256), 0, st, (const double*)partial, ntiles, (int)dp, (int)d, (int)n, (const double*)h->gK, ld,
                        (const double*)h->scratchZ, (const double*)s.res, snt, gdev);
     HIPCHK(h, hipGetLastError());

@@ -1,7 +1,7 @@
 // sigp_cv, sigp_cv_batch: leave-block-out cross-validation (K-fold / h-block / hv-block folds of consecutive rows) from one factorisation.
-// Included inside extern "C" of sigp.hip.  Kernels and the closed form: blockcv.hpp.
+// Included inside extern "C" of sigp.hip, after sigp_scores.inc (the shared steps) and sigp_loograd.inc.  Kernels and the closed form: blockcv.hpp.
 //
-//   U = L~^-T                      trtri_levels, as sigp_loo (n^3/3)
+//   U = L~^-T                      inv_factor, as sigp_loo (n^3/3)
 //   per fold f, window S_f:        P_SS = U_S U_S^T  (2 |S|^2 (n - min S) flops, split over K slices), a_S = U_S z;
 //                                  P_SS = M M^T and X = M^-1 by the factorisation's own diagonal-block kernel; the closing solves
 //   score                          loo_sum_kernel over the n terms
@@ -39,7 +39,6 @@ static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad,
                      const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, int G, int block, int gap,
                      const CvAdjoint* adj = nullptr) {
   const long ld = n_pad;
-  const int T = (int)(n_pad / NB);
   const long F = (n + block - 1) / block;
   const int wmax = (int)std::min<long>(n, (long)block + 2L * gap), wp = (int)round_up(wmax, 16);
   const long FP = std::max<long>(1, std::min<long>(F, CV_PASS_BLOCKS / nb)), blocks = FP * nb;
@@ -55,10 +54,7 @@ static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad,
   double* Xb = Pb + blocks * CV_MAXW * CV_MAXW;
   double* av = h->cvVec;
   int* info = (int*)(av + blocks * CV_MAXW);
-  {
-    ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
-    if ((rc = trtri_levels<double>(h, st, Lm, ld, dinvp, h->gU, h->gK, ld, T, T, nb, sL, sD, n_pad * n_pad))) return rc;
-  }
+  if ((rc = inv_factor(h, st, nb, Lm, sL, dinvp, sD, n_pad))) return rc;
   static AttrOnce d_attr;
   HIPCHK(h, d_attr.set(h->device, (const void*)potrf_diag_kernel<double>, DIAG_LDS_BYTES));
   const double* z = Lm + n_pad * ld;
@@ -130,15 +126,10 @@ int sigp_cv(sigp_handle* h, int64_t block, int64_t gap, int sigma_mode, double* 
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad;
   int rc;
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad + 4))) return rc;
-  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~ (host copy of the fit's epilogue, as sigp_loo)
-  HIPCHK(h, hipMemcpyAsync(tail + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
-  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1, (int)block, (int)gap))) return rc;
-  HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(score, tail, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((rc = scores_ensure(h, 1, n_pad))) return rc;
+  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
+  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, h->gPart + 4 * n_pad + 2, 0, sigma_mode, 1, (int)block, (int)gap))) return rc;
+  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
   return sync_slot(h, s);
 }
 
@@ -153,42 +144,26 @@ int sigp_cv_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, c
   if (h->b_n < 2) return fail(h, SIGP_BAD_ARG, "cv_batch: cross-validation needs n >= 2 training points");
   if (const char* why = cv_check_folds(h->b_n, block, gap, SIGP_CV_MAX_WINDOW))
     return fail(h, SIGP_BAD_ARG, "cv_batch: %s (block = %lld, gap = %lld, n = %ld, SIGP_CV_MAX_WINDOW = %d)", why, (long long)block, (long long)gap, h->b_n, SIGP_CV_MAX_WINDOW);
-  for (int64_t i = 0; i < count; ++i)
-    if (!(ell[i] > 0) || !std::isfinite(ell[i]) || !(sn_tilde[i] >= 0) || !std::isfinite(sn_tilde[i])) return fail(h, SIGP_BAD_ARG, "cv_batch: finite ell > 0 and sn_tilde >= 0 required");
+  int rc;
+  if ((rc = batch_check_params(h, "cv_batch", count, ell, sn_tilde))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad;
+  const long n = h->b_n, n_pad = h->b_npad;
   const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
-  const double inf = std::numeric_limits<double>::infinity(), qnan = std::nan("");
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
-  int rc;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4)))) return rc;
+  if ((rc = scores_ensure(h, G, n_pad))) return rc;
   std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
-    for (int b = 0; b < nb; ++b) s.kps_host[b] = make_kparams(kernel_id, ell[g0 + b], sn_tilde[g0 + b], (int)((first + g0 + b) % h->b_count));
-    if ((rc = upload_kparams(h, s, nb))) return rc;
-    if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
-    if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
-    if ((rc = epilogue_slot(h, s, nb, n, n_pad, 0))) return rc;
+    if ((rc = batch_group_fit(h, s, nb, kernel_id, ell + g0, sn_tilde + g0, first + g0))) return rc;
     if ((rc = cv_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G, (int)block, (int)gap))) return rc;
-    if (mean) HIPCHK(h, hipMemcpy2DAsync(mv.data(), (size_t)2 * n_pad * sizeof(double), h->gPart, (size_t)4 * n_pad * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(sc.data(), h->gPart + (long)G * 4 * n_pad, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = batch_scores_fetch(h, st, nb, G, n_pad, mean ? mv.data() : nullptr, sc.data()))) return rc;
     if ((rc = sync_slot(h, s))) return rc;
     for (int b = 0; b < nb; ++b) {
-      const long i = g0 + b;
       // a member whose K~ is not SPD, or one of whose P_SS failed its pivot test (+inf terms in its sums): +inf scores, NaN rows
       const bool ok = s.info_host[b] == 0 && std::isfinite(sc[(size_t)2 * b]) && std::isfinite(sc[(size_t)2 * b + 1]);
-      score[2 * i] = ok ? sc[(size_t)2 * b] : inf;
-      score[2 * i + 1] = ok ? sc[(size_t)2 * b + 1] : inf;
-      if (!mean) continue;
-      for (long j = 0; j < n; ++j) {
-        mean[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + j] : qnan;
-        var[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + n_pad + j] : qnan;
-      }
+      batch_scores_scatter(g0 + b, ok, &sc[(size_t)2 * b], mean ? &mv[(size_t)b * 2 * n_pad] : nullptr, n, n_pad, mean, var, nstride, score);
     }
   }
   h->built = h->factored = h->fitted = false;

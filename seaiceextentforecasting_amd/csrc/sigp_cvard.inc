@@ -1,16 +1,17 @@
 // sigp_cv_grad_ard: the leave-block-out scores AND the exact derivatives of one of them with respect to (log l_1 .. log l_d, log sn~)
-// (cvard.hpp has the formulae and the kernels).  Included inside extern "C" of sigp.hip, after sigp_looard.inc.
+// (cvard.hpp has the formulae and the kernels).  Included inside extern "C" of sigp.hip, after sigp_scores.inc (the shared steps),
+// sigp_blockcv.inc and sigp_looard.inc.
 //
-// The scales are set and the fit is made as sigp_loo_grad_ard makes it (ell = 1, sigp_fit_predict's own launches); then cv_launch (U = L~^-T
+// The scales are set and the fit is made as sigp_loo_grad_ard makes it (ard_theta_fit: ell = 1, sigp_fit_predict's own launches); then cv_launch (U = L~^-T
 // in gU, the scores: the same launches as sigp_cv, so the same bits) with, per pass of at most 1024 folds:
 //   beta_f, B_f, eps_f   cv_adj_fold_kernel, right after the closing solves (the fold blocks are overwritten by the next pass)
 //   beta, B              cv_adj_gather_kernel: the folds' terms added in ascending fold order into beta [n_pad] and the band store [n_pad][384]
 // and on top of it:
-//   P = U U^T            lower 128-tiles into gK (n^3/3), mirrored to the full symmetric matrix;  a = U z       (sigp_loo_grad_ard's launches)
+//   P = U U^T            kinv_lower: lower 128-tiles into gK (n^3/3);  a = U z (alpha_from_U);  mirror_P         (sigp_loo_grad_ard's launches)
 //   eps, v = P beta      cv_adj_eps_kernel, cv_adj_v_kernel (one pass over the rows of P, which also zeroes its padding)
 //   P B into gD          cv_band_product_kernel: the 128-tile loop over the three block columns of B's band (6 x 128 n_pad^2 flops)
-//   M = (P B) P^T        lower 128-tiles into gU, which is dead by then: syrk128_kernel's SET form (n^3 flops for any d)
-//   the ARD pass         ard_grad_partial_kernel<., ARD_W_LOO> over M, v, a, eps, then loo_ard_finish_kernel -- unchanged
+//   M = (P B) P^T        lower 128-tiles into gU, which is dead by then: syrk_set (n^3 flops for any d)
+//   the ARD pass         loo_ard_pass, as sigp_loo_grad_ard
 // Memory: sigp_loo_grad's single-fit buffers (gU, gK, gD, gV, gPart), ardXc, sigp_cv's workspaces and cvAdj: the band store, B_f / beta_f of one
 // pass and eps_f.  Profile class: SIGP_KC_MLII (on top of cv_launch's entries: two per pass, then U U^T, the n^2 passes, the banded
 // product, the product M, the ARD pass: one entry each).
@@ -22,51 +23,26 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
   if ((mean == nullptr) != (var == nullptr)) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: mean and var come together (both NULL: scores and gradient only)");
   if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
   if (criterion != SIGP_LOO_NLPD && criterion != SIGP_LOO_SSE) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: criterion must be SIGP_LOO_NLPD or SIGP_LOO_SSE");
-  if (h->n == 0) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: call set_train first");
-  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: fp64 engine only");
-  if (kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: RBF / MATERN52 only");
+  int rc;
+  if ((rc = ard_check_engine(h, "cv_grad_ard", kernel_id))) return rc;
   if (h->n < 2) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: cross-validation needs n >= 2 training points");
-  if (ntheta != h->d + 1) return fail(h, SIGP_BAD_ARG, "cv_grad_ard: theta = (log l_1 .. log l_d, log sn~): %ld entries required (got %lld)", h->d + 1, (long long)ntheta);
+  if ((rc = ard_check_theta(h, "cv_grad_ard", ntheta))) return rc;
   if (const char* why = cv_check_folds(h->n, block, gap, SIGP_CV_MAX_WINDOW))
     return fail(h, SIGP_BAD_ARG, "cv_grad_ard: %s (block = %lld, gap = %lld, n = %ld, SIGP_CV_MAX_WINDOW = %d)", why, (long long)block, (long long)gap, h->n, SIGP_CV_MAX_WINDOW);
-  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ld = n_pad;
-  const double inf = std::numeric_limits<double>::infinity(), qnan = std::nan("");
-  auto all_inf = [&]() -> int {
-    score[0] = score[1] = inf;
-    if (grad) for (long k = 0; k <= d; ++k) grad[k] = inf;
-    if (mean) for (long i = 0; i < n; ++i) mean[i] = var[i] = qnan;
-    return SIGP_NOT_SPD;
-  };
-  std::vector<double> ell((size_t)d);
-  for (long k = 0; k < d; ++k) ell[(size_t)k] = std::exp(theta[k]);
-  const double snt = std::exp(theta[d]);
-  for (long k = 0; k < d; ++k)
-    if (!std::isfinite(ell[(size_t)k]) || !(ell[(size_t)k] > 0)) return all_inf();
-  if (!std::isfinite(snt)) return all_inf();
-  int rc;
-  if ((rc = sigp_set_length_scales(h, ell.data(), d))) return rc;
-  double out[4];
-  rc = sigp_fit_predict(h, kernel_id, 1.0, snt, nullptr, 0, out, nullptr, nullptr);
-  if (rc == SIGP_NOT_SPD) return all_inf();
+  double snt, out[4];
+  rc = ard_theta_fit(h, kernel_id, theta, &snt, out);
+  if (rc == SIGP_NOT_SPD) return ard_all_inf(h, score, grad, mean, var);
   if (rc) return rc;
 
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
+  const long n = h->n, n_pad = h->n_pad, ld = n_pad;
   const int T = (int)(n_pad / NB);
-  const long ntiles = kbuild_tiles(n_pad), sM = n_pad * n_pad;
   const long F = (n + block - 1) / block, FP = std::min<long>(F, CV_PASS_BLOCKS);
   const long wp = round_up(std::min<long>(n, block + 2 * gap), 16);
-  // every buffer before the first launch: growing one of them later would drop what the earlier launches left in it
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, sM))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, sM))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad + 4 + (grad ? ntiles * dp + dp + 1 : 0)))) return rc;
+  if ((rc = ard_scores_ensure(h, grad != nullptr))) return rc;
   CvAdjoint adj{};
-  if (grad) {
-    if ((rc = ensure(h, &h->gD, &h->cap_gD, sM))) return rc;
-    if ((rc = ensure(h, &h->gV, &h->cap_gV, LooArdVecs::size(n_pad)))) return rc;
-    if ((rc = ensure(h, &h->ardXc, &h->cap_ardXc, n_pad * dp))) return rc;
-    if ((rc = ensure(h, &h->cvAdj, &h->cap_cvAdj, n_pad * CVA_BAND + FP * (wp * wp + wp) + F))) return rc;
-  }
+  if (grad && (rc = ensure(h, &h->cvAdj, &h->cap_cvAdj, n_pad * CVA_BAND + FP * (wp * wp + wp) + F))) return rc;   // (also before the first launch)
   LooArdVecs w{h->gV, n_pad};
   if (grad) {
     adj.crit = criterion;
@@ -78,35 +54,22 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
     HIPCHK(h, hipMemsetAsync(adj.band, 0, (size_t)n_pad * CVA_BAND * sizeof(double), st));
     HIPCHK(h, hipMemsetAsync(adj.beta, 0, (size_t)n_pad * sizeof(double), st));
   }
-  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~, as sigp_cv
-  HIPCHK(h, hipMemcpyAsync(tail + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
+  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~, as sigp_cv; then the tile pass's partials and the gradient
+  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
   if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1, (int)block, (int)gap, grad ? &adj : nullptr))) return rc;
-  if (mean) {
-    HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(h, hipMemcpyAsync(score, tail, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
   // a fold whose P_SS failed its pivot test left +inf in both sums
   auto finish = [&]() -> int {
     if ((rc = sync_slot(h, s))) return rc;
-    return std::isfinite(score[0]) && std::isfinite(score[1]) ? SIGP_OK : all_inf();
+    return std::isfinite(score[0]) && std::isfinite(score[1]) ? SIGP_OK : ard_all_inf(h, score, grad, mean, var);
   };
   if (!grad) return finish();
 
-  {   // P = U U^T, lower tiles
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * n_pad / 3, 0.0);
-    GemmArgs g{};
-    g.A = h->gU; g.lda = ld; g.B = h->gU; g.ldb = ld; g.C = h->gK; g.ldc = ld; g.K = (int)n_pad;
-    g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 1; g.ktri = 1;
-    if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
-  }
+  if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
   {   // a = U z;  P -> full;  eps;  v = P beta (and the padding of P zeroed)
     ProfScope ps(h, st, SIGP_KC_MLII, 4.0 * n_pad * n_pad, 28.0 * n_pad * n_pad);
-    hipLaunchKernelGGL(rowdot_kernel<double>, dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, st, (const double*)h->gU, ld, (int)n_pad, (int)n_pad, 2,
-                       (const double*)(s.mat + n_pad * ld), ld, w.a(), ld, 1, 0);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(loo_grad_mirror_kernel, dim3((unsigned)(n_pad / 32), (unsigned)(n_pad / 32), 1u), dim3(256), 0, st, h->gK, ld, sM);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = alpha_from_U(h, st, 1, s.mat + n_pad * ld, 0, w.a(), 0, n_pad))) return rc;
+    if ((rc = mirror_P(h, st, 1, n_pad))) return rc;
     hipLaunchKernelGGL(cv_adj_eps_kernel, dim3(1), dim3(256), 0, st, (const double*)adj.epsf, (int)F, w.eps());
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(cv_adj_v_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, st, h->gK, ld, (int)n, (int)n_pad, (const double*)w.beta(), w.v());
@@ -121,27 +84,8 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
   }
   {   // M = (P B) P^T: tile (bi, bj), bi >= bj, = rows bi of P B against rows bj of P (= its columns), the whole K span
     ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * (n_pad + NB), 0.0);
-    GemmArgs g{};
-    g.A = h->gD; g.lda = ld; g.B = h->gK; g.ldb = ld; g.C = h->gU; g.ldc = ld; g.K = (int)n_pad;
-    g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 1; g.ktri = 0;
-    if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
+    if ((rc = syrk_set(h, st, 1, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
   }
-  double* partial = tail + 4;
-  double* gdev = partial + ntiles * dp;
-  {   // the one pass: every tile's share of all d components, then the fixed-order sums
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 36), 4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp));
-    const int kid = kernel_id == SIGP_KERNEL_RBF ? KID_RBF : KID_MATERN52;
-    HIPCHK(h, hipMemsetAsync(h->ardXc, 0, (size_t)n_pad * dp * sizeof(double), st));
-    hipLaunchKernelGGL(ard_center_kernel, dim3((unsigned)d), dim3(256), 0, st, (const double*)h->X, (int)dp, (int)n, h->ardXc);
-    if (d <= 8)
-      hipLaunchKernelGGL((ard_grad_partial_kernel<8, ARD_W_LOO>), dim3((unsigned)ntiles), dim3(256), 0, st, (const double*)h->X, (const double*)h->ardXc, (int)dp, (int)d, (int)n,
-                         kid, (const double*)h->gU, ld, (const double*)w.a(), (const double*)nullptr, partial, (const double*)w.v(), (const double*)w.eps());
-    else
-      hipLaunchKernelGGL((ard_grad_partial_kernel<32, ARD_W_LOO>), dim3((unsigned)ntiles), dim3(256), 0, st, (const double*)h->X, (const double*)h->ardXc, (int)dp, (int)d, (int)n,
-                         kid, (const double*)h->gU, ld, (const double*)w.a(), (const double*)nullptr, partial, (const double*)w.v(), (const double*)w.eps());
-    hipLaunchKernelGGL(loo_ard_finish_kernel, dim3((unsigned)(d + 1)), dim3(256), 0, st, (const double*)partial, ntiles, (int)dp, (int)d, (int)n, (const double*)h->gU, ld, w, snt, gdev);
-    HIPCHK(h, hipGetLastError());
-  }
-  HIPCHK(h, hipMemcpyAsync(grad, gdev, (size_t)(d + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((rc = loo_ard_pass(h, st, kernel_id, w, snt, grad))) return rc;
   return finish();
 }

@@ -1,11 +1,11 @@
 // sigp_loo_grad / sigp_loo_grad_batch: the leave-one-out scores AND their exact derivatives with respect to (log l, log sn~) (loograd.hpp has
-// the formulae and the kernels).  Included inside extern "C" of sigp.hip, after loo_launch.
+// the formulae and the kernels).  Included inside extern "C" of sigp.hip, after sigp_scores.inc (the shared steps) and loo_launch.
 //
 // On top of loo_launch (U = L~^-T in gU, the scores: the same launches as sigp_loo, so the same bits), per lockstep member:
-//   P = U U^T        lower 128-tiles into gK (as sigp_nlml_grad, n^3/3), mirrored to the full symmetric matrix (loo_grad_mirror_kernel)
-//   a = U z          rowdot_kernel over U's upper triangle, as sigp_nlml_grad
+//   P = U U^T        kinv_lower: lower 128-tiles into gK (as sigp_nlml_grad, n^3/3);  mirror_P: to the full symmetric matrix
+//   a = U z          alpha_from_U, as sigp_nlml_grad
 //   t = D a, D -> D' one pass over gD (loo_grad_prep_kernel)
-//   W' = D' P        into gU, which is dead by then: syrk128_kernel's SET form on the full tile space with ktri = 1 (n^3 flops; the walk
+//   W' = D' P        into gU, which is dead by then: syrk_set on the full tile space with ktri = 1 (n^3 flops; the walk
 //                    issues the row blocks with the longest K spans first)
 //   b, P a, sum P^2  one pass over the rows of P (loo_grad_rows_kernel);  c = 2 colsum(W' o P) by row chunks (loo_grad_cols_kernel)
 //   the chain rule per point and four fixed-order sums (loo_grad_point_kernel)
@@ -15,29 +15,19 @@
 // Out of scope: gradients in sigp_small_run_loo (the one-workgroup LDS kernel), sharded fits, the fp32 engine.  Gradients with respect to
 // per-feature length scales: sigp_loo_grad_ard (sigp_looard.inc).
 
+// every buffer before the first launch: growing one of them later would drop what the earlier launches left in it
 static int loo_grad_ensure(sigp_handle* h, int G, long n_pad) {
   int rc;
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gD, &h->cap_gD, (long)G * n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4)))) return rc;
-  return ensure(h, &h->gV, &h->cap_gV, (long)G * LooGradVecs::size(n_pad));
+  if ((rc = scores_ensure(h, G, n_pad))) return rc;
+  return scores_grad_ensure(h, G, n_pad, LooGradVecs::size(n_pad));
 }
 
 // dK~/dlog l of RBF / Matern members into gD (full symmetric, zero on the padding): member b has data set ds[b] of X (stride strideX) and
 // length scale ell[b]
 static int loo_grad_build_dlogl(sigp_handle* h, hipStream_t st, int nb, int kernel_id, const double* ell, const int* ds, const double* X, long strideX,
                                 long n, long d, long dp, long n_pad) {
-  std::vector<KParams> dkp((size_t)nb);
-  for (int b = 0; b < nb; ++b) dkp[(size_t)b] = make_kparams(kernel_id == SIGP_KERNEL_RBF ? KID_RBF_DLOGL : KID_MATERN52_DLOGL, ell[b], 0.0, ds[b]);
-  if (h->cap_gKps < nb) {
-    HIPCHK(h, hipDeviceSynchronize());
-    if (h->gKps) HIPCHK(h, hipFree(h->gKps));
-    h->gKps = nullptr; h->cap_gKps = 0;
-    HIPCHK(h, hipMalloc((void**)&h->gKps, (size_t)nb * sizeof(KParams)));
-    h->cap_gKps = nb;
-  }
-  HIPCHK(h, hipMemcpyAsync(h->gKps, dkp.data(), (size_t)nb * sizeof(KParams), hipMemcpyHostToDevice, st));   // pageable: staged before the call returns
+  int rc;
+  if ((rc = upload_dlogl_kparams(h, st, nb, kernel_id, ell, ds))) return rc;
   ProfScope ps(h, st, SIGP_KC_KBUILD, nb * ((double)n * n * (3.0 * d + 20)), nb * 8.0 * n_pad * n_pad);
   dim3 grid((unsigned)(n_pad / KB_TN), (unsigned)(n_pad / KB_TM), (unsigned)nb);
   launch_kbuild<double>(h, grid, st, X, strideX, (int)dp, (int)d, (int)n, h->gD, n_pad * n_pad, n_pad, h->gKps, 1);
@@ -51,31 +41,17 @@ static int loo_grad_launch(sigp_handle* h, hipStream_t st, int nb, long n, long 
   const long ld = n_pad, sM = n_pad * n_pad;
   const int T = (int)(n_pad / NB), tri = h->opt_loo_grad_tri;
   int rc;
-  {   // P = U U^T, lower tiles
-    ProfScope ps(h, st, SIGP_KC_MLII, nb * (double)n_pad * n_pad * n_pad / 3, 0.0);
-    GemmArgs g{};
-    g.A = h->gU; g.lda = ld; g.B = h->gU; g.ldb = ld; g.C = h->gK; g.ldc = ld; g.K = (int)n_pad;
-    g.batch = nb; g.sA = g.sB = g.sC = sM;
-    g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 1; g.ktri = 1;
-    if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
-  }
+  if ((rc = kinv_lower(h, st, nb, n_pad))) return rc;
   {   // a = U z;  P -> full;  t = D a and D -> D'
     ProfScope ps(h, st, SIGP_KC_MLII, nb * 3.0 * n_pad * n_pad, nb * 36.0 * n_pad * n_pad);
-    hipLaunchKernelGGL(rowdot_kernel<double>, dim3((unsigned)((n_pad + 3) / 4), (unsigned)nb), dim3(256), 0, st, (const double*)h->gU, ld, (int)n_pad, (int)n_pad, 2,
-                       z, ld, v.base, ld, 1, 0, (const double*)nullptr, 0, 0, sM, sZ, v.stride);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(loo_grad_mirror_kernel, dim3((unsigned)(n_pad / 32), (unsigned)(n_pad / 32), (unsigned)nb), dim3(256), 0, st, h->gK, ld, sM);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = alpha_from_U(h, st, nb, z, sZ, v.base, v.stride, n_pad))) return rc;
+    if ((rc = mirror_P(h, st, nb, n_pad))) return rc;
     hipLaunchKernelGGL(loo_grad_prep_kernel, dim3((unsigned)(n_pad / 4), (unsigned)nb), dim3(256), 0, st, h->gD, ld, sM, (int)n, (int)n_pad, tri, v);
     HIPCHK(h, hipGetLastError());
   }
   {   // W' = D' P: tile (bi, bj) = rows bi of D' against rows bj of P (= its columns), K from the row block on
     ProfScope ps(h, st, SIGP_KC_MLII, nb * (tri ? 1.0 : 2.0) * n_pad * n_pad * n_pad, 0.0);
-    GemmArgs g{};
-    g.A = h->gD; g.lda = ld; g.B = h->gK; g.ldb = ld; g.C = h->gU; g.ldc = ld; g.K = (int)n_pad;
-    g.batch = nb; g.sA = g.sB = g.sC = sM;
-    g.r0 = 0; g.r1 = T; g.c0 = 0; g.c1 = T; g.lower = 0; g.ktri = tri ? 1 : 0;
-    if ((rc = launch_syrk128_t<double, true>(h, st, g))) return rc;
+    if ((rc = syrk_set(h, st, nb, h->gD, h->gK, h->gU, n_pad, 0, tri ? 1 : 0))) return rc;
   }
   {
     ProfScope ps(h, st, SIGP_KC_MLII, nb * 8.0 * n * n, nb * 24.0 * n * n);
@@ -106,9 +82,9 @@ int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t 
   const long n = h->n, n_pad = h->n_pad, ld = n_pad;
   int rc;
   if ((rc = loo_grad_ensure(h, 1, n_pad))) return rc;
-  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~, as sigp_loo
-  HIPCHK(h, hipMemcpyAsync(tail + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
-  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1))) return rc;
+  const double* q = h->gPart + 4 * n_pad + 2;       // gPart's tail: score [2], then q = y^T A~, as sigp_loo
+  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
+  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, q, 0, sigma_mode, 1))) return rc;
   if (refk) {
     if ((rc = build_xsxt(h, MSigma, ldsigma, h->gD))) return rc;     // X (M Sigma~) X^T = dK~/dl
   } else {
@@ -116,13 +92,9 @@ int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t 
     if ((rc = loo_grad_build_dlogl(h, st, 1, h->kernel_id, &h->ell, &ds0, h->X, 0L, n, h->d, h->dp, n_pad))) return rc;
   }
   LooGradVecs v{h->gV, LooGradVecs::size(n_pad), n_pad, (int)(n_pad / NB)};
-  if ((rc = loo_grad_launch(h, st, 1, n, n_pad, s.mat + n_pad * ld, 0, tail + 2, 0, sigma_mode, v))) return rc;
+  if ((rc = loo_grad_launch(h, st, 1, n, n_pad, s.mat + n_pad * ld, 0, q, 0, sigma_mode, v))) return rc;
   double g4[4];
-  if (mean) {
-    HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(h, hipMemcpyAsync(score, tail, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
   HIPCHK(h, hipMemcpyAsync(g4, h->gV + (5 + n_pad / NB) * n_pad, sizeof g4, hipMemcpyDeviceToHost, st));
   if ((rc = sync_slot(h, s))) return rc;
   const double scale1 = refk ? h->ell : 1.0;        // dK~/dlog l = l X (M Sigma~) X^T
@@ -140,15 +112,14 @@ int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
   if ((mean == nullptr) != (var == nullptr)) return fail(h, SIGP_BAD_ARG, "loo_grad_batch: mean and var come together (both NULL: scores and gradients only)");
   if (mean && nstride < h->b_n) return fail(h, SIGP_BAD_ARG, "loo_grad_batch: mean / var [count][nstride >= %ld] required", h->b_n);
   if (h->b_n < 2) return fail(h, SIGP_BAD_ARG, "loo_grad_batch: leave-one-out needs n >= 2 training points");
-  for (int64_t i = 0; i < count; ++i)
-    if (!(ell[i] > 0) || !std::isfinite(ell[i]) || !(sn_tilde[i] >= 0) || !std::isfinite(sn_tilde[i])) return fail(h, SIGP_BAD_ARG, "loo_grad_batch: finite ell > 0 and sn_tilde >= 0 required");
+  int rc;
+  if ((rc = batch_check_params(h, "loo_grad_batch", count, ell, sn_tilde))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad, ld = n_pad;
   const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
-  const double inf = std::numeric_limits<double>::infinity(), qnan = std::nan("");
+  const double inf = std::numeric_limits<double>::infinity();
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
-  int rc;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
   if ((rc = loo_grad_ensure(h, G, n_pad))) return rc;
   LooGradVecs v{h->gV, LooGradVecs::size(n_pad), n_pad, (int)(n_pad / NB)};
@@ -156,35 +127,22 @@ int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
   std::vector<int> ds((size_t)G);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
-    for (int b = 0; b < nb; ++b) {
-      ds[(size_t)b] = (int)((first + g0 + b) % h->b_count);
-      s.kps_host[b] = make_kparams(kernel_id, ell[g0 + b], sn_tilde[g0 + b], ds[(size_t)b]);
-    }
-    if ((rc = upload_kparams(h, s, nb))) return rc;
-    if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
-    if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
-    if ((rc = epilogue_slot(h, s, nb, n, n_pad, 0))) return rc;
+    for (int b = 0; b < nb; ++b) ds[(size_t)b] = (int)((first + g0 + b) % h->b_count);
+    if ((rc = batch_group_fit(h, s, nb, kernel_id, ell + g0, sn_tilde + g0, first + g0))) return rc;
     if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G))) return rc;
     if ((rc = loo_grad_build_dlogl(h, st, nb, kernel_id, ell + g0, ds.data(), h->bX, n_pad * dp, n, d, dp, n_pad))) return rc;
     if ((rc = loo_grad_launch(h, st, nb, n, n_pad, s.mat + n_pad * ld, s.matStride, s.res, 512, sigma_mode, v))) return rc;
-    if (mean) HIPCHK(h, hipMemcpy2DAsync(mv.data(), (size_t)2 * n_pad * sizeof(double), h->gPart, (size_t)4 * n_pad * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(sc.data(), h->gPart + (long)G * 4 * n_pad, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = batch_scores_fetch(h, st, nb, G, n_pad, mean ? mv.data() : nullptr, sc.data()))) return rc;
     HIPCHK(h, hipMemcpy2DAsync(g4.data(), 4 * sizeof(double), h->gV + (5 + n_pad / NB) * n_pad, (size_t)v.stride * sizeof(double), 4 * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
     if ((rc = sync_slot(h, s))) return rc;
     for (int b = 0; b < nb; ++b) {
       const long i = g0 + b;
       const bool ok = s.info_host[b] == 0;
-      score[2 * i] = ok ? sc[(size_t)2 * b] : inf;
-      score[2 * i + 1] = ok ? sc[(size_t)2 * b + 1] : inf;
+      batch_scores_scatter(i, ok, &sc[(size_t)2 * b], mean ? &mv[(size_t)b * 2 * n_pad] : nullptr, n, n_pad, mean, var, nstride, score);
       grad[4 * i] = ok ? g4[(size_t)4 * b] : inf;
       grad[4 * i + 1] = ok ? sn_tilde[i] * g4[(size_t)4 * b + 1] : inf;
       grad[4 * i + 2] = ok ? g4[(size_t)4 * b + 2] : inf;
       grad[4 * i + 3] = ok ? sn_tilde[i] * g4[(size_t)4 * b + 3] : inf;
-      if (!mean) continue;
-      for (long j = 0; j < n; ++j) {
-        mean[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + j] : qnan;
-        var[i * nstride + j] = ok ? mv[(size_t)b * 2 * n_pad + n_pad + j] : qnan;
-      }
     }
   }
   h->built = h->factored = h->fitted = false;

@@ -304,8 +304,21 @@ class GPR:
         ``grad=True`` (``sigp_loo_grad_batch``) adds nlpd_grad [F, 2] and sse_grad [F, 2] with respect to (log l, log sn~)."""
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        ell, sn, F, n, score, mean, var = self._batch_score_args("loo_batch", ell, sn_tilde, group, predictions)
+        g4 = np.zeros((F, 4)) if grad else None
+        if grad:
+            self._check(self._lib.sigp_loo_grad_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                                      L.ptr(score), L.ptr(g4)), "loo_batch")
+        else:
+            self._check(self._lib.sigp_loo_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                                 L.ptr(score)), "loo_batch")
+        return self._batch_score_result(score, mean, var, g4)
+
+    def _batch_score_args(self, what, ell, sn_tilde, group, predictions):
+        """what ``loo_batch`` and ``cv_batch`` do between their own checks and the library call: (ell [F], sn [F], F, n, score [F, 2], mean, var
+        [F, n] or None), the lockstep group set"""
         if self.kernel == "netdiffusion":
-            raise ValueError("loo_batch covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(loo=...)")
+            raise ValueError("%s covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(%s=...)" % (what, what[:-6]))
         ell = L.f64(np.atleast_1d(ell), 1)
         sn = L.f64(np.atleast_1d(sn_tilde), 1)
         F = len(ell)
@@ -313,23 +326,17 @@ class GPR:
             raise ValueError("ell and sn_tilde must have the same length")
         n = getattr(self, "_batch_n", None)
         if n is None:
-            raise RuntimeError("loo_batch: stage the data sets with upload_batch() first")
+            raise RuntimeError("%s: stage the data sets with upload_batch() first" % what)
         self.set_option("group", group)
-        score = np.zeros((F, 2))
-        mean = np.zeros((F, n)) if predictions else None
-        var = np.zeros((F, n)) if predictions else None
-        if grad:
-            g4 = np.zeros((F, 4))
-            self._check(self._lib.sigp_loo_grad_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
-                                                      L.ptr(score), L.ptr(g4)), "loo_batch")
-        else:
-            self._check(self._lib.sigp_loo_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
-                                                 L.ptr(score)), "loo_batch")
+        return ell, sn, F, n, np.zeros((F, 2)), (np.zeros((F, n)) if predictions else None), (np.zeros((F, n)) if predictions else None)
+
+    def _batch_score_result(self, score, mean, var, g4=None):
+        """... and after it: the result dict (the single fit, if any, is gone)"""
         self._fitted = False
         res = dict(nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
-        if grad:
+        if g4 is not None:
             res["nlpd_grad"], res["sse_grad"] = g4[:, :2].copy(), g4[:, 2:].copy()
-        if predictions:
+        if mean is not None:
             res["mean"], res["var"] = mean, var
         return res
 
@@ -408,28 +415,11 @@ class GPR:
         """``cv`` for many (data set, l, sn~) on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern), in lockstep groups
         of ``group`` fits (``sigp_cv_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F]) and, with
         ``predictions``, mean [F, n], var [F, n]; a member whose K~ (or one of whose blocks of K~^-1) is not SPD gets +inf / NaN."""
-        n = getattr(self, "_batch_n", None)
-        block, gap = self._cv_args(block, gap, sigma_f, n=n)
-        if self.kernel == "netdiffusion":
-            raise ValueError("cv_batch covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(cv=...)")
-        ell = L.f64(np.atleast_1d(ell), 1)
-        sn = L.f64(np.atleast_1d(sn_tilde), 1)
-        F = len(ell)
-        if len(sn) != F:
-            raise ValueError("ell and sn_tilde must have the same length")
-        if n is None:
-            raise RuntimeError("cv_batch: stage the data sets with upload_batch() first")
-        self.set_option("group", group)
-        score = np.zeros((F, 2))
-        mean = np.zeros((F, n)) if predictions else None
-        var = np.zeros((F, n)) if predictions else None
+        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "_batch_n", None))
+        ell, sn, F, n, score, mean, var = self._batch_score_args("cv_batch", ell, sn_tilde, group, predictions)
         self._check(self._lib.sigp_cv_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), block, gap, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
                                             L.ptr(score)), "cv_batch")
-        self._fitted = False
-        res = dict(nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
-        if predictions:
-            res["mean"], res["var"] = mean, var
-        return res
+        return self._batch_score_result(score, mean, var)
 
     def cv_grid(self, X, y, ells, sns, block, gap=0, sigma_f="refit", group=8, M=None):
         """The leave-block-out scores on the (l, sn~) grid for one data set, shaped like ``loo_grid``: dict(nlpd, sse), each
@@ -510,8 +500,17 @@ class GPR:
         every component of the exact gradient from one pass over K~^-1); ``grad=None``: value only (second entry None).  A non-SPD K~ or an
         overflowing exp(theta) gives ``(inf, [inf] * (d + 1))``, like ``nlml``.  Afterwards the handle is fitted at exp(theta) with the scales
         set: ``predict`` / ``predict_cov`` / ``loo`` / ``cv`` work on it, and ``nlml_`` is the value returned.  RBF / Matern, fp64."""
+        r = self._ard_call("nlml_ard", theta, grad, None, False, lambda th, mean, var, score, g: self._lib.sigp_nlml_grad_ard(
+            self._h, self._kid, L.ptr(th), th.shape[0], 0 if grad is None else 2, L.ptr(score), L.ptr(g)))
+        return r["value"], (r["grad"] if r["spd"] else np.full(self.d + 1, np.inf))      # (the inf gradient even with grad=None)
+
+    def _ard_call(self, what, theta, grad, which, predictions, call):
+        """what ``nlml_ard``, ``loo_ard`` and ``cv_ard`` share, after the checks of their own: the checks they have in common, the buffers, the
+        library call -- ``call(theta, mean, var, score, g)`` returns its code and leaves the two scores (``nlml_ard``: the nlML) in ``score``,
+        of which ``which`` is the value (None: ``nlml_ard``) --, the non-SPD branch and the handle's state afterwards.  Returns dict(value, grad,
+        mean, var, nlpd, sse, spd)."""
         if not self._has_data:
-            raise RuntimeError("nlml_ard: no data staged; call fit() or set_data() first")
+            raise RuntimeError("%s: no data staged; call fit() or set_data() first" % what)
         if grad not in (None, "exact"):
             raise ValueError("grad must be None or 'exact'")
         if self.kernel == "netdiffusion" or self.dtype != "f64":
@@ -519,16 +518,21 @@ class GPR:
         theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
         if theta.shape[0] != self.d + 1:
             raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
-        val = C.c_double()
-        g = np.zeros(self.d + 1)
+        score = np.zeros(2)
+        g = np.zeros(self.d + 1) if grad is not None else None
+        mean = np.zeros(self.n) if predictions else None
+        var = np.zeros(self.n) if predictions else None
         self._fitted = False
-        rc = self._lib.sigp_nlml_grad_ard(self._h, self._kid, L.ptr(theta), theta.shape[0], 0 if grad is None else 2, C.byref(val), L.ptr(g))
-        if rc == L.NOT_SPD:
+        rc = call(theta, mean, var, score, g)
+        spd = rc != L.NOT_SPD
+        if spd:
+            self._check(rc, what)
+            self._after_ard_call(theta, float(score[0]) if which is None else None, what)
+            value = np.float64(score[0 if which is None else which])
+        else:
             self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
-            return np.inf, np.full(self.d + 1, np.inf)
-        self._check(rc, "nlml_ard")
-        self._after_ard_call(theta, val.value, "nlml_ard")
-        return np.float64(val.value), (None if grad is None else g)
+            value, g = np.inf, (None if grad is None else np.full(self.d + 1, np.inf))
+        return dict(value=value, grad=g, mean=mean, var=var, nlpd=float(score[0]), sse=float(score[1]), spd=spd)
 
     def _after_ard_call(self, theta, nlml, what):
         """the handle's state after a library call that fitted at exp(theta) with per-feature scales: the fit's scalars (its epilogue: the
@@ -557,32 +561,12 @@ class GPR:
             raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if grad not in (None, "exact"):
+        if grad not in (None, "exact"):                    # (here, not only in _ard_call: a wrong ``grad`` is refused before missing data)
             raise ValueError("grad must be None or 'exact'")
-        if not self._has_data:
-            raise RuntimeError("loo_ard: no data staged; call fit() or set_data() first")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
-        if theta.shape[0] != self.d + 1:
-            raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
-        score = np.zeros(2)
-        g = np.zeros(self.d + 1) if grad is not None else None
-        mean = np.zeros(self.n) if predictions else None
-        var = np.zeros(self.n) if predictions else None
-        self._fitted = False
-        rc = self._lib.sigp_loo_grad_ard(self._h, self._kid, L.ptr(theta), theta.shape[0], L.LOO_MODES[sigma_f], L.LOO_CRITERION_IDS[criterion],
-                                         L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g))
-        if rc == L.NOT_SPD:
-            self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
-            value, g = np.inf, (None if grad is None else np.full(self.d + 1, np.inf))
-        else:
-            self._check(rc, "loo_ard")
-            self._after_ard_call(theta, None, "loo_ard")
-            value = np.float64(score[L.LOO_CRITERION_IDS[criterion]])
-        if predictions:
-            return dict(value=value, grad=g, mean=mean, var=var, nlpd=float(score[0]), sse=float(score[1]))
-        return value, g
+        r = self._ard_call("loo_ard", theta, grad, L.LOO_CRITERION_IDS[criterion], predictions, lambda th, mean, var, score, g: self._lib.sigp_loo_grad_ard(
+            self._h, self._kid, L.ptr(th), th.shape[0], L.LOO_MODES[sigma_f], L.LOO_CRITERION_IDS[criterion], L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
+        del r["spd"]
+        return r if predictions else (r["value"], r["grad"])
 
     def cv_ard(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit", grad="exact", predictions=False):
         """A leave-block-out score with per-feature (ARD) length scales as an optimiser's objective: theta = (log l_1 .. log l_d, log sn~) ->
@@ -598,30 +582,10 @@ class GPR:
         if grad not in (None, "exact"):
             raise ValueError("grad must be None or 'exact'")
         block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
-        if not self._has_data:
-            raise RuntimeError("cv_ard: no data staged; call fit() or set_data() first")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
-        if theta.shape[0] != self.d + 1:
-            raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
-        score = np.zeros(2)
-        g = np.zeros(self.d + 1) if grad is not None else None
-        mean = np.zeros(self.n) if predictions else None
-        var = np.zeros(self.n) if predictions else None
-        self._fitted = False
-        rc = self._lib.sigp_cv_grad_ard(self._h, self._kid, L.ptr(theta), theta.shape[0], block, gap, L.LOO_MODES[sigma_f], L.CV_CRITERION_IDS[criterion],
-                                        L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g))
-        if rc == L.NOT_SPD:
-            self._ard = True           # (set unless exp(theta) itself was refused; a scalar refit then clears them, which is harmless)
-            value, g = np.inf, (None if grad is None else np.full(self.d + 1, np.inf))
-        else:
-            self._check(rc, "cv_ard")
-            self._after_ard_call(theta, None, "cv_ard")
-            value = np.float64(score[L.CV_CRITERION_IDS[criterion]])
-        if predictions:
-            return dict(value=value, grad=g, mean=mean, var=var, nlpd=float(score[0]), sse=float(score[1]))
-        return value, g
+        r = self._ard_call("cv_ard", theta, grad, L.CV_CRITERION_IDS[criterion], predictions, lambda th, mean, var, score, g: self._lib.sigp_cv_grad_ard(
+            self._h, self._kid, L.ptr(th), th.shape[0], block, gap, L.LOO_MODES[sigma_f], L.CV_CRITERION_IDS[criterion], L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
+        del r["spd"]
+        return r if predictions else (r["value"], r["grad"])
 
     def cv_objective(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit"):
         """A leave-block-out score as an optimiser's objective over ONE common length scale: theta = (log l, log sn~) -> (value, grad [2])

@@ -305,3 +305,31 @@ def test_optimize_ard_other_criteria(S):
         b = gp.optimize(th0, ard=True, method="L-BFGS-B", bounds=bounds)
         c = gp.optimize_ard(np.log([np.sqrt(3.0), 1e-2]), method="L-BFGS-B", bounds=bounds)       # log l broadcast, criterion 'nlml' by default
     assert np.array_equal(a.x, b.x) and a.fun == b.fun and np.array_equal(c.x, a.x)
+
+
+# ---- 7. the profile entries of the calls ------------------------------------------------------------------------------------------------
+# (launches, flops, bytes) of SIGP_KC_MLII at n = 300 (three 128-tiles, padded rows in the last), d = 8, RBF: what the library books for
+# the triangular inversion, U U^T, the n^2 passes, the product M and the tile pass.  The figures are sums of products of small integers,
+# all exactly representable in a double, read off the library before the host drivers of these entry points were single-sourced.
+MLII_PINS = {
+    "nlml_ard": (3, 48368736.0, 513600.0),                    # triangular inversion, U U^T, the tile pass
+    "loo_ard_value_only": (2, 19054368.0, 360000.0),          # loo's own two entries
+    "loo_ard": (6, 125176032.0, 6182016.0),                   # ... + U U^T, the n^2 passes, the product M, the tile pass
+}
+
+
+def test_nlml_ard_and_loo_ard_profile_entries(S):
+    n, d = 300, 8
+    X, y, _ = O.synthetic_problem(n, d, 20252300)
+    th = _theta(ard_scales(d, 20252302))
+    calls = {"nlml_ard": lambda gp: gp.nlml_ard(th), "loo_ard_value_only": lambda gp: gp.loo_ard(th, grad=None), "loo_ard": lambda gp: gp.loo_ard(th)}
+    got = {}
+    with S.GPR(kernel="rbf") as gp:
+        gp.set_data(X, y)
+        for name, fn in calls.items():
+            gp.profile_reset()
+            fn(gp)
+            p = gp.profile_get()["mlii"]
+            got[name] = (p["launches"], p["flops"], p["bytes"])
+            print("%s: %r" % (name, got[name]))
+    assert got == MLII_PINS, got

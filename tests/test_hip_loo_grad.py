@@ -215,3 +215,103 @@ def test_what_has_no_leave_one_out_gradient(S):
         out = np.zeros(4)
         assert gp._lib.sigp_loo_grad(gp._h, 0, None, 0, None, None, L.ptr(out), L.ptr(out)) == L.BAD_ARG      # the reference kernel without M @ Sigma~
         assert np.all(np.isfinite(gp.loo(grad=True)["nlpd_grad"]))
+
+
+# ---- 6. the profile entries of the calls ------------------------------------------------------------------------------------------------
+# (launches, flops, bytes) of SIGP_KC_MLII at n = 300 (three 128-tiles, padded rows in the last), d = 8, RBF; the lockstep entries: one
+# group of two members.  The figures are sums of products of small integers, all exactly representable in a double, read off the library
+# before the host drivers of these entry points were single-sourced.
+MLII_PINS = {
+    "loo": (2, 19054368.0, 360000.0),                         # triangular inversion, the row pass
+    "loo_grad": (6, 95714208.0, 7828416.0),                   # ... + U U^T, the n^2 passes, the product W', the row / column / point passes
+    "nlml_exact": (2, 37748736.0, 0.0),                       # triangular inversion, U U^T
+    "loo_batch": (2, 38108736.0, 720000.0),
+    "loo_grad_batch": (6, 191428416.0, 15656832.0),
+    "cv_batch": (5, 207349576.0, 65400960.0),                 # triangular inversion, four entries for the one pass of 60 folds (block 5, gap 1)
+    "nlml_batch": (2, 75497472.0, 0.0),
+}
+
+
+def test_loo_nlml_and_lockstep_profile_entries(S):
+    n, d = 300, 8
+    Xb = np.zeros((2, n, d)); yb = np.zeros((2, n))
+    for b in range(2):
+        Xb[b], yb[b], _ = O.synthetic_problem(n, d, 20250900 + b)
+    ell, sn = np.array([np.sqrt(8.0), 2.0]), np.array([1e-2, 3e-2])
+    th = np.log(np.stack([ell, sn], axis=1))
+    single = {"loo": lambda gp: gp.loo(), "loo_grad": lambda gp: gp.loo(grad=True), "nlml_exact": lambda gp: gp.nlml(th[0], grad="exact")}
+    batch = {"loo_batch": lambda gp: gp.loo_batch(ell, sn, group=2), "loo_grad_batch": lambda gp: gp.loo_batch(ell, sn, group=2, grad=True),
+             "cv_batch": lambda gp: gp.cv_batch(ell, sn, 5, gap=1, group=2), "nlml_batch": lambda gp: gp.nlml_batch(th, group=2)}
+    got = {}
+    with S.GPR(kernel="rbf") as gp:
+        gp.fit(Xb[0], yb[0], ell[0], sn[0])
+        for name, fn in single.items():                      # (nlml comes last: it refits)
+            gp.profile_reset()
+            fn(gp)
+            p = gp.profile_get()["mlii"]
+            got[name] = (p["launches"], p["flops"], p["bytes"])
+            print("%s: %r" % (name, got[name]))
+        gp.upload_batch(Xb, yb, None, group=2)
+        for name, fn in batch.items():
+            gp.profile_reset()
+            fn(gp)
+            p = gp.profile_get()["mlii"]
+            got[name] = (p["launches"], p["flops"], p["bytes"])
+            print("%s: %r" % (name, got[name]))
+    assert got == MLII_PINS, got
+
+
+# ---- 7. a partial last lockstep group -----------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _partial_group_problem():
+    """three fits in groups of two at n = 130 (two 128-tiles, 126 padded rows): the second group has one member in a workspace laid out for
+    two, the one place where offsets indexed by the group size and by the members present part ways"""
+    B, n, d = 3, 130, 8
+    Xb = np.zeros((B, n, d)); yb = np.zeros((B, n))
+    for b in range(B):
+        Xb[b], yb[b], _ = O.synthetic_problem(n, d, 20251000 + b)
+    ell, sn = np.array([np.sqrt(8.0), 2.0, 3.5]), np.array([1e-2, 3e-2, 1e-1])
+    return Xb, yb, ell, sn, np.log(np.stack([ell, sn], axis=1))
+
+
+def _differing(pairs):
+    bad = []
+    for tag, a, b in pairs:
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        same = np.array_equal(a, b)
+        print("%s: %s (max |difference| %.3g)" % (tag, "same bits" if same else "DIFFERS", float(np.max(np.abs(a - b)))))
+        if not same:
+            bad.append(tag)
+    return bad
+
+
+def test_partial_last_lockstep_group_equals_single_fits(S):
+    """``loo_batch``, ``loo_batch(grad=True)`` and ``cv_batch`` against the single-fit calls at the same (l, sn~): the same bits.
+    ``nlml_batch`` already runs ragged last groups against ``nlml(grad="exact")`` in
+    test_hip_argument_ranges.py::test_lockstep_mlii_gradient_at_feature_counts_around_and_past_one_pad (five fits in groups of three, and a
+    member's bits equal whatever its group) and in test_hip_round2.py::test_lockstep_mlii_gradients_match_the_oracle_for_every_member, at the
+    tolerance two different reductions allow: ``sigp_nlml_grad`` reduces a stored dK~ row by row, ``sigp_nlml_grad_batch`` recomputes it over
+    the lower triangle, so the sums run in another order (2.8e-13 on gradients of order 10 here).  What has the same bits is pinned here too:
+    its values against the single fit, and its gradient against the one-member call of the same entry, where the group size and the members
+    present coincide."""
+    Xb, yb, ell, sn, th = _partial_group_problem()
+    block, gap = 5, 1
+    with S.GPR(kernel="rbf") as gp:
+        gp.upload_batch(Xb, yb, None, group=2)
+        loo = gp.loo_batch(ell, sn, group=2)
+        loog = gp.loo_batch(ell, sn, group=2, grad=True)
+        cv = gp.cv_batch(ell, sn, block, gap=gap, group=2)
+        nl, nlg = gp.nlml_batch(th, group=2, grad="exact")
+        alone = [gp.nlml_batch(th[i:i + 1], first=i, group=2, grad="exact") for i in range(len(ell))]
+        pairs = []
+        for i in range(len(ell)):
+            gp.fit(Xb[i], yb[i], ell[i], sn[i])
+            one, oneg, onecv = gp.loo(), gp.loo(grad=True), gp.cv(block, gap)
+            v, _ = gp.nlml(th[i], grad=None)
+            pairs += [("member %d loo_batch %s" % (i, k), loo[k][i], one[k]) for k in ("nlpd", "sse", "mean", "var")]
+            pairs += [("member %d loo_batch(grad) %s" % (i, k), loog[k][i], oneg[k]) for k in ("nlpd", "sse", "mean", "var") + KEYS]
+            pairs += [("member %d cv_batch %s" % (i, k), cv[k][i], onecv[k]) for k in ("nlpd", "sse", "mean", "var")]
+            pairs += [("member %d nlml_batch value" % i, nl[i], v), ("member %d nlml_batch value (alone)" % i, nl[i], alone[i][0][0]),
+                      ("member %d nlml_batch gradient (alone)" % i, nlg[i], alone[i][1][0])]
+    bad = _differing(pairs)
+    assert not bad, bad
