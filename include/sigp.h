@@ -235,8 +235,9 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
  * With scales set: SIGP_BAD_ARG for the reference kernel (SIGP_KERNEL_NETDIFFUSION in sigp_fit_predict, sigp_kernel_build_from_sigma)
  * and for sigp_dist_fit / sigp_dist_predict; on an fp32 handle the call itself is SIGP_BAD_ARG.  sigp_loo, sigp_cv, sigp_predict_cov and
  * sigp_get_alpha work on an ARD fit as on any other (they stage no features, or divide them as above).  The lockstep-batch entries
- * (sigp_batch_upload and everything on its resident data: sigp_batch_run, sigp_nlml_grad_batch, sigp_loo_batch, sigp_loo_grad_batch,
- * sigp_cv_batch) stage their own data and stay isotropic. */
+ * (sigp_batch_upload and everything on its resident data) stage their own data and neither read nor change these scales: sigp_batch_run,
+ * sigp_nlml_grad_batch, sigp_loo_batch, sigp_loo_grad_batch and sigp_cv_batch are isotropic; per-feature scales PER FIT of a lockstep group
+ * are sigp_batch_run_ard's and sigp_nlml_grad_ard_batch's (below). */
 int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
 /* MLII with per-feature length scales: theta = (log l_1 .. log l_d, log sn~), ntheta = d + 1 (else SIGP_BAD_ARG) -> the profiled nlML
  * (north/June1st.py:235-257) and, with grad_mode 2, its exact gradient grad [d + 1] (grad_mode 0: value only, grad may be NULL).  A grid
@@ -255,9 +256,38 @@ int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
  * sigp_nlml_grad does.  fp64 engine, RBF / Matern-5/2 only; before sigp_set_train: SIGP_BAD_ARG.  Afterwards the handle is fitted at
  * those hyper-parameters with the scales set: sigp_predict, sigp_predict_ride, sigp_loo, sigp_cv, sigp_predict_cov work on it.  Device
  * work is accounted under SIGP_KC_MLII (the triangular inversion, U U^T, the pass: one entry each).
- * Not covered: per-feature scales in the lockstep-batch entries (the ARD gradients of the leave-one-out and leave-block-out scores are
- * sigp_loo_grad_ard's and sigp_cv_grad_ard's), the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits. */
+ * Lockstep groups of such fits: sigp_nlml_grad_ard_batch (the ARD gradients of the leave-one-out and leave-block-out scores are
+ * sigp_loo_grad_ard's and sigp_cv_grad_ard's, single fits only).  Not covered: the one-workgroup kernel (sigp_small_*), the fp32 engine,
+ * sharded fits. */
 int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad);
+
+/* Per-feature (ARD) length scales in lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2, fp64).  Scales
+ * belong to a FIT, not to a data set: fit i uses data set (first + i) % batch with its own l_i in R^d, and two members of one group may share
+ * a data set and differ in scales (several starts per data set: the ARD likelihood is multimodal).  Per group (sigp_set_option "group") ONE
+ * staging launch fills, for every member, its scaled training features, scaled ride rows and its y -- u = x / l_k, the IEEE division, as
+ * sigp_set_length_scales stages them (a caller who uploads X / l and Xs / l as data sets of their own and runs the isotropic entries at
+ * ell = 1 gets the same bits) -- after ONE copy of the group's divisors; the staging area (8 group ((n_pad + 128) dp + n_pad) bytes) is
+ * allocated before the call's first launch.  From there on the group runs the isotropic entries' own launches at ell = 1: build, blocked
+ * Cholesky, epilogue.  The groups run one after another (no `concurrency`), as the score entries' do.
+ * sigp_batch_run_ard: ell [count][ldell >= d], sn_tilde [count] -> out [count][4], mean / var [count][m] as sigp_batch_run gives them (the
+ * ride points divided by the member's scales).  A non-finite or non-positive ell: SIGP_BAD_ARG.
+ * sigp_nlml_grad_ard_batch: what sigp_nlml_grad_batch does, with theta_i = theta[i ldtheta .. + ntheta) = (log l_1 .. log l_d, log sn~),
+ * ntheta = d + 1: nlml [count] and, with grad_mode 2, grad [count][ldgrad >= d + 1] (grad_mode 0: value only, grad may be NULL), the exact
+ * gradient of sigp_nlml_grad_ard.  Per group: staging, fit, L~^-T, K~^-1 = U U^T and A~ = U z for every member at once, then
+ * sigp_nlml_grad_ard's tile pass and its fixed-order sums with the member on a grid axis, one launch each (partials per member and tile,
+ * no atomics: the same bits on every run; the tile pass executes a single fit's instructions, so a member carries the bits
+ * sigp_nlml_grad_ard returns for that fit wherever the lockstep factorisation has the single fit's bits -- the small orders the tests pin;
+ * at large orders the blocked Cholesky's schedule depends on the number of members, as for every batch entry).  A member whose
+ * exp(theta) overflows, one of whose scales underflows to 0, or whose K~ is not SPD gets +inf in nlml and in all d + 1 gradient entries;
+ * its group mates are unaffected and the call returns SIGP_OK, as sigp_nlml_grad_batch does.
+ * SIGP_BAD_ARG: before sigp_batch_upload, an fp32 handle, the reference kernel, ntheta != d + 1, a leading dimension below its width.
+ * Device work is accounted under SIGP_KC_MLII, the staging under SIGP_KC_KBUILD.  Both calls leave the handle unfitted, as the other batch
+ * entries do, and neither read nor change the single-fit scales of sigp_set_length_scales.
+ * Not covered: ARD gradients of the leave-one-out / leave-block-out scores for lockstep groups, sigp_small_*, the fp32 engine, sharded fits. */
+int sigp_batch_run_ard(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, int64_t ldell, const double* sn_tilde,
+                       double* out, double* mean, double* var);
+int sigp_nlml_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
+                             int grad_mode, double* nlml, double* grad, int64_t ldgrad);
 
 /* Leave-one-out cross-validation with the hyper-parameters held (Rasmussen & Williams 5.4.2): what the block north/June1st.py:264-277
  * returns for training point i when it is fitted on the other n - 1 points and asked to predict point i, for every i, from ONE

@@ -64,6 +64,8 @@ SIGNATURES = {
     "sigp_nlml_grad_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, C.c_int, _dp, _dp]),
     "sigp_set_length_scales": (C.c_int, [_h, _dp, _i64]),
     "sigp_nlml_grad_ard": (C.c_int, [_h, C.c_int, _dp, _i64, C.c_int, C.POINTER(C.c_double), _dp]),
+    "sigp_batch_run_ard": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _i64, _dp, _dp, _dp, _dp]),
+    "sigp_nlml_grad_ard_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64]),
     "sigp_loo": (C.c_int, [_h, C.c_int, _dp, _dp, _dp]),
     "sigp_loo_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _i64, _dp]),
     "sigp_loo_grad": (C.c_int, [_h, C.c_int, _dp, _i64, _dp, _dp, _dp, _dp]),

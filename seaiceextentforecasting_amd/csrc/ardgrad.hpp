@@ -21,10 +21,12 @@ __device__ __forceinline__ double ard_h_from_sq(int kernel_id, double sq) {
 // Column means of the first n rows of U [n_pad][dp] (one block per feature, fixed-order sum) and the centred copy Uc = U - mean on those
 // rows; Uc's padding (rows >= n, columns >= d) is zeroed by the caller.  Differences of rows are unchanged; the expanded square of
 // ard_grad_partial_kernel then cancels at the scale of the data's spread, not of its offset (SST in kelvin, years).
-__global__ __launch_bounds__(256) void ard_center_kernel(const double* __restrict__ U, int dp, int n, double* __restrict__ Uc) {
+// blockIdx.y = lockstep member: its U and Uc lie sU doubles behind the previous member's (a single fit: one member, stride 0).
+__global__ __launch_bounds__(256) void ard_center_kernel(const double* __restrict__ U, int dp, int n, double* __restrict__ Uc, long sU = 0) {
   __shared__ double sh[4];
   __shared__ double mean;
   const int k = blockIdx.x;
+  U += (long)blockIdx.y * sU; Uc += (long)blockIdx.y * sU;
   double t = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) t += U[(long)i * dp + k];
   t = block_reduce_sum(t, sh);
@@ -48,13 +50,22 @@ __global__ __launch_bounds__(256) void ard_center_kernel(const double* __restric
 // WSEL picks the weight: ARD_W_NLML, the adjoint of the nlML above; ARD_W_LOO, the adjoint of a leave-one-out score (looard.hpp) --
 // W = (2 M_ij + v_i a_j + a_i v_j + 2 eps a_i a_j) o h with M = P diag(gamma) P read where P is read (its lower 128-tiles), v = P beta and
 // eps[0] from device memory (q is not read).  Everything after the weight is shared.
+// blockIdx.y = lockstep member (sigp_nlml_grad_ard_batch): member b reads U, Uc, P, a, q and writes partial at b times the strides of ms
+// (in doubles); the offsets are added to the pointers before anything is read, so a member executes the instructions a single fit does.
+// Single fits launch one member with zero strides; v and eps (ARD_W_LOO) have no member axis.
 enum { ARD_W_NLML = 0, ARD_W_LOO = 1 };
+struct ArdMemberStrides { long U, P, a, q, partial; };   // U and Uc alike; q: the slot's result rows (512 doubles apart)
 template <int DC, int WSEL = ARD_W_NLML>
 __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __restrict__ U, const double* __restrict__ Uc, int dp, int d, int n,
                                                                int kernel_id, const double* __restrict__ P, long ld,
                                                                const double* __restrict__ a, const double* __restrict__ q,
                                                                double* __restrict__ partial, const double* __restrict__ v = nullptr,
-                                                               const double* __restrict__ eps = nullptr) {
+                                                               const double* __restrict__ eps = nullptr, ArdMemberStrides ms = ArdMemberStrides{0, 0, 0, 0, 0}) {
+  {
+    const long mb = blockIdx.y;
+    U += mb * ms.U; Uc += mb * ms.U; P += mb * ms.P; a += mb * ms.a; partial += mb * ms.partial;
+    if constexpr (WSEL == ARD_W_NLML) q += mb * ms.q;
+  }
   const int u = blockIdx.x >> 1;                       // (the lower-triangle tile walk of kbuild_mfma_kernel)
   int k = (int)((sqrt(8.0 * u + 1.0) - 1.0) * 0.5);
   while ((k + 1) * (k + 2) / 2 <= u) ++k;
@@ -147,12 +158,20 @@ __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __r
 
 // grad[k] = sum over the tiles, in tile order, of partial[tile][k] (k < d: block k), and grad[d] = sn~ sum_i (P_ii / 2 - a_i^2 / (2 sf))
 // (block d).  Every thread adds its tiles / rows in ascending order and block_reduce_sum adds the threads in a fixed order: the same
-// bits on every run.
+// bits on every run.  blockIdx.y = lockstep member: the strides of ms as above, grad [member][sGrad], and the member's sn~ from sn_m
+// (device memory; NULL: the argument sn, a single fit).
 __global__ __launch_bounds__(256) void ard_grad_finish_kernel(const double* __restrict__ partial, long ntiles, int dp, int d, int n,
                                                               const double* __restrict__ P, long ld, const double* __restrict__ a,
-                                                              const double* __restrict__ q, double sn, double* __restrict__ grad) {
+                                                              const double* __restrict__ q, double sn, double* __restrict__ grad,
+                                                              ArdMemberStrides ms = ArdMemberStrides{0, 0, 0, 0, 0}, long sGrad = 0,
+                                                              const double* __restrict__ sn_m = nullptr) {
   __shared__ double sh[4];
   const int k = blockIdx.x;
+  {
+    const long mb = blockIdx.y;
+    partial += mb * ms.partial; P += mb * ms.P; a += mb * ms.a; q += mb * ms.q; grad += mb * sGrad;
+    if (sn_m != nullptr) sn = sn_m[mb];
+  }
   double t = 0.0;
   if (k < d) {
     for (long i = threadIdx.x; i < ntiles; i += 256) t += partial[i * dp + k];
@@ -162,6 +181,30 @@ __global__ __launch_bounds__(256) void ard_grad_finish_kernel(const double* __re
   }
   t = block_reduce_sum(t, sh);
   if (threadIdx.x == 0) grad[k] = k < d ? t : sn * t;
+}
+
+// Per-member scaled staging of a lockstep group (sigp_batch_run_ard, sigp_nlml_grad_ard_batch): member b = blockIdx.y has data set
+// (first_ds + b) % batch of the resident batch data (bX [batch][n_pad][dp], bXs [batch][ride][dp], by [batch][n_pad], zero padded) and the
+// divisors div [b][dp].  One launch fills the member's scaled training features, scaled ride rows and its y, laid out as the resident data are
+// so that the member is "data set b" of the staging area to every kernel that takes a data-set index.  u = x / l_k is the IEEE division
+// (pad_copy_kernel's, the same bits); the padding (rows >= n, features >= d) is zero in the source and stays zero.
+__global__ __launch_bounds__(256) void ard_stage_kernel(const double* __restrict__ bX, const double* __restrict__ bXs, const double* __restrict__ by,
+                                                        long first_ds, long batch, int n_pad, int ride, int dp, int d, const double* __restrict__ div,
+                                                        double* __restrict__ X, double* __restrict__ Xs, double* __restrict__ y) {
+  const long b = blockIdx.y, ds = (first_ds + b) % batch;
+  const long nx = (long)n_pad * dp, nr = (long)ride * dp;
+  long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx < nx + nr) {
+    const bool train = idx < nx;
+    if (!train) idx -= nx;
+    const int p = (int)(idx % dp);
+    double v = train ? bX[ds * nx + idx] : bXs[ds * nr + idx];
+    if (p < d) v = v / div[b * dp + p];
+    (train ? X + b * nx : Xs + b * nr)[idx] = v;
+  } else if (idx < nx + nr + n_pad) {
+    idx -= nx + nr;
+    y[b * n_pad + idx] = by[ds * n_pad + idx];
+  }
 }
 
 }  // namespace sigp

@@ -111,6 +111,7 @@ struct sigp_handle {
   double* XsRaw = nullptr; long cap_XsRaw = 0;
   double* ardDiv = nullptr; long cap_ardDiv = 0;
   double* ardXc = nullptr; long cap_ardXc = 0;
+  double* bStage = nullptr; long cap_bStage = 0;   // sigp_ardbatch.inc: a lockstep group's per-member scaled features, ride rows, y, divisors and sn~
   int opt_cv_slices = 0;     // K slices of the strip product of sigp_cv: 0 = auto (two workgroups per CU, at most 32), otherwise the count (clipped to the 32-column stages of the fit)
   int cv_slices_used = 0;    // ... and the count the last call ran with (sigp_get_stat "cv_slices")
   int cov_slices_used = 0;   // ... and the count the last call ran with (sigp_get_stat "cov_slices")
@@ -774,7 +775,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 570; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard
+int sigp_version(void) { return 580; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -812,7 +813,7 @@ int sigp_destroy(sigp_handle* h) {
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
   double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
-                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->cvAdj, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc};
+                    h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->cvAdj, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc, h->bStage};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
   if (h->sm_probs) (void)hipFree(h->sm_probs);
@@ -1788,6 +1789,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_predcov.inc"   // sigp_predict_cov: joint predictive covariance at new points
 #include "sigp_blockcv.inc"   // sigp_cv, sigp_cv_batch: leave-block-out cross-validation
 #include "sigp_ardgrad.inc"   // sigp_set_length_scales, sigp_nlml_grad_ard: per-feature length scales and their exact MLII gradient
+#include "sigp_ardbatch.inc"  // sigp_batch_run_ard, sigp_nlml_grad_ard_batch: per-feature length scales in lockstep groups
 #include "sigp_looard.inc"    // sigp_loo_grad_ard: exact per-feature gradients of the leave-one-out scores
 #include "sigp_cvard.inc"     // sigp_cv_grad_ard: exact per-feature gradients of the leave-block-out scores
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend

@@ -2,8 +2,8 @@
 // The ARD kernel is the isotropic one at ell = 1 on u = x / l, so the scales live in the STAGING: the handle keeps the raw features and
 // ride rows beside the scaled ones the builds read (pad_copy_kernel's divisor), and every later staging of test points divides alike.
 // No covariance function and no existing kernel changes; a handle that never sets scales runs the launches it ran before.
-// Out of scope: the lockstep-batch entries (their resident data is staged by sigp_batch_upload and stays isotropic), the one-workgroup
-// kernel (sigp_small_*), the fp32 engine, sharded fits.  ARD gradients of the leave-one-out / leave-block-out scores: sigp_looard.inc, sigp_cvard.inc.
+// Out of scope: the one-workgroup kernel (sigp_small_*), the fp32 engine, sharded fits.  Per-feature scales per fit of a lockstep group on the
+// resident batch data: sigp_ardbatch.inc.  ARD gradients of the leave-one-out / leave-block-out scores: sigp_looard.inc, sigp_cvard.inc.
 // Included inside extern "C" of sigp.hip, after sigp_scores.inc (the shared steps: sigp_nlml_grad_ard is ard_check_engine, ard_theta_fit,
 // inv_factor, kinv_lower, alpha_from_U, ard_tile_pass<ARD_W_NLML> and its own finish kernel) and sigp_blockcv.inc.
 

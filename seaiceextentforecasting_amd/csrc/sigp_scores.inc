@@ -67,24 +67,30 @@ static int mirror_P(sigp_handle* h, hipStream_t st, int nb, long n_pad) {
 }
 
 // ---- per-feature (ARD) gradients ---------------------------------------------------------------------------------------------------------------
-// The tile pass over the handle's scaled features: their centred copy into ardXc, then every tile's share of all d components into
-// partial [tiles][dp].  W = ARD_W_NLML: M = K~^-1 (lower tiles), a, q = y^T a;  W = ARD_W_LOO: M, a, v, eps of looard.hpp (q is not read).
-// The callers launch their own finish kernel, and book the pass and the finish under one profile entry of their own.
+// The tile pass over scaled features U [n_pad][dp] (nb lockstep members, strides ms): their centred copy into ardXc, then every tile's share
+// of all d components into partial [tiles][dp].  W = ARD_W_NLML: M = K~^-1 (lower tiles), a, q = y^T a;  W = ARD_W_LOO: M, a, v, eps of
+// looard.hpp (q is not read; one member).  The callers launch their own finish kernel, and book the pass and the finish under one profile
+// entry of their own.  ard_tile_pass: the single fit -- the handle's own features, one member, zero strides.
 extern "C++" {
+template <int W>
+static int ard_tile_pass_members(sigp_handle* h, hipStream_t st, int nb, const double* U, long n, long d, long dp, long n_pad, ArdMemberStrides ms, int kernel_id,
+                                 const double* M, long ldm, const double* a, const double* q, const double* v, const double* eps, double* partial) {
+  const long ntiles = kbuild_tiles(n_pad);
+  const int kid = kernel_id == SIGP_KERNEL_RBF ? KID_RBF : KID_MATERN52;
+  HIPCHK(h, hipMemsetAsync(h->ardXc, 0, (size_t)(ms.U * (nb - 1) + n_pad * dp) * sizeof(double), st));
+  hipLaunchKernelGGL(ard_center_kernel, dim3((unsigned)d, (unsigned)nb), dim3(256), 0, st, U, (int)dp, (int)n, h->ardXc, ms.U);
+  if (d <= 8)
+    hipLaunchKernelGGL((ard_grad_partial_kernel<8, W>), dim3((unsigned)ntiles, (unsigned)nb), dim3(256), 0, st, U, (const double*)h->ardXc, (int)dp, (int)d, (int)n, kid, M, ldm,
+                       a, q, partial, v, eps, ms);
+  else
+    hipLaunchKernelGGL((ard_grad_partial_kernel<32, W>), dim3((unsigned)ntiles, (unsigned)nb), dim3(256), 0, st, U, (const double*)h->ardXc, (int)dp, (int)d, (int)n, kid, M, ldm,
+                       a, q, partial, v, eps, ms);
+  return SIGP_OK;
+}
 template <int W>
 static int ard_tile_pass(sigp_handle* h, hipStream_t st, int kernel_id, const double* M, long ldm, const double* a, const double* q, const double* v,
                          const double* eps, double* partial) {
-  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ntiles = kbuild_tiles(n_pad);
-  const int kid = kernel_id == SIGP_KERNEL_RBF ? KID_RBF : KID_MATERN52;
-  HIPCHK(h, hipMemsetAsync(h->ardXc, 0, (size_t)n_pad * dp * sizeof(double), st));
-  hipLaunchKernelGGL(ard_center_kernel, dim3((unsigned)d), dim3(256), 0, st, (const double*)h->X, (int)dp, (int)n, h->ardXc);
-  if (d <= 8)
-    hipLaunchKernelGGL((ard_grad_partial_kernel<8, W>), dim3((unsigned)ntiles), dim3(256), 0, st, (const double*)h->X, (const double*)h->ardXc, (int)dp, (int)d, (int)n, kid, M, ldm,
-                       a, q, partial, v, eps);
-  else
-    hipLaunchKernelGGL((ard_grad_partial_kernel<32, W>), dim3((unsigned)ntiles), dim3(256), 0, st, (const double*)h->X, (const double*)h->ardXc, (int)dp, (int)d, (int)n, kid, M, ldm,
-                       a, q, partial, v, eps);
-  return SIGP_OK;
+  return ard_tile_pass_members<W>(h, st, 1, h->X, h->n, h->d, h->dp, h->n_pad, ArdMemberStrides{0, 0, 0, 0, 0}, kernel_id, M, ldm, a, q, v, eps, partial);
 }
 }  // extern "C++"
 
@@ -162,17 +168,26 @@ static int batch_check_params(sigp_handle* h, const char* what, int64_t count, c
   return SIGP_OK;
 }
 
-// One group of nb members through the fit: member b has (ell[b], snt[b]) and data set (first_ds + b) % batch.  Covariance build, blocked
-// Cholesky, epilogue: q stays on the device in the slot's result rows, and the parameters uploaded here stay put until the next group's
-// (y of member b is data set s.kps[b].ds).  sigp_batch_run has its own loop: concurrency and slots, which the score entries do without.
-static int batch_group_fit(sigp_handle* h, Slot& s, int nb, int kernel_id, const double* ell, const double* snt, long first_ds) {
+// One group of nb members through the fit on data sets laid out as the resident ones (X [.][n_pad][dp], y [.][n_pad], Xs [.][RIDE][dp]): member b
+// has (ell[b], snt[b]) and data set ds[b], m ride points.  Covariance build, blocked Cholesky, epilogue: q stays on the device in the slot's
+// result rows, and the parameters uploaded here stay put until the next group's (y of member b is data set s.kps[b].ds).
+static int batch_group_fit_on(sigp_handle* h, Slot& s, int nb, int kernel_id, const double* ell, const double* snt, const int* ds, const double* X, const double* y,
+                              const double* Xs, long m) {
   const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad;
   int rc;
-  for (int b = 0; b < nb; ++b) s.kps_host[b] = make_kparams(kernel_id, ell[b], snt[b], (int)((first_ds + b) % h->b_count));
+  for (int b = 0; b < nb; ++b) s.kps_host[b] = make_kparams(kernel_id, ell[b], snt[b], ds[b]);
   if ((rc = upload_kparams(h, s, nb))) return rc;
-  if ((rc = build_cov(h, s, nb, h->bX, n_pad * dp, h->by, n_pad, h->bXs, (long)RIDE * dp, n, d, dp, n_pad, 0))) return rc;
-  if ((rc = potrf_slot(h, s, nb, n_pad, false, 1))) return rc;
-  return epilogue_slot(h, s, nb, n, n_pad, 0);
+  if ((rc = build_cov(h, s, nb, X, n_pad * dp, y, n_pad, Xs, (long)RIDE * dp, n, d, dp, n_pad, m))) return rc;
+  if ((rc = potrf_slot(h, s, nb, n_pad, false, 1 + (int)m))) return rc;
+  return epilogue_slot(h, s, nb, n, n_pad, m);
+}
+
+// ... on the resident batch data: member b has data set (first_ds + b) % batch, no ride points.  sigp_batch_run has its own loop: concurrency
+// and slots, which the score entries do without.
+static int batch_group_fit(sigp_handle* h, Slot& s, int nb, int kernel_id, const double* ell, const double* snt, long first_ds) {
+  std::vector<int> ds((size_t)nb);
+  for (int b = 0; b < nb; ++b) ds[(size_t)b] = (int)((first_ds + b) % h->b_count);
+  return batch_group_fit_on(h, s, nb, kernel_id, ell, snt, ds.data(), h->bX, h->by, h->bXs, 0);
 }
 
 // a group's rows (mv [nb][2][n_pad] <- mean, var; NULL: none) and sums (sc [nb][2]) on their way to the host: the sums lie behind the rows of

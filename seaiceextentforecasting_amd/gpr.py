@@ -823,7 +823,9 @@ class GPR:
         sn_tilde [F]; F fits, fit i uses data set i % B.
         Returns dict(sigma_f, nlml, info, sigma_n, mean [F,m], var [F,m]).
 
-        RBF / Matern: lockstep groups on the blocked engine (data sets share (n, d, m)).
+        RBF / Matern: lockstep groups on the blocked engine (data sets share (n, d, m)).  A 2-D ``ell`` [F, d] gives every FIT its own
+        per-feature (ARD) length scales (``sigp_batch_run_ard``: the library divides the member's features and test points by them; the
+        groups then run one after another, ``concurrency`` does not apply).
         Reference kernel: X / y / Xs may also be LISTS of arrays of different shapes (the retro years: n grows with the
         year); fits of order n <= 128 run one workgroup per fit in a single launch (``smallbatch.SmallBatch``), with
         Sigma~ = expm(l M) formed as this engine's ``expm`` option says; larger ones go one at a time through ``fit``."""
@@ -842,14 +844,27 @@ class GPR:
             if Xsb.shape[0] != B or Xsb.shape[2] != d:
                 raise ValueError("Xs must be [B,m,d]")
             m = Xsb.shape[1]
-        ell = L.f64(np.atleast_1d(ell), 1)
+        ell = self._batch_ell(ell, d)
         sn = L.f64(np.atleast_1d(sn_tilde), 1)
         F = len(ell)
         if len(sn) != F:
             raise ValueError("ell and sn_tilde must have the same length")
         self._check(self._lib.sigp_batch_upload(self._h, B, L.ptr(Xb), n * d, L.ptr(yb), n, L.ptr(Xsb), m * d, n, d, m), "batch_upload")
-        self._batch_m, self._batch_n = m, n
+        self._batch_m, self._batch_n, self._batch_d, self._batch_B = m, n, d, B
         return self.run_batch(0, F, ell, sn, concurrency, group)
+
+    @staticmethod
+    def _batch_ell(ell, d):
+        """ell [F] (one common length scale per fit) or [F, d] (per-feature scales per fit) as a contiguous array"""
+        ell = L.f64(np.atleast_1d(ell))
+        if ell.ndim == 2:
+            if d is None:
+                raise RuntimeError("run_batch: stage the data sets with fit_batch() / upload_batch() first")
+            if ell.shape[1] != d:
+                raise ValueError("a 2-D ell must be [F, d] = [F, %d] (one length scale per fit and feature), got %s" % (d, ell.shape))
+        elif ell.ndim != 1:
+            raise ValueError("ell must be [F] or [F, d]")
+        return ell
 
     def predict_batch(self, X, y, Xs, ell, sn_tilde, **kw):
         """(mean [F, m], var [F, m]) of a batch of independent fits at their test points -- the per-(region, year) outputs
@@ -937,14 +952,15 @@ class GPR:
             Xsb = Xsb[None] if Xsb.ndim == 2 else Xsb
             m = Xsb.shape[1]
         self._check(self._lib.sigp_batch_upload(self._h, B, L.ptr(Xb), n * d, L.ptr(yb), n, L.ptr(Xsb), m * d, n, d, m), "batch_upload")
-        self._batch_m, self._batch_n = m, n
+        self._batch_m, self._batch_n, self._batch_d, self._batch_B = m, n, d, B
         self._check(self._lib.sigp_batch_reserve(self._h, int(group), int(concurrency)), "batch_reserve")
 
     def run_batch(self, first, count, ell, sn_tilde, concurrency=2, group=8):
         """Run ``count`` fits on the data sets already resident in HBM (after fit_batch / upload).
-        ``group`` fits are factorised in lockstep by each launch; ``concurrency`` groups are in flight."""
+        ``group`` fits are factorised in lockstep by each launch; ``concurrency`` groups are in flight.  ``ell`` [count, d]: per-feature
+        length scales per fit (``sigp_batch_run_ard``; one group in flight)."""
+        ell = self._batch_ell(ell, getattr(self, "_batch_d", None))
         self.set_option("group", group)
-        ell = L.f64(np.atleast_1d(ell), 1)
         sn = L.f64(np.atleast_1d(sn_tilde), 1)
         out = np.zeros((count, 4))
         if len(ell) != count or len(sn) != count:
@@ -952,8 +968,12 @@ class GPR:
         mdim = getattr(self, "_batch_m", 0)
         mean = np.zeros((count, max(mdim, 1)))
         var = np.zeros((count, max(mdim, 1)))
-        rc = self._lib.sigp_batch_run(self._h, int(first), int(count), self._kid, L.ptr(ell), L.ptr(sn), int(concurrency),
-                                      L.ptr(out), L.ptr(mean) if mdim else None, L.ptr(var) if mdim else None)
+        if ell.ndim == 2:
+            rc = self._lib.sigp_batch_run_ard(self._h, int(first), int(count), self._kid, L.ptr(ell), ell.shape[1], L.ptr(sn),
+                                              L.ptr(out), L.ptr(mean) if mdim else None, L.ptr(var) if mdim else None)
+        else:
+            rc = self._lib.sigp_batch_run(self._h, int(first), int(count), self._kid, L.ptr(ell), L.ptr(sn), int(concurrency),
+                                          L.ptr(out), L.ptr(mean) if mdim else None, L.ptr(var) if mdim else None)
         self._check(rc, "batch_run")
         self._fitted = False
         return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
@@ -1012,6 +1032,33 @@ class GPR:
         self._fitted = False
         return val, (g if grad is not None else None)
 
+    def nlml_ard_batch(self, theta, first=0, grad="exact", group=8):
+        """``nlml_ard`` for many fits in one device call on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern, fp64):
+        theta [F, d + 1] = (log l_1 .. log l_d, log sn~) per FIT, fit i uses data set (first + i) % B -- two fits may share a data set and
+        differ in scales (several starts per data set).  Lockstep groups of ``group`` fits (``sigp_nlml_grad_ard_batch``): per group one
+        staging launch divides every member's features by its scales, then the fit, K~^-1 and ``nlml_ard``'s one-pass gradient for all
+        members at once.  Returns (nlml [F], grad [F, d + 1] or None); a fit whose K~ is not SPD or whose exp(theta) overflows gets +inf in
+        its value and all its gradient entries, its group mates are unaffected.  The gradient pass is ``nlml_ard``'s own code: where the lockstep factorisation has the single fit's bits
+        (small orders), every fit carries the bits ``nlml_ard`` returns for it."""
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        d = getattr(self, "_batch_d", None)
+        if d is None:
+            raise RuntimeError("nlml_ard_batch: stage the data sets with upload_batch() first")
+        theta = L.f64(np.atleast_2d(theta), 2)
+        if theta.shape[1] != d + 1:
+            raise ValueError("theta must be [F, d + 1] = [F, %d] (log l_1 .. log l_d, log sn~), got %s" % (d + 1, theta.shape))
+        F = theta.shape[0]
+        self.set_option("group", group)
+        val = np.zeros(F)
+        g = np.zeros((F, d + 1)) if grad is not None else None
+        self._check(self._lib.sigp_nlml_grad_ard_batch(self._h, int(first), F, self._kid, L.ptr(theta), d + 1, d + 1, 0 if grad is None else 2, L.ptr(val),
+                                                       L.ptr(g), d + 1), "nlml_ard_batch")
+        self._fitted = False
+        return val, g
+
     def _loo_objective_batch(self, theta, criterion, sigma_f, group):
         """(value [F], grad [F, 2]) of a leave-one-out score for theta [F, 2] on the staged data sets, one device call (``loo_batch``)."""
         theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
@@ -1027,7 +1074,7 @@ class GPR:
         return f, g
 
     def optimize_batch(self, X, y, theta0, group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0, M=None, expm="eigh", method=None,
-                       criterion="nlml", sigma_f="refit"):
+                       criterion="nlml", sigma_f="refit", ard=False):
         """The reference's commented-out ``minimize(MLII, x0, method='CG', jac=True)`` (north/June1st.py:259-262) for EVERY data set
         of a retrospective run at once: X [B, n, d], y [B, n], theta0 [B, 2] (or [2]) -> dict(x [B, 2], fun [B], nit [B],
         converged [B], nfev = device calls).  The state of every data set lives on the host and each round is ONE device call for all
@@ -1038,8 +1085,20 @@ class GPR:
         Reference kernel (``method='newton'``): X / y (/ M) are sequences of ragged data sets (the 3 regions x years of
         September1st_retro.py:176-180); a round is ONE launch of one workgroup per point, value + exact gradient formed in LDS, and since
         extra points are free there each round carries several step lengths and their finite-difference neighbours: a modified-Newton
-        iteration with the line search inside the launch."""
+        iteration with the line search inside the launch.
+
+        Several starts per data set (RBF / Matern): ``theta0`` may have F = S B rows; start i uses data set i % B, the batch's own pairing,
+        and all F results come back -- choosing the best start of a data set is the caller's job.
+        ``ard=True`` (RBF / Matern, ``criterion='nlml'``): one length scale per feature, the same lockstep BFGS on ``nlml_ard_batch`` (d + 1
+        parameters per start).  ``theta0`` is [F, d + 1], [d + 1], [F, 2] or [2]; with two entries the common log l is repeated for all d
+        features.  Returns x [F, d + 1].  The leave-one-out / leave-block-out scores over per-feature scales have no lockstep form:
+        ``optimize_ard`` minimises them one data set at a time."""
         from .optim import bfgs_lockstep, newton_lockstep
+        if ard and criterion != "nlml":
+            raise ValueError("optimize_batch(ard=True): criterion must be 'nlml' (optimize_ard minimises the leave-one-out and leave-block-out scores over "
+                             "per-feature scales, one data set at a time)")
+        if ard and self.kernel == "netdiffusion":
+            raise ValueError("optimize_batch(ard=True): per-feature length scales cover the RBF / Matern kernels")
         if criterion != "nlml" and criterion not in L.LOO_CRITERIA:
             raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
         if criterion != "nlml" and self.kernel == "netdiffusion":
@@ -1058,7 +1117,24 @@ class GPR:
         X = L.f64(X, 3)
         B = X.shape[0]
         self.upload_batch(X, y, None, group=group, concurrency=1)
-        th0 = np.broadcast_to(np.asarray(theta0, dtype=np.float64), (B, 2))
+        th0 = np.asarray(theta0, dtype=np.float64)
+        p = 2
+        if ard:
+            d = X.shape[2]
+            p = d + 1
+            th0 = np.atleast_2d(th0)
+            if th0.ndim == 2 and th0.shape[1] == 2 and d != 1:      # (log l, log sn~): the common log l for every feature
+                th0 = np.concatenate([np.repeat(th0[:, :1], d, axis=1), th0[:, 1:]], axis=1)
+            if th0.ndim != 2 or th0.shape[1] != p:
+                raise ValueError("theta0 must hold d + 1 = %d entries per start, or 2 (log l is repeated for every feature)" % p)
+            if th0.shape[0] == 1:
+                th0 = th0[0]
+        if th0.ndim == 2 and th0.shape[0] != B and th0.shape[1] == p and th0.shape[0] % B == 0:
+            th0 = np.array(th0)                                   # S starts per data set: start i uses data set i % B
+        else:
+            th0 = np.broadcast_to(th0, (B, p))
+        if ard:
+            return bfgs_lockstep(lambda t: self.nlml_ard_batch(t, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
         if criterion != "nlml":   # the same lockstep BFGS on a leave-one-out score: one sigp_loo_grad_batch call per round
             return bfgs_lockstep(lambda t: self._loo_objective_batch(t, criterion, sigma_f, group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
         return bfgs_lockstep(lambda t: self.nlml_batch(t, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)

@@ -1,5 +1,6 @@
-"""Lockstep quasi-Newton driver for the ``MLII`` contract (north/June1st.py:235-262): B independent 2-parameter problems
-(theta = (log l, log sn~) per (region, year) data set) advance TOGETHER -- every round asks the caller for ONE trial point per
+"""Lockstep quasi-Newton driver for the ``MLII`` contract (north/June1st.py:235-262): B independent p-parameter problems
+(theta = (log l, log sn~) per (region, year) data set, p = 2; with per-feature length scales (log l_1 .. log l_d, log sn~), p = d + 1)
+advance TOGETHER -- every round asks the caller for ONE trial point per
 unfinished data set, i.e. one device call for the lot, whatever the individual line searches do.
 
 The reference's call (`minimize(MLII, x0, method='CG', jac=True)`, commented out at :259-262) started from its table entries; many of
@@ -10,21 +11,21 @@ import numpy as np
 
 
 def bfgs_lockstep(evaluate, theta0, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0):
-    """``evaluate(theta [B, 2]) -> (f [B], g [B, 2])`` (+inf where the fit fails).  Returns dict(x, fun, jac, nit, nfev, converged).
-    BFGS on the 2-vector per data set, Armijo backtracking; finished data sets ride along at their optimum so that every round is
+    """``evaluate(theta [B, p]) -> (f [B], g [B, p])`` (+inf where the fit fails), p = theta0.shape[1].  Returns dict(x, fun, jac, nit, nfev,
+    converged).  BFGS on the p-vector per data set, Armijo backtracking; finished data sets ride along at their optimum so that every round is
     one call of the same shape."""
     th = np.array(theta0, dtype=np.float64, copy=True)
-    B = th.shape[0]
+    B, p_ = th.shape
     f, g = evaluate(th)
     f, g = np.array(f, dtype=np.float64), np.array(g, dtype=np.float64)
     nfev = 1
-    H = np.tile(np.eye(2), (B, 1, 1))
+    H = np.tile(np.eye(p_), (B, 1, 1))
     fresh = np.ones(B, dtype=bool)                 # H is still the identity: unit first step, scale before the first update
     done = ~np.isfinite(f) | (np.max(np.abs(g), axis=1) <= gtol)
     nit = np.zeros(B, dtype=np.int64)
     small = np.zeros(B, dtype=np.int64)            # consecutive accepted steps with a negligible decrease
     step = np.ones(B)
-    direction = np.zeros((B, 2))
+    direction = np.zeros((B, p_))
     trial = th.copy()
     new_dir = np.ones(B, dtype=bool)
     for _ in range(maxiter * 8):
@@ -35,7 +36,7 @@ def bfgs_lockstep(evaluate, theta0, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=
             if new_dir[b]:
                 p = -H[b] @ g[b]
                 if p @ g[b] >= 0:                     # not a descent direction: reset the inverse Hessian
-                    H[b] = np.eye(2); p = -g[b]; fresh[b] = True
+                    H[b] = np.eye(p_); p = -g[b]; fresh[b] = True
                 nrm = np.linalg.norm(p)
                 if fresh[b] and nrm > 0:
                     p = p / nrm                       # first step of this data set: unit length in log space
@@ -56,9 +57,9 @@ def bfgs_lockstep(evaluate, theta0, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=
                 sy = s_ @ yv
                 if sy > 1e-14 * max(1.0, np.linalg.norm(s_) * np.linalg.norm(yv)):
                     if fresh[b]:
-                        H[b] = np.eye(2) * (sy / (yv @ yv)); fresh[b] = False
+                        H[b] = np.eye(p_) * (sy / (yv @ yv)); fresh[b] = False
                     rho = 1.0 / sy
-                    V = np.eye(2) - rho * np.outer(s_, yv)
+                    V = np.eye(p_) - rho * np.outer(s_, yv)
                     H[b] = V @ H[b] @ V.T + rho * np.outer(s_, s_)
                 new_dir[b] = True
                 small[b] = small[b] + 1 if df <= ftol * max(1.0, abs(f[b])) else 0
