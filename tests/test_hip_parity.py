@@ -2,7 +2,9 @@
 
 Tolerances (fp64):
   kernel matrix K~            <= 1e-13 relative (max-norm)         SURVEY.md 7 step 3
-  Cholesky factor L~          <= 1e-11 relative, ||LL^T-K||/||K|| <= 1e-13*sqrt(n)
+  Cholesky factor L~          <= 1e-11 relative, ||LL^T-K||/||K|| <= 1e-13*sqrt(n) here (easy matrices); the tight form,
+                              ||LL^T-K||_F/||K||_F <= 16 max(LAPACK's own, 2^-53) with the product in long double (LAPACK: 2-6e-16),
+                              at cond(K~) up to 1e14, is asserted in tests/test_hip_conditioning.py
   predictions (mean, var)     <= 1e-8 relative                      BASELINE.json north_star
   sigma_f, nlML               <= 1e-9 relative
 """
