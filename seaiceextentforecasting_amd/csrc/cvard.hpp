@@ -26,21 +26,16 @@
 #include <hip/hip_runtime.h>
 
 #include "blockcv.hpp"
+#include "score_layout.hpp"
 #include "syrk128.hpp"
 
 namespace sigp {
 
 constexpr int CVA_BAND = 3 * SY_T;     // columns of a row of the band store
+static_assert(CVA_BAND == SL_BAND && CV_MAXW == SL_BLK, "score_layout.hpp lays the band store and the fold blocks out for these");
 
-// What cv_launch does for the gradient when it is given one of these (sigp_cv_grad_ard): the fold adjoints of each pass and their assembly.
-struct CvAdjoint {
-  int crit;          // 0 nlpd, 1 sse
-  double* Bf;        // [folds of a pass][wp][wp]  (lower 16 x 16 subtiles written)
-  double* betaf;     // [folds of a pass][wp]
-  double* epsf;      // [F]
-  double* band;      // [n_pad][CVA_BAND], zero before the first pass
-  double* beta;      // [n_pad], zero before the first pass
-};
+// What cv_launch does for the gradient when it is given a CvAdjoint (sigp_cv_grad_ard; score_layout.hpp): the fold adjoints of each pass and
+// their assembly.
 
 // the first and the last fold whose window holds row x
 __device__ __forceinline__ int cva_first_fold(int x, int block, int gap) { return x >= gap ? (x - gap) / block : 0; }

@@ -17,19 +17,11 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_misc.hpp"
+#include "score_layout.hpp"
 
 namespace sigp {
 
-// Vector workspace of the pass (doubles, in the gradient workspace of sigp_loo_grad): a, beta, gamma, v [n_pad each], then eps.
-struct LooArdVecs {
-  double* base; long n_pad;
-  __host__ __device__ static long size(long n_pad) { return 4 * n_pad + 1; }
-  __host__ __device__ double* a() const { return base; }
-  __host__ __device__ double* beta() const { return base + n_pad; }
-  __host__ __device__ double* gamma() const { return base + 2 * n_pad; }
-  __host__ __device__ double* v() const { return base + 3 * n_pad; }
-  __host__ __device__ double* eps() const { return base + 4 * n_pad; }
-};
+// The vector workspace of the pass (in the gradient workspace of sigp_loo_grad), LooArdVecs: score_layout.hpp.
 
 // beta, gamma [n_pad] (zero from n on) and eps of the score `crit` (0 nlpd, 1 sse) in sigma mode `mode` (0 "refit", 1 "fixed"), one block:
 // g_i is the diagonal of P, q = y^T A~ comes from *q; s_i and var_i are formed as loo_rows_kernel / loo_grad_point_kernel form them.

@@ -16,23 +16,11 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_misc.hpp"
+#include "score_layout.hpp"
 
 namespace sigp {
 
-// Per-member vector workspace of the gradient pass (doubles): a, t, b (= P t), P a, sum_k P_ik^2 [n_pad each], the column pass's partial
-// sums [n_pad / 128][n_pad], the four gradient components.
-struct LooGradVecs {
-  double* base; long stride;        // member m at base + m * stride
-  long n_pad; int T;                // T = n_pad / 128 row chunks of the column pass
-  __host__ __device__ static long size(long n_pad) { return (5 + n_pad / 128) * n_pad + 4; }
-  __device__ double* a(int m) const { return base + m * stride; }
-  __device__ double* t(int m) const { return a(m) + n_pad; }
-  __device__ double* b(int m) const { return a(m) + 2 * n_pad; }
-  __device__ double* pa(int m) const { return a(m) + 3 * n_pad; }
-  __device__ double* pp(int m) const { return a(m) + 4 * n_pad; }
-  __device__ double* cpart(int m) const { return a(m) + 5 * n_pad; }
-  __device__ double* out(int m) const { return a(m) + (5 + T) * n_pad; }
-};
+// The per-member vector workspace of the gradient pass, LooGradVecs: score_layout.hpp.
 
 // P (the lower 128-tiles of U U^T) -> full symmetric: every element above the diagonal is its mirror image.  Grid (n_pad / 32, n_pad / 32,
 // member), 32 x 32 tiles through LDS so that both sides are coalesced; tile (bi, bj) with bi <= bj is written from tile (bj, bi).

@@ -31,6 +31,7 @@
 #include "ardgrad.hpp"
 #include "looard.hpp"
 #include "cvard.hpp"
+#include "score_layout.hpp"
 
 using namespace sigp;
 
@@ -38,6 +39,7 @@ namespace {
 
 constexpr int NB = 128;         // column-block width of the factorisation (= diagonal block)
 constexpr int RIDE = 128;       // rows of the ride-along block
+static_assert(NB == SL_BLK && RIDE == SL_BLK, "score_layout.hpp lays the workspaces out for these");
 constexpr int MAX_SLOTS = 16;
 
 struct ProfEvent { hipEvent_t a, b; int kclass; double flops; int K; };
@@ -1601,11 +1603,10 @@ int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const d
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad, ld = n_pad;
   const double sf = out[0];
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gD, &h->cap_gD, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, 4 * n_pad))) return rc;
-  if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)RIDE * n_pad))) return rc;
+  if ((rc = scores_ensure(h, 1, n_pad, MliiParts::size(n_pad)))) return rc;
+  if ((rc = scores_grad_ensure(h, 1, n_pad, 0))) return rc;
+  if ((rc = scores_mlii_ensure(h, (long)RIDE * n_pad, 1, n_pad, 0))) return rc;
+  const MliiParts mp{h->gPart};
   // U = L~^-T in gU, K~^-1 = U U^T on the lower 128-tiles of gK, A~ = L~^-T z = U z
   if ((rc = inv_factor(h, st, 1, s.mat, 0, s.dinv, 0, n_pad))) return rc;
   if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
@@ -1620,10 +1621,10 @@ int sigp_nlml_grad(sigp_handle* h, int kernel_id, const double theta[2], const d
     launch_kbuild<double>(h, grid, st, h->X, 0L, (int)h->dp, (int)h->d, (int)n, h->gD, 0L, ld, s.kps, 1);
     HIPCHK(h, hipGetLastError());
   }
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)n), dim3(256), 0, st, h->gK, h->gD, h->scratchZ, ld, (int)n, h->gPart);
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)n), dim3(256), 0, st, h->gK, h->gD, h->scratchZ, ld, (int)n, mp.rows());
   HIPCHK(h, hipGetLastError());
   std::vector<double> part((size_t)4 * n);
-  HIPCHK(h, hipMemcpyAsync(part.data(), h->gPart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(part.data(), mp.rows(), part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   double Td = 0, Qd = 0, trKinv = 0, aa = 0;   // T(D) = tr(K~^-1 D), Q(D) = A~^T D A~, tr(K~^-1), A~^T A~
   for (long i = 0; i < n; ++i) { Td += part[4 * i]; Qd += part[4 * i + 1]; trKinv += part[4 * i + 2]; aa += part[4 * i + 3]; }
@@ -1665,9 +1666,10 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
   int rc;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
   if (grad_mode != 0) {
-    if ((rc = scores_ensure(h, G, n_pad))) return rc;
-    if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)G * n_pad))) return rc;
+    if ((rc = scores_ensure(h, G, n_pad, MliiGroupParts::size(G, n_pad)))) return rc;
+    if ((rc = scores_mlii_ensure(h, (long)G * n_pad, G, n_pad, 0))) return rc;
   }
+  const MliiGroupParts mp{h->gPart, G, n_pad};
   std::vector<double> sums((size_t)G * 4);
   std::vector<int> ds((size_t)G);
   for (long g0 = 0; g0 < count; g0 += G) {
@@ -1687,12 +1689,11 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
       if ((rc = alpha_from_U(h, st, nb, s.mat + n_pad * ld, s.matStride, h->scratchZ, n_pad, n_pad))) return rc;
       // the derivative covariance for the on-the-fly dK~/dlog l (same data sets, same length scales)
       if ((rc = upload_dlogl_kparams(h, st, nb, kernel_id, ell.data(), ds.data()))) return rc;
-      double* part = h->gPart;                   // [nb][n_pad][4], then [nb][4]
       hipLaunchKernelGGL(grad_reduce_cov_kernel, dim3((unsigned)((n + GR_ROWS - 1) / GR_ROWS), (unsigned)nb), dim3(256), 0, st, (const double*)h->gK, n_pad * n_pad, ld,
-                         (const double*)h->scratchZ, n_pad, (const double*)h->bX, n_pad * dp, (int)dp, (int)d, (int)n, (const KParams*)h->gKps, part, 4 * n_pad);
-      hipLaunchKernelGGL(grad_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)part, 4 * n_pad, (int)n, part + (long)G * 4 * n_pad);
+                         (const double*)h->scratchZ, n_pad, (const double*)h->bX, n_pad * dp, (int)dp, (int)d, (int)n, (const KParams*)h->gKps, mp.rows(), mp.mstride());
+      hipLaunchKernelGGL(grad_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)mp.rows(), mp.mstride(), (int)n, mp.sums());
       HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(sums.data(), part + (long)G * 4 * n_pad, (size_t)nb * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(h, hipMemcpyAsync(sums.data(), mp.sums(), (size_t)nb * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     if ((rc = sync_slot(h, s))) return rc;
     for (int b = 0; b < nb; ++b) {
@@ -1718,17 +1719,17 @@ int sigp_nlml_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kerne
 // No U U^T, no dK~, no gD.  The factor, the ride rows and the fit's results are only read: sigp_predict / sigp_get_alpha
 // afterwards see what they saw before.  Profile class: SIGP_KC_MLII (trtri_levels and the row pass, one entry each).
 static int loo_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD,
-                      const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, int G) {
+                      const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, ScoreParts sp) {
   const long ld = n_pad;
   int rc;
   if ((rc = inv_factor(h, st, nb, Lm, sL, dinvp, sD, n_pad))) return rc;
   {
     ProfScope ps(h, st, SIGP_KC_MLII, nb * 2.0 * n * n, nb * 4.0 * n * n);
     hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4), (unsigned)nb), dim3(256), 0, st, (const double*)h->gU, ld, (int)n, Lm + n_pad * ld, y, q, mode,
-                       h->gPart, n_pad, n_pad * n_pad, sL, sY, sQ, 4 * n_pad, kps);
+                       sp.base, n_pad, n_pad * n_pad, sL, sY, sQ, sp.mstride(), kps);
     HIPCHK(h, hipGetLastError());
   }
-  hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)h->gPart, n_pad, 4 * n_pad, (int)n, h->gPart + (long)G * 4 * n_pad);
+  hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)sp.base, n_pad, sp.mstride(), (int)n, sp.sums());
   HIPCHK(h, hipGetLastError());
   return SIGP_OK;
 }
@@ -1744,10 +1745,11 @@ int sigp_loo(sigp_handle* h, int sigma_mode, double* mean, double* var, double* 
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad;
   int rc;
-  if ((rc = scores_ensure(h, 1, n_pad))) return rc;
-  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
-  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, h->gPart + 4 * n_pad + 2, 0, sigma_mode, 1))) return rc;
-  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
+  if ((rc = scores_ensure(h, 1, n_pad, ScoreParts::size(1, n_pad)))) return rc;
+  const ScoreParts sp{h->gPart, 1, n_pad};
+  if ((rc = scores_stage_q(h, st, sp))) return rc;
+  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, sp.q(), 0, sigma_mode, sp))) return rc;
+  if ((rc = scores_to_host(h, st, n, sp, mean, var, score))) return rc;
   return sync_slot(h, s);
 }
 
@@ -1770,13 +1772,14 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
-  if ((rc = scores_ensure(h, G, n_pad))) return rc;
+  if ((rc = scores_ensure(h, G, n_pad, ScoreParts::size(G, n_pad)))) return rc;
+  const ScoreParts sp{h->gPart, G, n_pad};
   std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
     if ((rc = batch_group_fit(h, s, nb, kernel_id, ell + g0, sn_tilde + g0, first + g0))) return rc;
-    if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G))) return rc;
-    if ((rc = batch_scores_fetch(h, st, nb, G, n_pad, mean ? mv.data() : nullptr, sc.data()))) return rc;
+    if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, sp))) return rc;
+    if ((rc = batch_scores_fetch(h, st, nb, sp, mean ? mv.data() : nullptr, sc.data()))) return rc;
     if ((rc = sync_slot(h, s))) return rc;
     for (int b = 0; b < nb; ++b)
       batch_scores_scatter(g0 + b, s.info_host[b] == 0, &sc[(size_t)2 * b], mean ? &mv[(size_t)b * 2 * n_pad] : nullptr, n, n_pad, mean, var, nstride, score);

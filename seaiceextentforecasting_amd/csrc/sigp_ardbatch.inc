@@ -11,17 +11,12 @@
 // gradient's work SIGP_KC_MLII.  Out of scope: ARD gradients of the leave-one-out / leave-block-out scores for groups, sigp_small_*, the
 // fp32 engine, sharded fits.  Included inside extern "C" of sigp.hip, after sigp_ardgrad.inc.
 
-// the staging area of slot s (sized for its capacity, so a later, larger group of the same call never reallocates it) and its parts
-struct ArdStage {
-  double *X, *Xs, *y, *div, *sn;      // [cap][n_pad][dp], [cap][RIDE][dp], [cap][n_pad], divisors [cap][dp], sn~ [cap]
-  long cap;
-};
+// the staging area of slot s (ArdStage, score_layout.hpp), sized for the slot's capacity
 static int ard_stage_ensure(sigp_handle* h, const Slot& s, ArdStage* a) {
   const long cap = s.capB, n_pad = h->b_npad, dp = h->b_dp;
   int rc;
-  if ((rc = ensure(h, &h->bStage, &h->cap_bStage, cap * ((n_pad + RIDE) * dp + n_pad + dp + 1)))) return rc;
-  a->cap = cap;
-  a->X = h->bStage; a->Xs = a->X + cap * n_pad * dp; a->y = a->Xs + cap * (long)RIDE * dp; a->div = a->y + cap * n_pad; a->sn = a->div + cap * dp;
+  if ((rc = ensure(h, &h->bStage, &h->cap_bStage, ArdStage::size(cap, n_pad, dp)))) return rc;
+  *a = ArdStage::at(h->bStage, cap, n_pad, dp);
   return SIGP_OK;
 }
 
@@ -108,17 +103,14 @@ int sigp_nlml_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int k
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
   hipStream_t st = s.s_upd;
   h->nslots = std::max(h->nslots, 1);
-  // every buffer before the first launch: growing one of them later would drop what the earlier launches left in it
   ArdStage a;
   if ((rc = ard_stage_ensure(h, s, &a))) return rc;
   if (grad_mode != 0) {
-    if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
-    if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
-    if ((rc = ensure(h, &h->gPart, &h->cap_gPart, (long)G * (ntiles * dp + d + 1)))) return rc;
-    if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)G * n_pad))) return rc;
-    if ((rc = ensure(h, &h->ardXc, &h->cap_ardXc, (long)G * n_pad * dp))) return rc;
+    if ((rc = scores_ensure(h, G, n_pad, ArdParts::size(G, ntiles, dp, d + 1)))) return rc;
+    if ((rc = scores_mlii_ensure(h, (long)G * n_pad, G, n_pad, dp))) return rc;
   }
-  const ArdMemberStrides ms{n_pad * dp, n_pad * n_pad, n_pad, 512, ntiles * dp};
+  const ArdParts ap{h->gPart, G, ntiles, dp, d + 1};
+  const ArdMemberStrides ms{n_pad * dp, n_pad * n_pad, n_pad, 512, ap.mstride()};
   std::vector<double> hdiv((size_t)(a.cap * (dp + 1))), one((size_t)G, 1.0), ell((size_t)G * d), snt((size_t)G), gh((size_t)G * (d + 1));
   std::vector<int> ds((size_t)G);
   std::vector<char> ok((size_t)G);
@@ -149,13 +141,13 @@ int sigp_nlml_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int k
       if ((rc = kinv_lower(h, st, nb, n_pad))) return rc;
       if ((rc = alpha_from_U(h, st, nb, s.mat + n_pad * ld, s.matStride, h->scratchZ, n_pad, n_pad))) return rc;
       // the one pass over every member's K~^-1 and the fixed-order sums, one launch each (q = y^T A~ in the slot's result rows)
-      double* partial = h->gPart;
-      double* gdev = h->gPart + (long)G * ntiles * dp;
+      double* partial = ap.partial();
+      double* gdev = ap.grad();
       {
         ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 30)), nb * (4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp)));
         if ((rc = ard_tile_pass_members<ARD_W_NLML>(h, st, nb, a.X, n, d, dp, n_pad, ms, kernel_id, h->gK, ld, h->scratchZ, s.res, nullptr, nullptr, partial))) return rc;
         hipLaunchKernelGGL(ard_grad_finish_kernel, dim3((unsigned)(d + 1), (unsigned)nb), dim3(256), 0, st, (const double*)partial, ntiles, (int)dp, (int)d, (int)n,
-                           (const double*)h->gK, ld, (const double*)h->scratchZ, (const double*)s.res, 0.0, gdev, ms, d + 1, (const double*)a.sn);
+                           (const double*)h->gK, ld, (const double*)h->scratchZ, (const double*)s.res, 0.0, gdev, ms, ap.gw, (const double*)a.sn);
         HIPCHK(h, hipGetLastError());
       }
       HIPCHK(h, hipMemcpyAsync(gh.data(), gdev, (size_t)nb * (d + 1) * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -78,18 +78,16 @@ int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64
   hipStream_t st = s.s_upd;
   const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ld = n_pad;
   const long ntiles = kbuild_tiles(n_pad);
-  if ((rc = ensure(h, &h->gU, &h->cap_gU, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gK, &h->cap_gK, n_pad * n_pad))) return rc;
-  if ((rc = ensure(h, &h->gPart, &h->cap_gPart, ntiles * dp + dp + 1))) return rc;
-  if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, (long)RIDE * n_pad))) return rc;
-  if ((rc = ensure(h, &h->ardXc, &h->cap_ardXc, n_pad * dp))) return rc;
+  if ((rc = scores_ensure(h, 1, n_pad, ArdParts::size(1, ntiles, dp, dp + 1)))) return rc;
+  if ((rc = scores_mlii_ensure(h, (long)RIDE * n_pad, 1, n_pad, dp))) return rc;
+  const ArdParts ap{h->gPart, 1, ntiles, dp, dp + 1};
   // U = L~^-T, K~^-1 = U U^T (lower 128-tiles in gK), A~ = U z: the route of sigp_nlml_grad
   if ((rc = inv_factor(h, st, 1, s.mat, 0, s.dinv, 0, n_pad))) return rc;
   if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
   if ((rc = alpha_from_U(h, st, 1, s.mat + n_pad * ld, 0, h->scratchZ, 0, n_pad))) return rc;
   // the one pass: every tile's share of all d components, then the fixed-order sums (s.res[0] = y^T A~ of the fit just made)
-  double* partial = h->gPart;
-  double* gdev = h->gPart + ntiles * dp;
+  double* partial = ap.partial();
+  double* gdev = ap.grad();
   {
     ProfScope ps(h, st, SIGP_KC_MLII, (double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 30), 4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp));
     if ((rc = ard_tile_pass<ARD_W_NLML>(h, st, kernel_id, h->gK, ld, h->scratchZ, s.res, nullptr, nullptr, partial))) return rc;

@@ -7,7 +7,7 @@
 //   score                          loo_sum_kernel over the n terms
 //
 // Only reads the factor, the ride rows and the fit's state.  Folds are worked off in passes of at most CV_PASS_BLOCKS (member, fold) pairs,
-// which bounds the workspaces whatever n / block is (doubles): cvPart pairs S (wp^2 + wp), cvBlk 2 pairs 128^2, cvVec pairs (128 + 1).
+// which bounds the workspaces whatever n / block is (CvWork, score_layout.hpp).
 
 constexpr long CV_PASS_BLOCKS = 1024;
 
@@ -32,28 +32,42 @@ static int cv_slices(const sigp_handle* h, long folds, long n) {
   return (int)std::max(1L, std::min(S, nch));
 }
 
-// the launcher the single and the lockstep entry points share (arguments as loo_launch); results in h->gPart laid out as loo_launch leaves them.
+// The work buffers of a pass over a group of nb members: FP = blocks / nb folds of each.  The layout depends on nb, so every group lays its own
+// view over the arenas ...
+static CvWork cv_work(const sigp_handle* h, int nb, long n, long block, long gap) {
+  const long F = (n + block - 1) / block;
+  const long FP = std::max<long>(1, std::min<long>(F, CV_PASS_BLOCKS / nb));
+  return CvWork{h->cvPart, h->cvBlk, h->cvVec, FP * nb, cv_slices(h, std::min<long>(F, CV_PASS_BLOCKS), n), round_up(std::min<long>(n, block + 2 * gap), 16)};
+}
+
+// ... which the entry grows for the groups it will run: of G members and, with tail > 0, a last one of `tail`
+static int cv_work_ensure(sigp_handle* h, long n, long block, long gap, int G, int tail) {
+  int rc;
+  for (int nb : {G, tail}) {
+    if (nb < 1) continue;
+    const CvWork w = cv_work(h, nb, n, block, gap);
+    if ((rc = ensure(h, &h->cvPart, &h->cap_cvPart, CvWork::part_size(w.blocks, w.S, w.wp)))) return rc;
+    if ((rc = ensure(h, &h->cvBlk, &h->cap_cvBlk, CvWork::blk_size(w.blocks)))) return rc;
+    if ((rc = ensure(h, &h->cvVec, &h->cap_cvVec, CvWork::vec_size(w.blocks)))) return rc;
+  }
+  return SIGP_OK;
+}
+
+// the launcher the single and the lockstep entry points share (arguments as loo_launch; cw = cv_work of this nb); results in sp as loo_launch leaves them.
 // adj (sigp_cv_grad_ard, nb = 1 only; cvard.hpp): after every pass's closing solves, the fold adjoints of that pass and their assembly
 // into adj->band / adj->beta -- Xb and av are overwritten by the next pass.  With adj = nullptr the launches are those of sigp_cv.
 static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD,
-                     const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, int G, int block, int gap,
+                     const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, ScoreParts sp, CvWork cw, int block, int gap,
                      const CvAdjoint* adj = nullptr) {
   const long ld = n_pad;
   const long F = (n + block - 1) / block;
-  const int wmax = (int)std::min<long>(n, (long)block + 2L * gap), wp = (int)round_up(wmax, 16);
-  const long FP = std::max<long>(1, std::min<long>(F, CV_PASS_BLOCKS / nb)), blocks = FP * nb;
-  const int S = cv_slices(h, std::min<long>(F, CV_PASS_BLOCKS), n);
+  const int wmax = (int)std::min<long>(n, (long)block + 2L * gap), wp = (int)cw.wp;
+  const long FP = cw.blocks / nb;
+  const int S = (int)cw.S;
   h->cv_slices_used = S;
   int rc;
-  if ((rc = ensure(h, &h->cvPart, &h->cap_cvPart, blocks * S * ((long)wp * wp + wp)))) return rc;
-  if ((rc = ensure(h, &h->cvBlk, &h->cap_cvBlk, 2 * blocks * CV_MAXW * CV_MAXW))) return rc;
-  if ((rc = ensure(h, &h->cvVec, &h->cap_cvVec, blocks * (CV_MAXW + 1)))) return rc;
-  double* part = h->cvPart;
-  double* apart = part + blocks * S * (long)wp * wp;
-  double* Pb = h->cvBlk;
-  double* Xb = Pb + blocks * CV_MAXW * CV_MAXW;
-  double* av = h->cvVec;
-  int* info = (int*)(av + blocks * CV_MAXW);
+  double *part = cw.part(), *apart = cw.apart(), *Pb = cw.Pb(), *Xb = cw.Xb(), *av = cw.av();
+  int* info = cw.info();
   if ((rc = inv_factor(h, st, nb, Lm, sL, dinvp, sD, n_pad))) return rc;
   static AttrOnce d_attr;
   HIPCHK(h, d_attr.set(h->device, (const void*)potrf_diag_kernel<double>, DIAG_LDS_BYTES));
@@ -82,7 +96,7 @@ static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad,
     {
       ProfScope ps(h, st, SIGP_KC_MLII, wf * 2.0 * wmax * wmax, wf * 8.0 * wmax * wmax);
       hipLaunchKernelGGL(cv_close_kernel, dim3(nf, (unsigned)nb), dim3(256), 0, st, (const double*)Xb, (const double*)av, (const int*)info, y, sY, kps, q, sQ, mode,
-                         (int)n, block, gap, (int)f0, h->gPart, n_pad, 4 * n_pad);
+                         (int)n, block, gap, (int)f0, sp.base, n_pad, sp.mstride());
       HIPCHK(h, hipGetLastError());
     }
     if (adj && nb == 1) {
@@ -108,7 +122,7 @@ static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad,
       }
     }
   }
-  hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)h->gPart, n_pad, 4 * n_pad, (int)n, h->gPart + (long)G * 4 * n_pad);
+  hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)sp.base, n_pad, sp.mstride(), (int)n, sp.sums());
   HIPCHK(h, hipGetLastError());
   return SIGP_OK;
 }
@@ -126,10 +140,12 @@ int sigp_cv(sigp_handle* h, int64_t block, int64_t gap, int sigma_mode, double* 
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad;
   int rc;
-  if ((rc = scores_ensure(h, 1, n_pad))) return rc;
-  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
-  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, h->gPart + 4 * n_pad + 2, 0, sigma_mode, 1, (int)block, (int)gap))) return rc;
-  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
+  if ((rc = scores_ensure(h, 1, n_pad, ScoreParts::size(1, n_pad)))) return rc;
+  if ((rc = cv_work_ensure(h, n, block, gap, 1, 0))) return rc;
+  const ScoreParts sp{h->gPart, 1, n_pad};
+  if ((rc = scores_stage_q(h, st, sp))) return rc;
+  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, sp.q(), 0, sigma_mode, sp, cv_work(h, 1, n, block, gap), (int)block, (int)gap))) return rc;
+  if ((rc = scores_to_host(h, st, n, sp, mean, var, score))) return rc;
   return sync_slot(h, s);
 }
 
@@ -152,13 +168,15 @@ int sigp_cv_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, c
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
-  if ((rc = scores_ensure(h, G, n_pad))) return rc;
+  if ((rc = scores_ensure(h, G, n_pad, ScoreParts::size(G, n_pad)))) return rc;
+  if ((rc = cv_work_ensure(h, n, block, gap, G, (int)(count % G)))) return rc;
+  const ScoreParts sp{h->gPart, G, n_pad};
   std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
     if ((rc = batch_group_fit(h, s, nb, kernel_id, ell + g0, sn_tilde + g0, first + g0))) return rc;
-    if ((rc = cv_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G, (int)block, (int)gap))) return rc;
-    if ((rc = batch_scores_fetch(h, st, nb, G, n_pad, mean ? mv.data() : nullptr, sc.data()))) return rc;
+    if ((rc = cv_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, sp, cv_work(h, nb, n, block, gap), (int)block, (int)gap))) return rc;
+    if ((rc = batch_scores_fetch(h, st, nb, sp, mean ? mv.data() : nullptr, sc.data()))) return rc;
     if ((rc = sync_slot(h, s))) return rc;
     for (int b = 0; b < nb; ++b) {
       // a member whose K~ is not SPD, or one of whose P_SS failed its pivot test (+inf terms in its sums): +inf scores, NaN rows

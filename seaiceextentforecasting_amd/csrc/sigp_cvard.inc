@@ -41,23 +41,21 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
   const long F = (n + block - 1) / block, FP = std::min<long>(F, CV_PASS_BLOCKS);
   const long wp = round_up(std::min<long>(n, block + 2 * gap), 16);
   if ((rc = ard_scores_ensure(h, grad != nullptr))) return rc;
+  if ((rc = cv_work_ensure(h, n, block, gap, 1, 0))) return rc;
+  if (grad && (rc = ensure(h, &h->cvAdj, &h->cap_cvAdj, CvAdjStore::size(n_pad, FP, wp, F)))) return rc;
+  const ScoreArdParts ap{h->gPart, n_pad, kbuild_tiles(n_pad), h->dp};   // the scores as sigp_cv has them; then the tile pass's partials and the gradient
+  const ScoreParts sp = ap.scores();
+  const LooArdVecs w{h->gV, n_pad};
   CvAdjoint adj{};
-  if (grad && (rc = ensure(h, &h->cvAdj, &h->cap_cvAdj, n_pad * CVA_BAND + FP * (wp * wp + wp) + F))) return rc;   // (also before the first launch)
-  LooArdVecs w{h->gV, n_pad};
   if (grad) {
-    adj.crit = criterion;
-    adj.band = h->cvAdj;
-    adj.Bf = adj.band + n_pad * CVA_BAND;
-    adj.betaf = adj.Bf + FP * wp * wp;
-    adj.epsf = adj.betaf + FP * wp;
-    adj.beta = w.beta();
+    adj = CvAdjStore{h->cvAdj, n_pad, FP, wp, F}.adjoint(criterion, w.beta());
     HIPCHK(h, hipMemsetAsync(adj.band, 0, (size_t)n_pad * CVA_BAND * sizeof(double), st));
     HIPCHK(h, hipMemsetAsync(adj.beta, 0, (size_t)n_pad * sizeof(double), st));
   }
-  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~, as sigp_cv; then the tile pass's partials and the gradient
-  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
-  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1, (int)block, (int)gap, grad ? &adj : nullptr))) return rc;
-  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
+  if ((rc = scores_stage_q(h, st, sp))) return rc;
+  if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, sp.q(), 0, sigma_mode, sp, cv_work(h, 1, n, block, gap), (int)block, (int)gap,
+                      grad ? &adj : nullptr))) return rc;
+  if ((rc = scores_to_host(h, st, n, sp, mean, var, score))) return rc;
   // a fold whose P_SS failed its pivot test left +inf in both sums
   auto finish = [&]() -> int {
     if ((rc = sync_slot(h, s))) return rc;
@@ -86,6 +84,6 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
     ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * (n_pad + NB), 0.0);
     if ((rc = syrk_set(h, st, 1, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
   }
-  if ((rc = loo_ard_pass(h, st, kernel_id, w, snt, grad))) return rc;
+  if ((rc = loo_ard_pass(h, st, kernel_id, w, ap, snt, grad))) return rc;
   return finish();
 }

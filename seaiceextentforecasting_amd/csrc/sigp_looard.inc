@@ -15,12 +15,11 @@
 // Out of scope: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits.  The leave-block-out scores: sigp_cvard.inc.
 
 // The ARD pass of a leave-one-out / leave-block-out score (sigp_cv_grad_ard shares it) over M in gU with the vectors w: every tile's share of
-// all d components, then the fixed-order sums; the gradient [d + 1] on its way to the caller.  The partials [tiles][dp] and the gradient lie
-// behind gPart's tail (score [2], q, one spare).
-static int loo_ard_pass(sigp_handle* h, hipStream_t st, int kernel_id, LooArdVecs w, double snt, double* grad) {
-  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ntiles = kbuild_tiles(n_pad);
-  double* partial = h->gPart + 4 * n_pad + 4;
-  double* gdev = partial + ntiles * dp;
+// all d components, then the fixed-order sums; the gradient [d + 1] on its way to the caller.  The partials and the gradient lie in ap.
+static int loo_ard_pass(sigp_handle* h, hipStream_t st, int kernel_id, LooArdVecs w, ScoreArdParts ap, double snt, double* grad) {
+  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ntiles = ap.tiles;
+  double* partial = ap.partial();
+  double* gdev = ap.grad();
   int rc;
   {
     ProfScope ps(h, st, SIGP_KC_MLII, (double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 36), 4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp));
@@ -51,19 +50,20 @@ int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad, ld = n_pad;
   if ((rc = ard_scores_ensure(h, grad != nullptr))) return rc;
-  double* tail = h->gPart + 4 * n_pad;              // score [2], then q = y^T A~, as sigp_loo; then the tile pass's partials and the gradient
-  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
-  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, tail + 2, 0, sigma_mode, 1))) return rc;
-  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
+  const ScoreArdParts ap{h->gPart, n_pad, kbuild_tiles(n_pad), h->dp};   // the scores as sigp_loo has them; then the tile pass's partials and the gradient
+  const ScoreParts sp = ap.scores();
+  const LooArdVecs w{h->gV, n_pad};
+  if ((rc = scores_stage_q(h, st, sp))) return rc;
+  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, sp.q(), 0, sigma_mode, sp))) return rc;
+  if ((rc = scores_to_host(h, st, n, sp, mean, var, score))) return rc;
   if (!grad) return sync_slot(h, s);
 
-  LooArdVecs w{h->gV, n_pad};
   if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
   {   // a = U z;  P -> full;  beta, gamma, eps;  v = P beta and P Gamma
     ProfScope ps(h, st, SIGP_KC_MLII, 4.0 * n_pad * n_pad, 36.0 * n_pad * n_pad);
     if ((rc = alpha_from_U(h, st, 1, s.mat + n_pad * ld, 0, w.a(), 0, n_pad))) return rc;
     if ((rc = mirror_P(h, st, 1, n_pad))) return rc;
-    hipLaunchKernelGGL(loo_ard_coef_kernel, dim3(1), dim3(256), 0, st, (const double*)h->gK, ld, (int)n, (int)n_pad, (const double*)(tail + 2), sigma_mode, criterion, w);
+    hipLaunchKernelGGL(loo_ard_coef_kernel, dim3(1), dim3(256), 0, st, (const double*)h->gK, ld, (int)n, (int)n_pad, (const double*)sp.q(), sigma_mode, criterion, w);
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(loo_ard_scale_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, st, (const double*)h->gK, h->gD, ld, (int)n, (int)n_pad, w);
     HIPCHK(h, hipGetLastError());
@@ -72,6 +72,6 @@ int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_
     ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * (n_pad + NB), 0.0);
     if ((rc = syrk_set(h, st, 1, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
   }
-  if ((rc = loo_ard_pass(h, st, kernel_id, w, snt, grad))) return rc;
+  if ((rc = loo_ard_pass(h, st, kernel_id, w, ap, snt, grad))) return rc;
   return sync_slot(h, s);
 }

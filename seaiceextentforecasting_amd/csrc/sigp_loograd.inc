@@ -15,10 +15,9 @@
 // Out of scope: gradients in sigp_small_run_loo (the one-workgroup LDS kernel), sharded fits, the fp32 engine.  Gradients with respect to
 // per-feature length scales: sigp_loo_grad_ard (sigp_looard.inc).
 
-// every buffer before the first launch: growing one of them later would drop what the earlier launches left in it
 static int loo_grad_ensure(sigp_handle* h, int G, long n_pad) {
   int rc;
-  if ((rc = scores_ensure(h, G, n_pad))) return rc;
+  if ((rc = scores_ensure(h, G, n_pad, ScoreParts::size(G, n_pad)))) return rc;
   return scores_grad_ensure(h, G, n_pad, LooGradVecs::size(n_pad));
 }
 
@@ -82,20 +81,21 @@ int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t 
   const long n = h->n, n_pad = h->n_pad, ld = n_pad;
   int rc;
   if ((rc = loo_grad_ensure(h, 1, n_pad))) return rc;
-  const double* q = h->gPart + 4 * n_pad + 2;       // gPart's tail: score [2], then q = y^T A~, as sigp_loo
-  if ((rc = scores_stage_q(h, st, n_pad))) return rc;
-  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, q, 0, sigma_mode, 1))) return rc;
+  const ScoreParts sp{h->gPart, 1, n_pad};
+  const LooGradVecs v{h->gV, LooGradVecs::size(n_pad), n_pad, (int)(n_pad / NB)};
+  const double* q = sp.q();
+  if ((rc = scores_stage_q(h, st, sp))) return rc;
+  if ((rc = loo_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, q, 0, sigma_mode, sp))) return rc;
   if (refk) {
     if ((rc = build_xsxt(h, MSigma, ldsigma, h->gD))) return rc;     // X (M Sigma~) X^T = dK~/dl
   } else {
     const int ds0 = 0;
     if ((rc = loo_grad_build_dlogl(h, st, 1, h->kernel_id, &h->ell, &ds0, h->X, 0L, n, h->d, h->dp, n_pad))) return rc;
   }
-  LooGradVecs v{h->gV, LooGradVecs::size(n_pad), n_pad, (int)(n_pad / NB)};
   if ((rc = loo_grad_launch(h, st, 1, n, n_pad, s.mat + n_pad * ld, 0, q, 0, sigma_mode, v))) return rc;
   double g4[4];
-  if ((rc = scores_to_host(h, st, n, n_pad, mean, var, score))) return rc;
-  HIPCHK(h, hipMemcpyAsync(g4, h->gV + (5 + n_pad / NB) * n_pad, sizeof g4, hipMemcpyDeviceToHost, st));
+  if ((rc = scores_to_host(h, st, n, sp, mean, var, score))) return rc;
+  HIPCHK(h, hipMemcpyAsync(g4, v.out(0), sizeof g4, hipMemcpyDeviceToHost, st));
   if ((rc = sync_slot(h, s))) return rc;
   const double scale1 = refk ? h->ell : 1.0;        // dK~/dlog l = l X (M Sigma~) X^T
   grad[0] = scale1 * g4[0]; grad[1] = h->sn_tilde * g4[1];
@@ -122,18 +122,19 @@ int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
   hipStream_t st = s.s_upd;
   if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
   if ((rc = loo_grad_ensure(h, G, n_pad))) return rc;
-  LooGradVecs v{h->gV, LooGradVecs::size(n_pad), n_pad, (int)(n_pad / NB)};
+  const ScoreParts sp{h->gPart, G, n_pad};
+  const LooGradVecs v{h->gV, LooGradVecs::size(n_pad), n_pad, (int)(n_pad / NB)};
   std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2), g4((size_t)G * 4);
   std::vector<int> ds((size_t)G);
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
     for (int b = 0; b < nb; ++b) ds[(size_t)b] = (int)((first + g0 + b) % h->b_count);
     if ((rc = batch_group_fit(h, s, nb, kernel_id, ell + g0, sn_tilde + g0, first + g0))) return rc;
-    if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, G))) return rc;
+    if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, h->by, n_pad, s.kps, s.res, 512, sigma_mode, sp))) return rc;
     if ((rc = loo_grad_build_dlogl(h, st, nb, kernel_id, ell + g0, ds.data(), h->bX, n_pad * dp, n, d, dp, n_pad))) return rc;
     if ((rc = loo_grad_launch(h, st, nb, n, n_pad, s.mat + n_pad * ld, s.matStride, s.res, 512, sigma_mode, v))) return rc;
-    if ((rc = batch_scores_fetch(h, st, nb, G, n_pad, mean ? mv.data() : nullptr, sc.data()))) return rc;
-    HIPCHK(h, hipMemcpy2DAsync(g4.data(), 4 * sizeof(double), h->gV + (5 + n_pad / NB) * n_pad, (size_t)v.stride * sizeof(double), 4 * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
+    if ((rc = batch_scores_fetch(h, st, nb, sp, mean ? mv.data() : nullptr, sc.data()))) return rc;
+    HIPCHK(h, hipMemcpy2DAsync(g4.data(), 4 * sizeof(double), v.out(0), (size_t)v.stride * sizeof(double), 4 * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
     if ((rc = sync_slot(h, s))) return rc;
     for (int b = 0; b < nb; ++b) {
       const long i = g0 + b;

@@ -2,25 +2,32 @@
 // and sigp_cv_grad_ard.  Included inside extern "C" of sigp.hip, before sigp_nlml_grad.  Host code only: each launch sequence is written
 // once here and the entry points call the steps in order.  Every step takes the number of lockstep members nb; a single fit is nb = 1.
 //
-// Workspaces (per member, strides in doubles): gU [n_pad][n_pad] holds U = L~^-T, gK [n_pad][n_pad] parks the inversion's products and then
-// holds P = K~^-1, both with member stride n_pad^2.  gPart: per member [4][n_pad] (mean, var and the two rows of score terms, member stride
-// 4 n_pad), then -- behind the rows of the G members the workspace was sized for, NOT of the nb members present -- 4 G doubles of sums: the
-// score entries' [G][2], sigp_nlml_grad_batch's [G][4]; a single fit (G = 1): score [2], then q = y^T A~.
+// Workspaces: gU [n_pad][n_pad] holds U = L~^-T, gK [n_pad][n_pad] parks the inversion's products and then holds P = K~^-1, both with member
+// stride n_pad^2.  Every other arena's layout: score_layout.hpp.
 
 // ---- workspaces ------------------------------------------------------------------------------------------------------------------------------
-// the score entries' buffers for G lockstep members; `extra` doubles behind gPart's sums (the tile partials of a per-feature gradient pass)
-static int scores_ensure(sigp_handle* h, int G, long n_pad, long extra = 0) {
+// An entry point grows every buffer it will touch here, before its first launch, and builds its views afterwards: growing a buffer later
+// would drop what the earlier launches left in it, and the launch helpers below take views and grow nothing.
+// gU and gK for G lockstep members, and gPart for the view the entry lays over it (`parts` = that view's size)
+static int scores_ensure(sigp_handle* h, int G, long n_pad, long parts) {
   int rc;
   if ((rc = ensure(h, &h->gU, &h->cap_gU, (long)G * n_pad * n_pad))) return rc;
   if ((rc = ensure(h, &h->gK, &h->cap_gK, (long)G * n_pad * n_pad))) return rc;
-  return ensure(h, &h->gPart, &h->cap_gPart, (long)G * (4 * n_pad + 4) + extra);
+  return ensure(h, &h->gPart, &h->cap_gPart, parts);
 }
 
-// ... and what a gradient pass adds: the second matrix operand gD and gvec doubles of vectors per member
+// ... and what a gradient pass adds: the second matrix operand gD and gvec doubles of vectors per member (0: none)
 static int scores_grad_ensure(sigp_handle* h, int G, long n_pad, long gvec) {
   int rc;
   if ((rc = ensure(h, &h->gD, &h->cap_gD, (long)G * n_pad * n_pad))) return rc;
   return ensure(h, &h->gV, &h->cap_gV, (long)G * gvec);
+}
+
+// ... the MLII entries: a = U z in scratchZ (zlen doubles), and for a per-feature gradient the centred features [G][n_pad][dp] in ardXc (dp = 0: none)
+static int scores_mlii_ensure(sigp_handle* h, long zlen, int G, long n_pad, long dp) {
+  int rc;
+  if ((rc = ensure(h, &h->scratchZ, &h->cap_Z, zlen))) return rc;
+  return ensure(h, &h->ardXc, &h->cap_ardXc, (long)G * n_pad * dp);
 }
 
 // ---- the cubic steps -------------------------------------------------------------------------------------------------------------------------
@@ -132,32 +139,31 @@ static int ard_all_inf(sigp_handle* h, double* score, double* grad, double* mean
   return SIGP_NOT_SPD;
 }
 
-// sigp_loo_grad_ard / sigp_cv_grad_ard: the single fit's score buffers with room for the tile pass's partials and the gradient behind them, and
-// for a gradient gD, the vectors and the centred features.  Every buffer before the first launch: growing one of them later would drop what
-// the earlier launches left in it.
+// sigp_loo_grad_ard / sigp_cv_grad_ard: the single fit's score buffers (without a gradient: ScoreParts of one member; ScoreArdParts begins with
+// them) and, for a gradient, gD, the vectors and the centred features
 static int ard_scores_ensure(sigp_handle* h, bool grad) {
   const long n_pad = h->n_pad, dp = h->dp;
   int rc;
-  if ((rc = scores_ensure(h, 1, n_pad, grad ? kbuild_tiles(n_pad) * dp + dp + 1 : 0))) return rc;
+  if ((rc = scores_ensure(h, 1, n_pad, grad ? ScoreArdParts::size(n_pad, kbuild_tiles(n_pad), dp) : ScoreParts::size(1, n_pad)))) return rc;
   if (!grad) return SIGP_OK;
   if ((rc = scores_grad_ensure(h, 1, n_pad, LooArdVecs::size(n_pad)))) return rc;
   return ensure(h, &h->ardXc, &h->cap_ardXc, n_pad * dp);
 }
 
-// ---- single fits: the tail of gPart and the read-back -------------------------------------------------------------------------------------
-// behind the one member's rows: score [2], then q = y^T A~ -- the host copy of the fit's epilogue (s.res may have moved on)
-static int scores_stage_q(sigp_handle* h, hipStream_t st, long n_pad) {
-  HIPCHK(h, hipMemcpyAsync(h->gPart + 4 * n_pad + 2, h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
+// ---- single fits: q and the read-back ------------------------------------------------------------------------------------------------------
+// q = y^T A~ behind the one member's scores -- the host copy of the fit's epilogue (s.res may have moved on)
+static int scores_stage_q(sigp_handle* h, hipStream_t st, ScoreParts sp) {
+  HIPCHK(h, hipMemcpyAsync(sp.q(), h->fit_res.data(), sizeof(double), hipMemcpyHostToDevice, st));
   return SIGP_OK;
 }
 
 // mean, var [n] (may be NULL together) and score [2] on their way to the caller; complete after sync_slot
-static int scores_to_host(sigp_handle* h, hipStream_t st, long n, long n_pad, double* mean, double* var, double* score) {
+static int scores_to_host(sigp_handle* h, hipStream_t st, long n, ScoreParts sp, double* mean, double* var, double* score) {
   if (mean) {
-    HIPCHK(h, hipMemcpyAsync(mean, h->gPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(var, h->gPart + n_pad, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(mean, sp.mean(0), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(var, sp.var(0), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
   }
-  HIPCHK(h, hipMemcpyAsync(score, h->gPart + 4 * n_pad, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(score, sp.sums(), 2 * sizeof(double), hipMemcpyDeviceToHost, st));
   return SIGP_OK;
 }
 
@@ -190,11 +196,11 @@ static int batch_group_fit(sigp_handle* h, Slot& s, int nb, int kernel_id, const
   return batch_group_fit_on(h, s, nb, kernel_id, ell, snt, ds.data(), h->bX, h->by, h->bXs, 0);
 }
 
-// a group's rows (mv [nb][2][n_pad] <- mean, var; NULL: none) and sums (sc [nb][2]) on their way to the host: the sums lie behind the rows of
-// all G members the workspace is laid out for, whatever nb is
-static int batch_scores_fetch(sigp_handle* h, hipStream_t st, int nb, int G, long n_pad, double* mv, double* sc) {
-  if (mv) HIPCHK(h, hipMemcpy2DAsync(mv, (size_t)2 * n_pad * sizeof(double), h->gPart, (size_t)4 * n_pad * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(sc, h->gPart + (long)G * 4 * n_pad, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+// a group's rows (mv [nb][2][n_pad] <- mean, var; NULL: none) and sums (sc [nb][2]) on their way to the host, nb <= sp.G
+static int batch_scores_fetch(sigp_handle* h, hipStream_t st, int nb, ScoreParts sp, double* mv, double* sc) {
+  const long n_pad = sp.n_pad;
+  if (mv) HIPCHK(h, hipMemcpy2DAsync(mv, (size_t)2 * n_pad * sizeof(double), sp.mean(0), (size_t)sp.mstride() * sizeof(double), (size_t)2 * n_pad * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(sc, sp.sums(), (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
   return SIGP_OK;
 }
 
