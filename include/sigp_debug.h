@@ -25,6 +25,38 @@ int sigp_debug_time_syrk(sigp_handle* h, int rt, int K, int patch, int small, in
 int sigp_debug_stream_concurrency(sigp_handle* h, int nstreams, int reps, int blocks, int iters, int use_slot_streams, double* ms_out);
 /* which CUs does a hipExtStreamCreateWithCUMask mask enable? out2[2*b] = XCC_ID, out2[2*b+1] = HW_ID of block b (tools/cumask_probe.py) */
 int sigp_debug_cumask_probe(sigp_handle* h, const unsigned* mask8, int blocks, unsigned* out2);
+
+/*
+ * Run-and-return entries (tests/test_hip_tile_primitives.py): the caller's HOST operands go to the device, exactly ONE launch is issued
+ * through the launcher the engine uses (no ablation bits, no stamps, plain tile walk), and the output buffer comes back WHOLE, so that
+ * gaps and tiles the descriptor does not own can be inspected.  dtype = SIGP_F64 / SIGP_F32 (the element type of every buffer).
+ * Every entry checks its descriptor against the buffer sizes given in elements and returns SIGP_BAD_ARG, launching nothing, for a
+ * descriptor that would read or write outside them, for a row or member stride that is not a multiple of 16 bytes, for K that is not a
+ * positive multiple of the K-slice (16 doubles / 32 floats), and for what the kernels do not implement: ktri = 2 outside the plain walk
+ * of gemm_mfma_kernel, ktri with `auto`, zshift without a lower walk or with ktri = 1, a tile whose triangular k span is empty, a ride
+ * row with more than 16 rows in use, members that share output tiles.
+ *
+ * sigp_debug_run_gemm: C (-)= A B^T over the tile window (r0, r1, c0, c1) of GemmArgsT, in units of cfg's tile.  cfg:
+ *   0  32x128 SET          1  32x128 SET, B transposed      2  32x128 SETNEG, B transposed
+ *   3  64x64 SET           4  64x64 SUB                     5  64x64 SUB, B transposed
+ *   6  128x128 SUB         7  128x128 SETNEG, B transposed  8  32x32 SUB
+ *   9  syrk128 SUB (launch_syrk128_t: option diag_tiles picks the diagonal-skip instantiation as in a fit)   10  syrk128 SET
+ *   11 auto (gemm_sub_auto with the handle's small_tile_threshold / tiny_tile_threshold; window in 128-units)
+ * B = NULL or B == A: ONE operand of a_elems elements (the launch sees the same device pointer on both sides; ldb, sB, zB as given).
+ * zshift shifts the trapezoid of member y of the `batch` axis (blockIdx.y) down by zshift * y tile rows.
+ */
+int sigp_debug_run_gemm(sigp_handle* h, int dtype, int cfg, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int K, int r0, int r1,
+                        int c0, int c1, int lower, int ktri, int batch, int64_t sA, int64_t sB, int64_t sC, int zcount, int64_t zA, int64_t zB, int64_t zC,
+                        int zshift, int ride_bi1, int ride_rows, int64_t a_elems, int64_t b_elems, int64_t c_elems);
+/* panel_strip_kernel: strips rb0 .. rb0 + nstrips - 1 (128-row blocks of M) of the panel of block columns [J, J + Wp), Mt = [Wp * 128][ldm] per member;
+ * option strip_tri picks the instantiation.  M comes back whole. */
+int sigp_debug_run_strip(sigp_handle* h, int dtype, void* M, int64_t ld, const void* Mt, int64_t ldm, int rb0, int nstrips, int J, int Wp, int members, int64_t sM,
+                         int64_t sMt, int64_t m_elems, int64_t mt_elems);
+/* chain_link_kernel on block column c of M: block (c+1, c) is solved into `scratch` and applied to block (c+1, c+1), the rows_ride 128-row blocks
+ * below it are solved in place.  M and scratch come back whole. */
+int sigp_debug_run_link(sigp_handle* h, int dtype, void* M, int64_t ld, int c, const void* Linv, void* scratch, int rows_ride, int members, int64_t sM, int64_t sL,
+                        int64_t sS, int64_t m_elems, int64_t linv_elems, int64_t scratch_elems);
+/* (the diagonal block: sigp_debug_time_diag with reps = 1, skip = 0 returns L and Linv of one block) */
 #ifdef __cplusplus
 }
 #endif

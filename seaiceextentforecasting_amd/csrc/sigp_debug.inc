@@ -257,3 +257,204 @@ int sigp_debug_cumask_probe(sigp_handle* h, const unsigned* mask8, int blocks, u
   (void)hipFree(d); (void)hipStreamDestroy(st);
   return SIGP_OK;
 }
+
+// ---- run-and-return entries: ONE launch of a tile primitive on the caller's operands, through the launcher the engine uses ----------------
+// (tests/test_hip_tile_primitives.py).  Every entry works out the largest element each operand can touch from the descriptor and refuses
+// (SIGP_BAD_ARG, nothing launched) what would leave the buffers, what is misaligned for the 16-byte staging accesses, and the descriptors
+// the kernels do not implement.
+}  // extern "C" (templates need C++ linkage)
+
+// the tiles member y owns in a plain-walk launch: what gemm_tile_coords hands out over blockIdx.x < gemm_grid_size (patch = 0)
+template <typename F>
+static void debug_for_owned_tiles(int r0, int r1, int c0, int c1, int lower, int zshift, int y, F&& f) {
+  for (int bj = c0; bj < c1; ++bj) {
+    const int lo = lower ? std::max(r0, bj + zshift * y) : r0;
+    for (int bi = lo; bi < r1; ++bi) f(bi, bj);
+  }
+}
+
+struct DebugDeviceBuf {   // freed on every return path
+  void* p = nullptr;
+  ~DebugDeviceBuf() { if (p) (void)hipFree(p); }
+};
+
+enum { DBG_CFG_32x128_SET = 0, DBG_CFG_32x128_SET_BT, DBG_CFG_32x128_SETNEG_BT, DBG_CFG_64x64_SET, DBG_CFG_64x64_SUB, DBG_CFG_64x64_SUB_BT,
+       DBG_CFG_128x128_SUB, DBG_CFG_128x128_SETNEG_BT, DBG_CFG_32x32_SUB, DBG_CFG_SYRK128_SUB, DBG_CFG_SYRK128_SET, DBG_CFG_AUTO, DBG_CFG_COUNT };
+
+template <typename Real>
+static int debug_run_gemm_t(sigp_handle* h, int cfg, const void* A, long lda, const void* B, long ldb, void* C, long ldc, int K, int r0, int r1, int c0,
+                            int c1, int lower, int ktri, int batch, long sA, long sB, long sC, int zcount, long zA, long zB, long zC, int zshift,
+                            int ride_bi1, int ride_rows, long a_elems, long b_elems, long c_elems) {
+  constexpr int KTe = Num<Real>::KT, NE = Num<Real>::NE;
+  constexpr long LIM = 1L << 20;
+  static const int tm_of[DBG_CFG_COUNT] = {32, 32, 32, 64, 64, 64, 128, 128, 32, 128, 128, 128};
+  static const int tn_of[DBG_CFG_COUNT] = {128, 128, 128, 64, 64, 64, 128, 128, 32, 128, 128, 128};
+  if (!h || !A || !C || cfg < 0 || cfg >= DBG_CFG_COUNT) return SIGP_BAD_ARG;
+  const bool alias = B == nullptr || B == A;          // one operand: the launch sees the SAME device pointer on both sides
+  const bool bt = cfg == DBG_CFG_32x128_SET_BT || cfg == DBG_CFG_32x128_SETNEG_BT || cfg == DBG_CFG_64x64_SUB_BT || cfg == DBG_CFG_128x128_SETNEG_BT;
+  const bool syrk = cfg == DBG_CFG_SYRK128_SUB || cfg == DBG_CFG_SYRK128_SET;
+  const int TM = tm_of[cfg], TN = tn_of[cfg];
+  if (K < KTe || K % KTe || K > LIM) return fail(h, SIGP_BAD_ARG, "debug_run_gemm: K = %d is not a positive multiple of the K-slice %d", K, KTe);
+  if (r0 < 0 || c0 < 0 || r1 > 4096 || c1 > 4096 || (lower != 0 && lower != 1)) return fail(h, SIGP_BAD_ARG, "debug_run_gemm: tile window");
+  if (batch < 0 || batch > 64 || zcount < 0 || zcount > 64) return fail(h, SIGP_BAD_ARG, "debug_run_gemm: member counts");
+  const int nby = std::max(1, batch), nbz = std::max(1, zcount);
+  if (lda < 1 || ldb < 1 || ldc < 1 || sA < 0 || sB < 0 || sC < 0 || zA < 0 || zB < 0 || zC < 0 || lda > LIM || ldb > LIM || ldc > LIM ||
+      a_elems < 1 || b_elems < (alias ? 0 : 1) || c_elems < 1 || std::max({sA, sB, sC, zA, zB, zC}) > (1L << 40))
+    return fail(h, SIGP_BAD_ARG, "debug_run_gemm: strides");
+  if (lda % NE || ldb % NE || ldc % NE || sA % NE || sB % NE || sC % NE || zA % NE || zB % NE || zC % NE)
+    return fail(h, SIGP_BAD_ARG, "debug_run_gemm: a row or member stride is not a multiple of 16 bytes");
+  if ((nby > 1 && sC == 0) || (nbz > 1 && zC == 0)) return fail(h, SIGP_BAD_ARG, "debug_run_gemm: members would write the same tiles");
+  if (ktri < 0 || ktri > 2 || (ktri == 2 && (syrk || cfg == DBG_CFG_AUTO || lower)) || (ktri == 1 && cfg == DBG_CFG_AUTO))
+    return fail(h, SIGP_BAD_ARG, "debug_run_gemm: ktri = %d is not implemented by this kernel / walk", ktri);
+  // zshift moves member blockIdx.y's trapezoid: only the plain lower walk knows it, and only downwards (the grid is sized for member 0)
+  if (zshift < 0 || zshift > 4096 || (zshift && (!lower || ktri == 1))) return fail(h, SIGP_BAD_ARG, "debug_run_gemm: zshift needs a lower walk without ktri = 1");
+  if (ride_bi1 < 0 || ride_rows < 0 || (ride_bi1 > 0 && (ride_rows < 1 || ride_rows > 16 || ride_bi1 > r1)))
+    return fail(h, SIGP_BAD_ARG, "debug_run_gemm: ride row (the RD form multiplies at most 16 rows)");
+  bool ok = true;
+  const long b_cap = alias ? a_elems : b_elems;
+  for (int y = 0; y < nby && ok; ++y)
+    for (int z = 0; z < nbz && ok; ++z)
+      debug_for_owned_tiles(r0, r1, c0, c1, lower, zshift, y, [&](int bi, int bj) {
+        const long ks = ktri == 1 ? (long)bi * TM : 0;
+        long span = K - ks;
+        if (ktri == 2) span = std::min<long>(span, (long)(bj + 1) * TN);
+        if (span < KTe || span % KTe) { ok = false; return; }       // (an empty span still stages one slice in syrk128_kernel)
+        const long a_hi = y * sA + z * zA + ((long)bi * TM + TM - 1) * lda + ks + span - 1;
+        const long b_hi = y * sB + z * zB + (bt ? (ks + span - 1) * ldb + (long)bj * TN + TN - 1 : ((long)bj * TN + TN - 1) * ldb + ks + span - 1);
+        const long c_hi = y * sC + z * zC + ((long)bi * TM + TM - 1) * ldc + (long)bj * TN + TN - 1;
+        if (a_hi >= a_elems || b_hi >= b_cap || c_hi >= c_elems) ok = false;
+      });
+  if (!ok) return fail(h, SIGP_BAD_ARG, "debug_run_gemm: the descriptor reaches outside the operand buffers (or a tile's k span is empty)");
+
+  HIPCHK(h, hipSetDevice(h->device));
+  DebugDeviceBuf dA, dB, dC;
+  HIPCHK(h, hipMalloc(&dA.p, (size_t)a_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dA.p, A, (size_t)a_elems * sizeof(Real), hipMemcpyHostToDevice));
+  if (!alias) {
+    HIPCHK(h, hipMalloc(&dB.p, (size_t)b_elems * sizeof(Real)));
+    HIPCHK(h, hipMemcpy(dB.p, B, (size_t)b_elems * sizeof(Real), hipMemcpyHostToDevice));
+  }
+  HIPCHK(h, hipMalloc(&dC.p, (size_t)c_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dC.p, C, (size_t)c_elems * sizeof(Real), hipMemcpyHostToDevice));
+  GemmArgsT<Real> g{};
+  g.A = (const Real*)dA.p; g.lda = lda; g.B = alias ? g.A : (const Real*)dB.p; g.ldb = ldb; g.C = (Real*)dC.p; g.ldc = ldc;
+  g.K = K; g.batch = batch; g.sA = sA; g.sB = sB; g.sC = sC; g.r0 = r0; g.r1 = r1; g.c0 = c0; g.c1 = c1; g.lower = lower;
+  g.stamp = nullptr; g.dbg = 0; g.patch = 0; g.ntile = 0; g.ktri = ktri;
+  g.zcount = zcount; g.zA = zA; g.zB = zB; g.zC = zC; g.zshift = zshift; g.ride_bi1 = ride_bi1; g.ride_rows = ride_rows;
+  hipStream_t st = h->slots[0].s_upd;
+  int rc = SIGP_BAD_ARG;
+  switch (cfg) {
+    case DBG_CFG_32x128_SET: rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, st, g); break;
+    case DBG_CFG_32x128_SET_BT: rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, true>(h, st, g); break;
+    case DBG_CFG_32x128_SETNEG_BT: rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SETNEG, true>(h, st, g); break;
+    case DBG_CFG_64x64_SET: rc = launch_gemm_cfg<Real, 64, 64, 2, 2, GEMM_SET, false>(h, st, g); break;
+    case DBG_CFG_64x64_SUB: rc = launch_gemm_cfg<Real, 64, 64, 2, 2, GEMM_SUB, false>(h, st, g); break;
+    case DBG_CFG_64x64_SUB_BT: rc = launch_gemm_cfg<Real, 64, 64, 2, 2, GEMM_SUB, true>(h, st, g); break;
+    case DBG_CFG_128x128_SUB: rc = launch_gemm_cfg<Real, 128, 128, 2, 2, GEMM_SUB, false>(h, st, g); break;
+    case DBG_CFG_128x128_SETNEG_BT: rc = launch_gemm_cfg<Real, 128, 128, 2, 2, GEMM_SETNEG, true>(h, st, g); break;
+    case DBG_CFG_32x32_SUB: rc = launch_gemm_cfg<Real, 32, 32, 2, 2, GEMM_SUB, false>(h, st, g); break;
+    case DBG_CFG_SYRK128_SUB: rc = launch_syrk128_t<Real, false>(h, st, g); break;
+    case DBG_CFG_SYRK128_SET: rc = launch_syrk128_t<Real, true>(h, st, g); break;
+    case DBG_CFG_AUTO: rc = gemm_sub_auto<Real>(h, st, g); break;
+  }
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(C, dC.p, (size_t)c_elems * sizeof(Real), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+template <typename Real>
+static int debug_run_strip_t(sigp_handle* h, void* M, long ld, const void* Mt, long ldm, int rb0, int nstrips, int J, int Wp, int members, long sM, long sMt,
+                             long m_elems, long mt_elems) {
+  constexpr int NE = Num<Real>::NE;
+  constexpr long LIM = 1L << 20;
+  if (!h || !M || !Mt) return SIGP_BAD_ARG;
+  if (rb0 < 0 || nstrips < 0 || J < 0 || Wp < 1 || Wp > MT_W || members < 1 || members > 64 || rb0 > 4096 || nstrips > 4096 || J > 4096)
+    return fail(h, SIGP_BAD_ARG, "debug_run_strip: strips / panel");
+  if (ld < (long)(J + Wp) * NB || ldm < (long)Wp * NB || ld > LIM || ldm > LIM || sM < 0 || sMt < 0 || m_elems < 1 || mt_elems < 1 || std::max(sM, sMt) > (1L << 40) ||
+      (members > 1 && sM == 0))
+    return fail(h, SIGP_BAD_ARG, "debug_run_strip: strides");
+  if (ld % NE || ldm % NE || sM % NE || sMt % NE) return fail(h, SIGP_BAD_ARG, "debug_run_strip: a row or member stride is not a multiple of 16 bytes");
+  if (nstrips > 0 && ((members - 1) * sM + ((long)(rb0 + nstrips) * NB - 1) * ld + (long)(J + Wp) * NB - 1 >= m_elems ||
+                      (members - 1) * sMt + ((long)Wp * NB - 1) * ldm + (long)Wp * NB - 1 >= mt_elems))
+    return fail(h, SIGP_BAD_ARG, "debug_run_strip: the descriptor reaches outside the operand buffers");
+  HIPCHK(h, hipSetDevice(h->device));
+  DebugDeviceBuf dM, dT;
+  HIPCHK(h, hipMalloc(&dM.p, (size_t)m_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dM.p, M, (size_t)m_elems * sizeof(Real), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dT.p, (size_t)mt_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dT.p, Mt, (size_t)mt_elems * sizeof(Real), hipMemcpyHostToDevice));
+  hipStream_t st = h->slots[0].s_upd;
+  if (nstrips > 0) {
+    StripArgsT<Real> a{(Real*)dM.p, ld, sM, (const Real*)dT.p, ldm, sMt, rb0, J, Wp};
+    const int rc = launch_panel_strip<Real>(h, st, a, nstrips, members);
+    if (rc) return rc;
+  }
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(M, dM.p, (size_t)m_elems * sizeof(Real), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+template <typename Real>
+static int debug_run_link_t(sigp_handle* h, void* M, long ld, int c, const void* Linv, void* scratch, int rows_ride, int members, long sM, long sL, long sS,
+                            long m_elems, long linv_elems, long scratch_elems) {
+  constexpr int NE = Num<Real>::NE;
+  constexpr long LIM = 1L << 20;
+  if (!h || !M || !Linv || !scratch) return SIGP_BAD_ARG;
+  if (c < 0 || c > 4096 || rows_ride < 0 || rows_ride > 4096 || members < 1 || members > 64) return fail(h, SIGP_BAD_ARG, "debug_run_link: column / rows / members");
+  if (ld < (long)(c + 2) * NB || ld > LIM || sM < 0 || sL < 0 || sS < 0 || m_elems < 1 || linv_elems < 1 || scratch_elems < 1 || std::max({sM, sL, sS}) > (1L << 40) ||
+      (members > 1 && (sM == 0 || sS == 0)))
+    return fail(h, SIGP_BAD_ARG, "debug_run_link: strides");
+  if (ld % NE || sM % NE || sL % NE || sS % NE) return fail(h, SIGP_BAD_ARG, "debug_run_link: a row or member stride is not a multiple of 16 bytes");
+  if ((members - 1) * sM + ((long)(c + 2 + rows_ride) * NB - 1) * ld + (long)(c + 2) * NB - 1 >= m_elems || (members - 1) * sL + (long)NB * NB > linv_elems ||
+      (members - 1) * sS + (long)NB * NB > scratch_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_link: the descriptor reaches outside the operand buffers");
+  HIPCHK(h, hipSetDevice(h->device));
+  DebugDeviceBuf dM, dL, dS;
+  HIPCHK(h, hipMalloc(&dM.p, (size_t)m_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dM.p, M, (size_t)m_elems * sizeof(Real), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dL.p, (size_t)linv_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dL.p, Linv, (size_t)linv_elems * sizeof(Real), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dS.p, (size_t)scratch_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dS.p, scratch, (size_t)scratch_elems * sizeof(Real), hipMemcpyHostToDevice));
+  LinkArgsT<Real> a{};
+  a.Acol = (Real*)dM.p + (long)(c + 1) * NB * ld + (long)c * NB; a.ld = ld;
+  a.Linv = (const Real*)dL.p;
+  a.Cdiag = (Real*)dM.p + (long)(c + 1) * NB * (ld + 1);
+  a.scratch = (Real*)dS.p;
+  a.sM = sM; a.sL = sL; a.sS = sS; a.rows_ride = rows_ride;
+  hipStream_t st = h->slots[0].s_upd;
+  const int rc = launch_chain_link<Real>(h, st, a, members);
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(M, dM.p, (size_t)m_elems * sizeof(Real), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(scratch, dS.p, (size_t)scratch_elems * sizeof(Real), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+extern "C" {
+
+int sigp_debug_run_gemm(sigp_handle* h, int dtype, int cfg, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int K, int r0, int r1,
+                        int c0, int c1, int lower, int ktri, int batch, int64_t sA, int64_t sB, int64_t sC, int zcount, int64_t zA, int64_t zB, int64_t zC,
+                        int zshift, int ride_bi1, int ride_rows, int64_t a_elems, int64_t b_elems, int64_t c_elems) {
+  if (dtype == SIGP_F32)
+    return debug_run_gemm_t<float>(h, cfg, A, lda, B, ldb, C, ldc, K, r0, r1, c0, c1, lower, ktri, batch, sA, sB, sC, zcount, zA, zB, zC, zshift, ride_bi1, ride_rows,
+                                   a_elems, b_elems, c_elems);
+  if (dtype != SIGP_F64) return SIGP_BAD_ARG;
+  return debug_run_gemm_t<double>(h, cfg, A, lda, B, ldb, C, ldc, K, r0, r1, c0, c1, lower, ktri, batch, sA, sB, sC, zcount, zA, zB, zC, zshift, ride_bi1, ride_rows,
+                                  a_elems, b_elems, c_elems);
+}
+
+int sigp_debug_run_strip(sigp_handle* h, int dtype, void* M, int64_t ld, const void* Mt, int64_t ldm, int rb0, int nstrips, int J, int Wp, int members, int64_t sM,
+                         int64_t sMt, int64_t m_elems, int64_t mt_elems) {
+  if (dtype == SIGP_F32) return debug_run_strip_t<float>(h, M, ld, Mt, ldm, rb0, nstrips, J, Wp, members, sM, sMt, m_elems, mt_elems);
+  if (dtype != SIGP_F64) return SIGP_BAD_ARG;
+  return debug_run_strip_t<double>(h, M, ld, Mt, ldm, rb0, nstrips, J, Wp, members, sM, sMt, m_elems, mt_elems);
+}
+
+int sigp_debug_run_link(sigp_handle* h, int dtype, void* M, int64_t ld, int c, const void* Linv, void* scratch, int rows_ride, int members, int64_t sM, int64_t sL,
+                        int64_t sS, int64_t m_elems, int64_t linv_elems, int64_t scratch_elems) {
+  if (dtype == SIGP_F32) return debug_run_link_t<float>(h, M, ld, c, Linv, scratch, rows_ride, members, sM, sL, sS, m_elems, linv_elems, scratch_elems);
+  if (dtype != SIGP_F64) return SIGP_BAD_ARG;
+  return debug_run_link_t<double>(h, M, ld, c, Linv, scratch, rows_ride, members, sM, sL, sS, m_elems, linv_elems, scratch_elems);
+}

@@ -106,6 +106,31 @@ int trapezoid_update(sigp_handle* h, const FactorView<Real>& v, hipStream_t st, 
   return gemm_sub_auto(h, st, g);
 }
 
+// ---- the launches of the two fused panel kernels (the engine's only ones; the debug library's run-and-return entries go through them too) ----
+// chain_link_kernel: the 36 chain workgroups + 8 ride workgroups per 128-row block below block row c+1, of nb lockstep members
+template <typename Real>
+int launch_chain_link(sigp_handle* h, hipStream_t st, const LinkArgsT<Real>& a, int nb) {
+  static AttrOnce l_attr;
+  HIPCHK(h, l_attr.set(h->device, (const void*)chain_link_kernel<Real>, link_lds_bytes<Real>()));
+  hipLaunchKernelGGL(chain_link_kernel<Real>, dim3((unsigned)(LINK_CHAIN_WGS + 8 * a.rows_ride), (unsigned)nb), dim3(256), link_lds_bytes<Real>(), st, a);
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
+// panel_strip_kernel: nstrips 128-row strips from row block a.rb0 down, of nb lockstep members (option strip_tri picks the instantiation)
+template <typename Real>
+int launch_panel_strip(sigp_handle* h, hipStream_t st, const StripArgsT<Real>& a, int nstrips, int nb) {
+  static AttrOnce strip_attr, strip_attr_full;
+  if (h->opt_strip_tri) {
+    HIPCHK(h, strip_attr.set(h->device, (const void*)panel_strip_kernel<Real>, SY_LDS_BYTES));
+    hipLaunchKernelGGL(panel_strip_kernel<Real>, dim3(nstrips, nb), dim3(256), SY_LDS_BYTES, st, a);
+  } else {
+    HIPCHK(h, strip_attr_full.set(h->device, (const void*)panel_strip_kernel<Real, false>, SY_LDS_BYTES));
+    hipLaunchKernelGGL((panel_strip_kernel<Real, false>), dim3(nstrips, nb), dim3(256), SY_LDS_BYTES, st, a);
+  }
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
+
 // ---- a panel as a latency chain ---------------------------------------------------------------------------------------------
 // Block columns [J0, J0 + Wp) of the view's lockstep members (already up to date), right-looking and column by column, arranged
 // around the chain  diagonal block c -> what diagonal block c+1 needs -> diagonal block c+1:
@@ -119,8 +144,6 @@ int trapezoid_update(sigp_handle* h, const FactorView<Real>& v, hipStream_t st, 
 // on_col (may be null): called once block column c is final in the matrix (the sharded fit streams it to the other ranks).
 template <typename Real>
 int chain_panel(sigp_handle* h, const FactorView<Real>& v, hipStream_t sp, int J0, int Wp, int rlim, const std::function<int(int)>* on_col = nullptr) {
-  static AttrOnce l_attr;
-  HIPCHK(h, l_attr.set(h->device, (const void*)chain_link_kernel<Real>, link_lds_bytes<Real>()));
   const int nb = v.nb;
   int rc = diag_block(h, v, sp, J0);
   if (rc) return rc;
@@ -155,8 +178,7 @@ int chain_panel(sigp_handle* h, const FactorView<Real>& v, hipStream_t sp, int J
       a.sM = v.matStride; a.sL = v.dinvStride; a.sS = (long)NB * NB;
       a.rows_ride = rows_below - 1;
       ProfScope ps(h, sp, SIGP_KC_TRSM, nb * (2.0 * rows_below * NB * NB * NB + (double)NB * NB * NB), nb * 2.0 * rows_below * NB * NB * 8);
-      hipLaunchKernelGGL(chain_link_kernel<Real>, dim3((unsigned)(LINK_CHAIN_WGS + 8 * a.rows_ride), (unsigned)nb), dim3(256), link_lds_bytes<Real>(), sp, a);
-      HIPCHK(h, hipGetLastError());
+      if ((rc = launch_chain_link<Real>(h, sp, a, nb))) return rc;
     }
     GemmArgsT<Real> gu = update_args(v, c, 1, c + 1, 0, Wp - i - 1, rlim);   // columns c+1 .. J0+Wp-1 from row block c+2 down (block (c+1, c+1) is done)
     gu.r0 = 2; gu.r1 *= 2; gu.c0 *= 2; gu.c1 *= 2;
@@ -256,16 +278,8 @@ struct PotrfRun {
     }
     {
       ProfScope ps(h, sp, SIGP_KC_TRSM, nb * (double)below * 2.0 * NB * NB * NB * (Wp * (Wp + 1) / 2), nb * (double)below * 2.0 * Wp * NB * NB * 8);
-      static AttrOnce strip_attr, strip_attr_full;
       StripArgsT<Real> a{v.M, v.ld, v.matStride, mt, MT_LD, mtStride, J0 + Wp, J0, Wp};
-      if (h->opt_strip_tri) {
-        HIPCHK(h, strip_attr.set(h->device, (const void*)panel_strip_kernel<Real>, SY_LDS_BYTES));
-        hipLaunchKernelGGL(panel_strip_kernel<Real>, dim3(below, nb), dim3(256), SY_LDS_BYTES, sp, a);
-      } else {
-        HIPCHK(h, strip_attr_full.set(h->device, (const void*)panel_strip_kernel<Real, false>, SY_LDS_BYTES));
-        hipLaunchKernelGGL((panel_strip_kernel<Real, false>), dim3(below, nb), dim3(256), SY_LDS_BYTES, sp, a);
-      }
-      HIPCHK(h, hipGetLastError());
+      if ((rc = launch_panel_strip<Real>(h, sp, a, below, nb))) return rc;
     }
     return SIGP_OK;
   }

@@ -173,6 +173,16 @@ def err(a, b):
     return float(np.max(np.abs(np.asarray(a, dtype=LD) - np.asarray(b, dtype=LD))))
 
 
+def hp_matmul(A, B, block=64):
+    """A @ B in long double (A [m, k], B [k, n] of any real type, widened first), by row blocks of A: every entry is one plain
+    dot product over k ascending in extended precision (NumPy has no BLAS for long double)."""
+    A, B = np.asarray(A, dtype=LD), np.asarray(B, dtype=LD)
+    out = np.empty((A.shape[0], B.shape[1]), dtype=LD)
+    for i in range(0, A.shape[0], block):
+        out[i:i + block] = A[i:i + block] @ B
+    return out
+
+
 def cond2(K):
     w = np.linalg.eigvalsh(np.asarray(K, dtype=np.float64))
     return float(w[-1] / abs(w[0])) if w[0] != 0 else np.inf
