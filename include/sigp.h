@@ -271,8 +271,8 @@ int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
  * sigp_nlml_grad does.  fp64 engine, RBF / Matern-5/2 only; before sigp_set_train: SIGP_BAD_ARG.  Afterwards the handle is fitted at
  * those hyper-parameters with the scales set: sigp_predict, sigp_predict_ride, sigp_loo, sigp_cv, sigp_predict_cov work on it.  Device
  * work is accounted under SIGP_KC_MLII (the triangular inversion, U U^T, the pass: one entry each).
- * Lockstep groups of such fits: sigp_nlml_grad_ard_batch (the ARD gradients of the leave-one-out and leave-block-out scores are
- * sigp_loo_grad_ard's and sigp_cv_grad_ard's, single fits only).  Not covered: the one-workgroup kernel (sigp_small_*), the fp32 engine,
+ * Lockstep groups of such fits: sigp_nlml_grad_ard_batch (the ARD gradients of the leave-one-out scores are sigp_loo_grad_ard's and, in
+ * lockstep groups, sigp_loo_grad_ard_batch's; those of the leave-block-out scores sigp_cv_grad_ard's, single fits only).  Not covered: the one-workgroup kernel (sigp_small_*), the fp32 engine,
  * sharded fits. */
 int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad);
 
@@ -298,7 +298,8 @@ int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64
  * SIGP_BAD_ARG: before sigp_batch_upload, an fp32 handle, the reference kernel, ntheta != d + 1, a leading dimension below its width.
  * Device work is accounted under SIGP_KC_MLII, the staging under SIGP_KC_KBUILD.  Both calls leave the handle unfitted, as the other batch
  * entries do, and neither read nor change the single-fit scales of sigp_set_length_scales.
- * Not covered: ARD gradients of the leave-one-out / leave-block-out scores for lockstep groups, sigp_small_*, the fp32 engine, sharded fits. */
+ * The leave-one-out scores and their ARD gradients for lockstep groups: sigp_loo_grad_ard_batch.  Not covered: ARD gradients of the
+ * leave-block-out scores for lockstep groups, sigp_small_*, the fp32 engine, sharded fits. */
 int sigp_batch_run_ard(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, int64_t ldell, const double* sn_tilde,
                        double* out, double* mean, double* var);
 int sigp_nlml_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
@@ -363,10 +364,31 @@ int sigp_loo_grad_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
  * SIGP_BAD_ARG: the reference kernel, an fp32 handle, before sigp_set_train, n < 2, ntheta != d + 1, a bad sigma_mode or criterion.
  * SIGP_NOT_SPD: a non-SPD K~ or an exp(theta[k]) that is not finite and positive (sn~ = 0 is allowed): +inf in score and every grad entry,
  * NaN in mean / var.  Afterwards the handle is fitted at those hyper-parameters with the scales set, as after sigp_nlml_grad_ard.
- * Not covered: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits.  The leave-block-out scores: sigp_cv_grad_ard. */
+ * Lockstep groups of such fits: sigp_loo_grad_ard_batch (below).  Not covered: sigp_small_*, the fp32 engine, sharded fits.  The
+ * leave-block-out scores: sigp_cv_grad_ard. */
 enum { SIGP_LOO_NLPD = 0, SIGP_LOO_SSE = 1 };
 int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int sigma_mode, int criterion,
                       double* mean, double* var, double* score, double* grad);
+/* ... for lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2, fp64): what sigp_loo_grad_batch does, with
+ * scales per FIT as in sigp_nlml_grad_ard_batch -- fit i uses data set (first + i) % batch and theta_i = theta[i ldtheta .. + ntheta) =
+ * (log l_1 .. log l_d, log sn~), ntheta = d + 1; two members of one group may share a data set and differ in scales.  score [count][2] =
+ * nlpd, sse; mean / var [count][nstride >= n] (both or neither); grad [count][ldgrad >= d + 1], the derivatives of the score `criterion`
+ * names, or NULL: scores and predictions only, no cubic work beyond sigp_loo_batch's.  Groups of `group` members (sigp_set_option) run one
+ * after another.  Per group: sigp_batch_run_ard's staging launch, the isotropic entries' fit at ell = 1 on the staged features and
+ * sigp_loo_batch's launches on it -- the scores and predictions carry the bits sigp_loo_batch returns on data sets X / l uploaded as they
+ * are, at ell = 1 --, then for every member at once K~^-1 = U U^T, a = U z, the coefficients beta, gamma, eps, v = P beta and P Gamma, ONE
+ * cubic product M = (P Gamma) P^T per member (n^3 flops, whatever d) and sigp_loo_grad_ard's tile pass and fixed-order sums with the
+ * member on a grid axis (no atomics: the same bits on every run, whatever the group size; a member executes a single fit's instructions
+ * and carries the bits sigp_loo_grad_ard returns for it wherever the lockstep factorisation has the single fit's bits).  One copy brings a
+ * group's gradients back.  A member whose exp(theta) overflows, one of whose scales underflows to 0, or whose K~ is not SPD gets +inf in
+ * both scores and all d + 1 gradient entries and NaN rows in mean / var; its group mates are unaffected and the call returns SIGP_OK.
+ * Memory beside the slot: three matrices of 8 group n_pad^2 bytes (L~^-T / M, K~^-1, P Gamma), as sigp_loo_grad_batch, and the staging area.
+ * SIGP_BAD_ARG: before sigp_batch_upload, count < 1, an fp32 handle, the reference kernel, n < 2, ntheta != d + 1, a leading dimension
+ * below its width, a bad sigma_mode or criterion, mean without var.  Device work is accounted under SIGP_KC_MLII, the staging under
+ * SIGP_KC_KBUILD.  The handle is left unfitted, as after the other batch entries.
+ * Not covered: the leave-block-out scores in lockstep groups, sigp_small_*, the fp32 engine, sharded fits. */
+int sigp_loo_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
+                            int sigma_mode, int criterion, double* mean, double* var, int64_t nstride, double* score, double* grad, int64_t ldgrad);
 /* sigp_small_run with the leave-one-out cross-validation of every fit in the SAME single launch (L~^-1 formed in LDS over L~ as in
  * sigp_small_run_grad): out6 [nprob][6] = sigma_f, nlML, info, sigma_n, nlpd, sse; mean / var as in sigp_small_run;
  * loo_mean / loo_var [nprob][nstride >= largest n of the upload], entries beyond a set's n = NaN.  info > 0: nlpd = sse = +inf and NaN rows.

@@ -50,21 +50,22 @@ __global__ __launch_bounds__(256) void ard_center_kernel(const double* __restric
 // WSEL picks the weight: ARD_W_NLML, the adjoint of the nlML above; ARD_W_LOO, the adjoint of a leave-one-out score (looard.hpp) --
 // W = (2 M_ij + v_i a_j + a_i v_j + 2 eps a_i a_j) o h with M = P diag(gamma) P read where P is read (its lower 128-tiles), v = P beta and
 // eps[0] from device memory (q is not read).  Everything after the weight is shared.
-// blockIdx.y = lockstep member (sigp_nlml_grad_ard_batch): member b reads U, Uc, P, a, q and writes partial at b times the strides of ms
-// (in doubles); the offsets are added to the pointers before anything is read, so a member executes the instructions a single fit does.
-// Single fits launch one member with zero strides; v and eps (ARD_W_LOO) have no member axis.
+// blockIdx.y = lockstep member (sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch): member b reads U, Uc, P, a, q (ARD_W_NLML) or v, eps
+// (ARD_W_LOO) and writes partial at b times the strides of ms (in doubles); the offsets are added to the pointers before anything is read,
+// so a member executes the instructions a single fit does.  Single fits launch one member with zero strides.
 enum { ARD_W_NLML = 0, ARD_W_LOO = 1 };
-struct ArdMemberStrides { long U, P, a, q, partial; };   // U and Uc alike; q: the slot's result rows (512 doubles apart)
+struct ArdMemberStrides { long U, P, a, q, partial, v, eps; };   // U and Uc alike; q: the slot's result rows (512 doubles apart); v, eps: ARD_W_LOO alone
 template <int DC, int WSEL = ARD_W_NLML>
 __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __restrict__ U, const double* __restrict__ Uc, int dp, int d, int n,
                                                                int kernel_id, const double* __restrict__ P, long ld,
                                                                const double* __restrict__ a, const double* __restrict__ q,
                                                                double* __restrict__ partial, const double* __restrict__ v = nullptr,
-                                                               const double* __restrict__ eps = nullptr, ArdMemberStrides ms = ArdMemberStrides{0, 0, 0, 0, 0}) {
+                                                               const double* __restrict__ eps = nullptr, ArdMemberStrides ms = ArdMemberStrides{0, 0, 0, 0, 0, 0, 0}) {
   {
     const long mb = blockIdx.y;
     U += mb * ms.U; Uc += mb * ms.U; P += mb * ms.P; a += mb * ms.a; partial += mb * ms.partial;
     if constexpr (WSEL == ARD_W_NLML) q += mb * ms.q;
+    else { v += mb * ms.v; eps += mb * ms.eps; }
   }
   const int u = blockIdx.x >> 1;                       // (the lower-triangle tile walk of kbuild_mfma_kernel)
   int k = (int)((sqrt(8.0 * u + 1.0) - 1.0) * 0.5);
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(256) void ard_grad_partial_kernel(const double* __r
 __global__ __launch_bounds__(256) void ard_grad_finish_kernel(const double* __restrict__ partial, long ntiles, int dp, int d, int n,
                                                               const double* __restrict__ P, long ld, const double* __restrict__ a,
                                                               const double* __restrict__ q, double sn, double* __restrict__ grad,
-                                                              ArdMemberStrides ms = ArdMemberStrides{0, 0, 0, 0, 0}, long sGrad = 0,
+                                                              ArdMemberStrides ms = ArdMemberStrides{0, 0, 0, 0, 0, 0, 0}, long sGrad = 0,
                                                               const double* __restrict__ sn_m = nullptr) {
   __shared__ double sh[4];
   const int k = blockIdx.x;

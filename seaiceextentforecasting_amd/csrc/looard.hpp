@@ -22,13 +22,22 @@
 namespace sigp {
 
 // The vector workspace of the pass (in the gradient workspace of sigp_loo_grad), LooArdVecs: score_layout.hpp.
+// Lockstep members (sigp_loo_grad_ard_batch): every kernel below takes the member from a grid dimension and adds the member's offsets -- P, PG
+// and M n_pad^2 apart, the vectors LooArdGroupVecs::mstride() apart, q in the slot's result rows -- to its pointers before anything is
+// read: uniform values, no vector register, and a member executes the instructions a single fit does.  The single fits launch one member
+// with zero strides.
+struct LooArdStrides { long P, q, w, partial, grad; };   // P: P, PG and M alike;  w: the vector workspace;  q: 512 doubles in a slot
 
 // beta, gamma [n_pad] (zero from n on) and eps of the score `crit` (0 nlpd, 1 sse) in sigma mode `mode` (0 "refit", 1 "fixed"), one block:
 // g_i is the diagonal of P, q = y^T A~ comes from *q; s_i and var_i are formed as loo_rows_kernel / loo_grad_point_kernel form them.
-// Every thread adds its points in ascending order and block_reduce_sum adds the threads in a fixed order.
+// Every thread adds its points in ascending order and block_reduce_sum adds the threads in a fixed order.  blockIdx.x = lockstep member.
 __global__ __launch_bounds__(256) void loo_ard_coef_kernel(const double* __restrict__ P, long ld, int n, int n_pad, const double* __restrict__ q, int mode, int crit,
-                                                           LooArdVecs w) {
+                                                           LooArdVecs w, LooArdStrides ms = LooArdStrides{0, 0, 0, 0, 0}) {
   __shared__ double sh[4];
+  {
+    const long mb = blockIdx.x;
+    P += mb * ms.P; q += mb * ms.q; w.base += mb * ms.w;
+  }
   const double* a = w.a();
   double* beta = w.beta();
   double* gamma = w.gamma();
@@ -64,8 +73,13 @@ __global__ __launch_bounds__(256) void loo_ard_coef_kernel(const double* __restr
 }
 
 // One WAVE per row i < n_pad of the full P:  v_i = sum_{k < n} P_ik beta_k  and row i of P Gamma, PG_ik = P_ik gamma_k, written whole
-// (zero from column n on; rows n .. n_pad are zero and v is zero there).
-__global__ __launch_bounds__(256) void loo_ard_scale_kernel(const double* __restrict__ P, double* __restrict__ PG, long ld, int n, int n_pad, LooArdVecs w) {
+// (zero from column n on; rows n .. n_pad are zero and v is zero there).  blockIdx.y = lockstep member.
+__global__ __launch_bounds__(256) void loo_ard_scale_kernel(const double* __restrict__ P, double* __restrict__ PG, long ld, int n, int n_pad, LooArdVecs w,
+                                                            LooArdStrides ms = LooArdStrides{0, 0, 0, 0, 0}) {
+  {
+    const long mb = blockIdx.y;
+    P += mb * ms.P; PG += mb * ms.P; w.base += mb * ms.w;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave;
   if (i >= n_pad) return;
@@ -95,11 +109,18 @@ __global__ __launch_bounds__(256) void loo_ard_scale_kernel(const double* __rest
 }
 
 // grad[k] = sum over the tiles, in tile order, of partial[tile][k] (k < d: block k), and grad[d] = sn~ tr G = sn~ sum_i (M_ii + v_i a_i + eps a_i^2)
-// (block d): ard_grad_finish_kernel with the adjoint of a leave-one-out score in the noise component.
+// (block d): ard_grad_finish_kernel with the adjoint of a leave-one-out score in the noise component.  blockIdx.y = lockstep member: grad
+// [member][ms.grad], and the member's sn~ from sn_m (device memory; NULL: the argument sn, a single fit).
 __global__ __launch_bounds__(256) void loo_ard_finish_kernel(const double* __restrict__ partial, long ntiles, int dp, int d, int n, const double* __restrict__ M, long ld,
-                                                             LooArdVecs w, double sn, double* __restrict__ grad) {
+                                                             LooArdVecs w, double sn, double* __restrict__ grad, LooArdStrides ms = LooArdStrides{0, 0, 0, 0, 0},
+                                                             const double* __restrict__ sn_m = nullptr) {
   __shared__ double sh[4];
   const int k = blockIdx.x;
+  {
+    const long mb = blockIdx.y;
+    partial += mb * ms.partial; M += mb * ms.P; w.base += mb * ms.w; grad += mb * ms.grad;
+    if (sn_m != nullptr) sn = sn_m[mb];
+  }
   double t = 0.0;
   if (k < d) {
     for (long i = threadIdx.x; i < ntiles; i += 256) t += partial[i * dp + k];

@@ -10,11 +10,13 @@
 //                       MliiParts            sigp_nlml_grad
 //                       MliiGroupParts       sigp_nlml_grad_batch
 //                       ArdParts             sigp_nlml_grad_ard, sigp_nlml_grad_ard_batch
+//                       LooArdGroupParts     sigp_loo_grad_ard_batch: ScoreParts of G members, then ArdParts of G members
 //   gV                  LooGradVecs          sigp_loo_grad(_batch)
 //                       LooArdVecs           sigp_loo_grad_ard, sigp_cv_grad_ard
+//                       LooArdGroupVecs      sigp_loo_grad_ard_batch: G LooArdVecs at an even member stride
 //   cvPart cvBlk cvVec  CvWork               cv_launch
 //   cvAdj               CvAdjStore           sigp_cv_grad_ard; it fills the CvAdjoint that cv_launch and the kernels take
-//   bStage              ArdStage             sigp_batch_run_ard, sigp_nlml_grad_ard_batch
+//   bStage              ArdStage             sigp_batch_run_ard, sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch
 // gU, gK, gD [G][n_pad][n_pad], scratchZ and ardXc are used whole: they have no layout beyond their size.
 // Everything is in doubles.  n_pad is a multiple of 128, dp of 64, wp of 16.
 #pragma once
@@ -84,6 +86,15 @@ struct ArdParts {
   __host__ __device__ double* grad() const { return base + G * mstride(); }
 };
 
+// The per-feature gradient of a leave-one-out score for a lockstep group: ScoreParts of G members (the sums behind all G members' rows, as
+// ever), then ArdParts of G members keeping gw = d + 1 gradient entries each.
+struct LooArdGroupParts {
+  double* base; long G, n_pad, tiles, dp, gw;
+  __host__ __device__ static long size(long G, long n_pad, long tiles, long dp, long gw) { return ScoreParts::size(G, n_pad) + ArdParts::size(G, tiles, dp, gw); }
+  __host__ __device__ ScoreParts scores() const { return ScoreParts{base, G, n_pad}; }
+  __host__ __device__ ArdParts ard() const { return ArdParts{base + ScoreParts::size(G, n_pad), G, tiles, dp, gw}; }
+};
+
 // ---- gV --------------------------------------------------------------------------------------------------------------------------------------
 // Per-member vector workspace of sigp_loo_grad's gradient pass: a, t, b (= P t), P a, sum_k P_ik^2 [n_pad each], the column pass's partial
 // sums [n_pad / 128][n_pad], the four gradient components.  a and t are read in 16-byte pairs: every row starts at an even offset, and
@@ -111,6 +122,15 @@ struct LooArdVecs {
   __host__ __device__ double* gamma() const { return base + 2 * n_pad; }
   __host__ __device__ double* v() const { return base + 3 * n_pad; }
   __host__ __device__ double* eps() const { return base + 4 * n_pad; }
+};
+
+// ... of the G members of a lockstep group.  LooArdVecs::size is odd and the vectors are read in 16-byte pairs, so the members lie
+// mstride() = 4 n_pad + 2 apart (even; one double spare behind eps): member b is the LooArdVecs at base + b mstride().
+struct LooArdGroupVecs {
+  double* base; long n_pad, G;
+  __host__ __device__ static long size(long G, long n_pad) { return G * (4 * n_pad + 2); }
+  __host__ __device__ long mstride() const { return 4 * n_pad + 2; }
+  __host__ __device__ LooArdVecs member(long b) const { return LooArdVecs{base + b * mstride(), n_pad}; }
 };
 
 // ---- cvPart, cvBlk, cvVec ----------------------------------------------------------------------------------------------------------------------

@@ -8,8 +8,9 @@
 // The gradient: inv_factor, kinv_lower, alpha_from_U for all members at once (as sigp_nlml_grad_batch), then sigp_nlml_grad_ard's tile pass
 // and finish kernel with the member on grid.y -- partials per (member, tile), fixed-order sums, no atomics.
 // Both entries run their groups one after another on slot 0, as the score entries do.  Profile classes: the staging SIGP_KC_KBUILD, the
-// gradient's work SIGP_KC_MLII.  Out of scope: ARD gradients of the leave-one-out / leave-block-out scores for groups, sigp_small_*, the
-// fp32 engine, sharded fits.  Included inside extern "C" of sigp.hip, after sigp_ardgrad.inc.
+// gradient's work SIGP_KC_MLII.  The leave-one-out scores and their ARD gradients for groups: sigp_looardbatch.inc, on this file's staging.
+// Out of scope: ARD gradients of the leave-block-out scores for groups, sigp_small_*, the fp32 engine, sharded fits.  Included inside
+// extern "C" of sigp.hip, after sigp_ardgrad.inc.
 
 // the staging area of slot s (ArdStage, score_layout.hpp), sized for the slot's capacity
 static int ard_stage_ensure(sigp_handle* h, const Slot& s, ArdStage* a) {

@@ -9,26 +9,35 @@
 //   v = P beta, P Gamma into gD, one pass over the rows of P (loo_ard_scale_kernel)
 //   M = (P Gamma) P^T lower 128-tiles into gU, which is dead by then: syrk_set on the lower tile space, whole diagonal tiles
 //                    (the DG form of a diagonal tile belongs to the product form !SET alone, and A != B here anyway): n^3 flops for any d
-//   the ARD pass     loo_ard_pass: ard_tile_pass<ARD_W_LOO> over M, v, a, eps, then loo_ard_finish_kernel
+//   the ARD pass     loo_ard_pass (one member of loo_ard_pass_members): the tile pass with ARD_W_LOO over M, v, a, eps, then loo_ard_finish_kernel
 // Memory: sigp_loo_grad's single-fit buffers (gU, gK, gD, gV, gPart; gPart also holds the pass's per-tile partials) plus ardXc.
 // Profile class: SIGP_KC_MLII (on top of loo_launch's two entries: U U^T, the n^2 passes, the product M, the ARD pass: one entry each).
-// Out of scope: the lockstep-batch entries, sigp_small_*, the fp32 engine, sharded fits.  The leave-block-out scores: sigp_cvard.inc.
+// Out of scope: sigp_small_*, the fp32 engine, sharded fits.  Lockstep groups: sigp_loo_grad_ard_batch (sigp_looardbatch.inc), which runs
+// these launches with a member axis.  The leave-block-out scores: sigp_cvard.inc.
 
 // The ARD pass of a leave-one-out / leave-block-out score (sigp_cv_grad_ard shares it) over M in gU with the vectors w: every tile's share of
 // all d components, then the fixed-order sums; the gradient [d + 1] on its way to the caller.  The partials and the gradient lie in ap.
-static int loo_ard_pass(sigp_handle* h, hipStream_t st, int kernel_id, LooArdVecs w, ScoreArdParts ap, double snt, double* grad) {
-  const long n = h->n, d = h->d, dp = h->dp, n_pad = h->n_pad, ntiles = ap.tiles;
-  double* partial = ap.partial();
-  double* gdev = ap.grad();
+// The member form (sigp_loo_grad_ard_batch): nb lockstep members on scaled features U [nb][n_pad][dp] (member stride sU), member b's M in gU,
+// vectors, partials and gradient at b times the strides of ls behind w, partial and gdev (ls.grad = d + 1: the group's gradients go to the
+// host in one copy), its sn~ in sn_m[b] (NULL: snt).  One member with zero strides is the single fit.
+static int loo_ard_pass_members(sigp_handle* h, hipStream_t st, int nb, int kernel_id, const double* U, long sU, long n, long d, long dp, long n_pad, LooArdVecs w,
+                                LooArdStrides ls, double* partial, double* gdev, double snt, const double* sn_m, double* grad) {
+  const long ntiles = kbuild_tiles(n_pad);
+  const ArdMemberStrides ms{sU, ls.P, ls.w, 0, ls.partial, ls.w, ls.w};
   int rc;
   {
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 36), 4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp));
-    if ((rc = ard_tile_pass<ARD_W_LOO>(h, st, kernel_id, h->gU, n_pad, w.a(), nullptr, w.v(), w.eps(), partial))) return rc;
-    hipLaunchKernelGGL(loo_ard_finish_kernel, dim3((unsigned)(d + 1)), dim3(256), 0, st, (const double*)partial, ntiles, (int)dp, (int)d, (int)n, (const double*)h->gU, n_pad, w, snt, gdev);
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 36)), nb * (4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp)));
+    if ((rc = ard_tile_pass_members<ARD_W_LOO>(h, st, nb, U, n, d, dp, n_pad, ms, kernel_id, h->gU, n_pad, w.a(), nullptr, w.v(), w.eps(), partial))) return rc;
+    hipLaunchKernelGGL(loo_ard_finish_kernel, dim3((unsigned)(d + 1), (unsigned)nb), dim3(256), 0, st, (const double*)partial, ntiles, (int)dp, (int)d, (int)n,
+                       (const double*)h->gU, n_pad, w, snt, gdev, ls, sn_m);
     HIPCHK(h, hipGetLastError());
   }
-  HIPCHK(h, hipMemcpyAsync(grad, gdev, (size_t)(d + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(grad, gdev, (size_t)nb * (d + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
   return SIGP_OK;
+}
+
+static int loo_ard_pass(sigp_handle* h, hipStream_t st, int kernel_id, LooArdVecs w, ScoreArdParts ap, double snt, double* grad) {
+  return loo_ard_pass_members(h, st, 1, kernel_id, h->X, 0, h->n, h->d, h->dp, h->n_pad, w, LooArdStrides{0, 0, 0, 0, 0}, ap.partial(), ap.grad(), snt, nullptr, grad);
 }
 
 int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int sigma_mode, int criterion, double* mean, double* var, double* score,

@@ -76,7 +76,7 @@ static int mirror_P(sigp_handle* h, hipStream_t st, int nb, long n_pad) {
 // ---- per-feature (ARD) gradients ---------------------------------------------------------------------------------------------------------------
 // The tile pass over scaled features U [n_pad][dp] (nb lockstep members, strides ms): their centred copy into ardXc, then every tile's share
 // of all d components into partial [tiles][dp].  W = ARD_W_NLML: M = K~^-1 (lower tiles), a, q = y^T a;  W = ARD_W_LOO: M, a, v, eps of
-// looard.hpp (q is not read; one member).  The callers launch their own finish kernel, and book the pass and the finish under one profile
+// looard.hpp (q is not read; v and eps at the strides ms.v, ms.eps).  The callers launch their own finish kernel, and book the pass and the finish under one profile
 // entry of their own.  ard_tile_pass: the single fit -- the handle's own features, one member, zero strides.
 extern "C++" {
 template <int W>
@@ -97,7 +97,7 @@ static int ard_tile_pass_members(sigp_handle* h, hipStream_t st, int nb, const d
 template <int W>
 static int ard_tile_pass(sigp_handle* h, hipStream_t st, int kernel_id, const double* M, long ldm, const double* a, const double* q, const double* v,
                          const double* eps, double* partial) {
-  return ard_tile_pass_members<W>(h, st, 1, h->X, h->n, h->d, h->dp, h->n_pad, ArdMemberStrides{0, 0, 0, 0, 0}, kernel_id, M, ldm, a, q, v, eps, partial);
+  return ard_tile_pass_members<W>(h, st, 1, h->X, h->n, h->d, h->dp, h->n_pad, ArdMemberStrides{0, 0, 0, 0, 0, 0, 0}, kernel_id, M, ldm, a, q, v, eps, partial);
 }
 }  // extern "C++"
 

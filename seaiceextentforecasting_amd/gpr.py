@@ -1059,6 +1059,79 @@ class GPR:
         self._fitted = False
         return val, g
 
+    def loo_ard_batch(self, theta, first=0, criterion="loo_nlpd", sigma_f="refit", grad="exact", group=8, predictions=False):
+        """``loo_ard`` for many fits in one device call on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern, fp64):
+        theta [F, d + 1] = (log l_1 .. log l_d, log sn~) per FIT, fit i uses data set (first + i) % B -- two fits may share a data set and
+        differ in scales.  Lockstep groups of ``group`` fits (``sigp_loo_grad_ard_batch``): per group one staging launch, the fit and
+        ``loo_batch``'s launches at ell = 1 on the staged features, then ``loo_ard``'s gradient for all members at once (one cubic product
+        per member, one tile pass).  Returns (value [F], grad [F, d + 1] or None) with value = the leave-one-out negative log predictive
+        density (``criterion='loo_nlpd'``) or sum of squared errors (``'loo_sse'``); ``grad=None``: values only, no cubic work beyond
+        ``loo_batch``'s.  ``predictions=True`` returns dict(value, grad, mean [F, n], var [F, n], nlpd [F], sse [F]) instead.  A fit whose K~
+        is not SPD or whose exp(theta) overflows gets +inf in its value, both scores and all its gradient entries and NaN predictions; its
+        group mates are unaffected.  The gradient pass is ``loo_ard``'s own code: where the lockstep factorisation has the single fit's
+        bits (small orders), every fit carries the bits ``loo_ard`` returns for it."""
+        if criterion not in L.LOO_CRITERION_IDS:
+            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        d, n = getattr(self, "_batch_d", None), getattr(self, "_batch_n", None)
+        if d is None:
+            raise RuntimeError("loo_ard_batch: stage the data sets with upload_batch() first")
+        theta = L.f64(np.atleast_2d(theta), 2)
+        if theta.shape[1] != d + 1:
+            raise ValueError("theta must be [F, d + 1] = [F, %d] (log l_1 .. log l_d, log sn~), got %s" % (d + 1, theta.shape))
+        F = theta.shape[0]
+        self.set_option("group", group)
+        score = np.zeros((F, 2))
+        g = np.zeros((F, d + 1)) if grad is not None else None
+        mean = np.zeros((F, n)) if predictions else None
+        var = np.zeros((F, n)) if predictions else None
+        self._check(self._lib.sigp_loo_grad_ard_batch(self._h, int(first), F, self._kid, L.ptr(theta), d + 1, d + 1, L.LOO_MODES[sigma_f], L.LOO_CRITERION_IDS[criterion],
+                                                      L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1), "loo_ard_batch")
+        self._fitted = False
+        value = score[:, L.LOO_CRITERION_IDS[criterion]].copy()
+        if not predictions:
+            return value, g
+        return dict(value=value, grad=g, mean=mean, var=var, nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
+
+    def optimize_ard_batch(self, X, y, theta0, criterion="loo_nlpd", sigma_f="refit", group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0):
+        """``optimize_ard`` for EVERY data set of a retrospective run at once: X [B, n, d], y [B, n] -> dict(x [F, d + 1], fun [F], nit [F],
+        converged [F], nfev = device calls), the lockstep BFGS of ``optimize_batch`` (``optim.bfgs_lockstep``) over one length scale per
+        feature and the noise, each round ONE device call for all unfinished starts.  ``criterion`` 'loo_nlpd' or 'loo_sse' minimises that
+        leave-one-out score (``loo_ard_batch`` with ``sigma_f``) -- with d + 1 hyper-parameters and few data the marginal likelihood overfits
+        the relevance of features, and the predictive score is the honest objective; 'nlml' is ``optimize_batch(ard=True)``.  ``theta0`` is
+        [F, d + 1], [d + 1], [F, 2] or [2] (the common log l is repeated for all d features); F = S B rows are S starts per data set, start
+        i on data set i % B, and all F results come back.  RBF / Matern, fp64.  The leave-block-out scores have no lockstep form:
+        ``optimize_ard(criterion='cv_*')`` minimises them one data set at a time."""
+        from .optim import bfgs_lockstep
+        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS:
+            raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        if criterion == "nlml":
+            return self.optimize_batch(X, y, theta0, group=group, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step, ard=True)
+        X = L.f64(X, 3)
+        B, d = X.shape[0], X.shape[2]
+        p = d + 1
+        th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
+        if th0.ndim == 2 and th0.shape[1] == 2 and d != 1:      # (log l, log sn~): the common log l for every feature
+            th0 = np.concatenate([np.repeat(th0[:, :1], d, axis=1), th0[:, 1:]], axis=1)
+        if th0.ndim != 2 or th0.shape[1] != p:
+            raise ValueError("theta0 must hold d + 1 = %d entries per start, or 2 (log l is repeated for every feature)" % p)
+        if th0.shape[0] != B and th0.shape[0] % B == 0:
+            th0 = np.array(th0)                                   # S starts per data set: start i uses data set i % B
+        else:
+            th0 = np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, p))
+        self.upload_batch(X, y, None, group=group, concurrency=1)
+        return bfgs_lockstep(lambda t: self.loo_ard_batch(t, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol,
+                             ftol=ftol, max_step=max_step)
+
     def _loo_objective_batch(self, theta, criterion, sigma_f, group):
         """(value [F], grad [F, 2]) of a leave-one-out score for theta [F, 2] on the staged data sets, one device call (``loo_batch``)."""
         theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
@@ -1091,12 +1164,12 @@ class GPR:
         and all F results come back -- choosing the best start of a data set is the caller's job.
         ``ard=True`` (RBF / Matern, ``criterion='nlml'``): one length scale per feature, the same lockstep BFGS on ``nlml_ard_batch`` (d + 1
         parameters per start).  ``theta0`` is [F, d + 1], [d + 1], [F, 2] or [2]; with two entries the common log l is repeated for all d
-        features.  Returns x [F, d + 1].  The leave-one-out / leave-block-out scores over per-feature scales have no lockstep form:
-        ``optimize_ard`` minimises them one data set at a time."""
+        features.  Returns x [F, d + 1].  The leave-one-out scores over per-feature scales in lockstep: ``optimize_ard_batch``; the
+        leave-block-out scores have no lockstep form, ``optimize_ard`` minimises them one data set at a time."""
         from .optim import bfgs_lockstep, newton_lockstep
         if ard and criterion != "nlml":
-            raise ValueError("optimize_batch(ard=True): criterion must be 'nlml' (optimize_ard minimises the leave-one-out and leave-block-out scores over "
-                             "per-feature scales, one data set at a time)")
+            raise ValueError("optimize_batch(ard=True): criterion must be 'nlml' (optimize_ard_batch minimises the leave-one-out scores over per-feature "
+                             "scales in lockstep; optimize_ard the leave-one-out and leave-block-out scores, one data set at a time)")
         if ard and self.kernel == "netdiffusion":
             raise ValueError("optimize_batch(ard=True): per-feature length scales cover the RBF / Matern kernels")
         if criterion != "nlml" and criterion not in L.LOO_CRITERIA:
