@@ -272,7 +272,7 @@ int sigp_set_length_scales(sigp_handle* h, const double* ell, int64_t d);
  * those hyper-parameters with the scales set: sigp_predict, sigp_predict_ride, sigp_loo, sigp_cv, sigp_predict_cov work on it.  Device
  * work is accounted under SIGP_KC_MLII (the triangular inversion, U U^T, the pass: one entry each).
  * Lockstep groups of such fits: sigp_nlml_grad_ard_batch (the ARD gradients of the leave-one-out scores are sigp_loo_grad_ard's and, in
- * lockstep groups, sigp_loo_grad_ard_batch's; those of the leave-block-out scores sigp_cv_grad_ard's, single fits only).  Not covered: the one-workgroup kernel (sigp_small_*), the fp32 engine,
+ * lockstep groups, sigp_loo_grad_ard_batch's; those of the leave-block-out scores sigp_cv_grad_ard's and sigp_cv_grad_ard_batch's).  Not covered: the one-workgroup kernel (sigp_small_*), the fp32 engine,
  * sharded fits. */
 int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int grad_mode, double* nlml, double* grad);
 
@@ -298,8 +298,8 @@ int sigp_nlml_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64
  * SIGP_BAD_ARG: before sigp_batch_upload, an fp32 handle, the reference kernel, ntheta != d + 1, a leading dimension below its width.
  * Device work is accounted under SIGP_KC_MLII, the staging under SIGP_KC_KBUILD.  Both calls leave the handle unfitted, as the other batch
  * entries do, and neither read nor change the single-fit scales of sigp_set_length_scales.
- * The leave-one-out scores and their ARD gradients for lockstep groups: sigp_loo_grad_ard_batch.  Not covered: ARD gradients of the
- * leave-block-out scores for lockstep groups, sigp_small_*, the fp32 engine, sharded fits. */
+ * The leave-one-out and leave-block-out scores and their ARD gradients for lockstep groups: sigp_loo_grad_ard_batch,
+ * sigp_cv_grad_ard_batch.  Not covered: sigp_small_*, the fp32 engine, sharded fits. */
 int sigp_batch_run_ard(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, int64_t ldell, const double* sn_tilde,
                        double* out, double* mean, double* var);
 int sigp_nlml_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
@@ -386,7 +386,7 @@ int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_
  * SIGP_BAD_ARG: before sigp_batch_upload, count < 1, an fp32 handle, the reference kernel, n < 2, ntheta != d + 1, a leading dimension
  * below its width, a bad sigma_mode or criterion, mean without var.  Device work is accounted under SIGP_KC_MLII, the staging under
  * SIGP_KC_KBUILD.  The handle is left unfitted, as after the other batch entries.
- * Not covered: the leave-block-out scores in lockstep groups, sigp_small_*, the fp32 engine, sharded fits. */
+ * The leave-block-out scores in lockstep groups: sigp_cv_grad_ard_batch.  Not covered: sigp_small_*, the fp32 engine, sharded fits. */
 int sigp_loo_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
                             int sigma_mode, int criterion, double* mean, double* var, int64_t nstride, double* score, double* grad, int64_t ldgrad);
 /* sigp_small_run with the leave-one-out cross-validation of every fit in the SAME single launch (L~^-1 formed in LDS over L~ as in
@@ -452,9 +452,36 @@ int sigp_small_run_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, c
  * SIGP_NOT_SPD: a non-SPD K~, an exp(theta[k]) that is not finite and positive, or a fold whose P_SS fails its pivot test: +inf in score and
  * every grad entry, NaN in mean / var.  Afterwards the handle is fitted at those hyper-parameters with the scales set, as after
  * sigp_loo_grad_ard.
- * Not covered: the lockstep-batch entries (and optimize_batch), sigp_small_*, the reference kernel, the fp32 engine, sharded fits. */
+ * Lockstep groups of such fits: sigp_cv_grad_ard_batch (below).  Not covered: sigp_small_*, the reference kernel, the fp32 engine, sharded
+ * fits. */
 int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int64_t block, int64_t gap, int sigma_mode,
                      int criterion, double* mean, double* var, double* score, double* grad);
+/* ... for lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2, fp64): what sigp_cv_batch does, with scales
+ * per FIT and every other convention as in sigp_loo_grad_ard_batch -- fit i uses data set (first + i) % batch and theta_i =
+ * theta[i ldtheta .. + ntheta) = (log l_1 .. log l_d, log sn~), ntheta = d + 1; two members of one group may share a data set and differ in
+ * scales.  block, gap and the fold limits as sigp_cv, on the batch's n.  score [count][2] = nlpd, sse; mean / var [count][nstride >= n]
+ * (both or neither); grad [count][ldgrad >= d + 1], the derivatives of the score `criterion` names, or NULL: scores and predictions only,
+ * no cubic work beyond sigp_cv_batch's.  Groups of `group` members (sigp_set_option) run one after another.  Per group:
+ * sigp_batch_run_ard's staging launch, the isotropic entries' fit at ell = 1 on the staged features and sigp_cv_batch's launches on it --
+ * the scores and predictions carry the bits sigp_cv_batch returns on data sets X / l uploaded as they are, at ell = 1 --, with, per pass of
+ * 1024 / members folds of every member, the fold adjoints beta_f, B_f, eps_f of all (member, fold) pairs in one launch and their assembly
+ * into every member's beta and band store in another; then for every member at once K~^-1 = U U^T, a = U z, eps, v = P beta, P B over
+ * B's band, ONE cubic product M = (P B) P^T per member (n^3 flops, whatever d and the folds) and sigp_loo_grad_ard's tile pass and
+ * fixed-order sums with the member on a grid axis.  Every entry of beta and B adds its folds' terms in ascending fold order in one chain
+ * from zero, however the folds are split into passes (no atomics): the same bits on every run, whatever the group size, and a member
+ * executes a single fit's instructions and carries the bits sigp_cv_grad_ard returns for it wherever the lockstep factorisation has the
+ * single fit's bits.  One copy brings a group's gradients back.  A member whose exp(theta) overflows, one of whose scales underflows to 0,
+ * whose K~ is not SPD or one of whose folds' P_SS fails its pivot test gets +inf in both scores and all d + 1 gradient entries and NaN rows
+ * in mean / var; its group mates are unaffected and the call returns SIGP_OK.
+ * Memory beside the slot: three matrices of 8 group n_pad^2 bytes (L~^-T / M, K~^-1, P B), the staging area, sigp_cv_batch's work buffers,
+ * per member a band store (8 x 384 n_pad bytes) and eps_f, and B_f / beta_f of one pass of at most 1024 (member, fold) pairs.
+ * SIGP_BAD_ARG: everything sigp_loo_grad_ard_batch refuses, and sigp_cv's fold checks (block + 2 gap <= SIGP_CV_MAX_WINDOW, every fold
+ * leaves a training row).  Device work is accounted under SIGP_KC_MLII (sigp_cv_grad_ard's entries, their figures times the members), the
+ * staging under SIGP_KC_KBUILD.  The handle is left unfitted, as after the other batch entries.
+ * Not covered: sigp_small_*, the reference kernel, the fp32 engine, sharded fits. */
+int sigp_cv_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
+                           int64_t block, int64_t gap, int sigma_mode, int criterion, double* mean, double* var, int64_t nstride, double* score,
+                           double* grad, int64_t ldgrad);
 
 /* One large fit sharded over the GPUs of a node (BASELINE configs[3] fp64, configs[4] fp32 + fp64 refinement): 1-D block-cyclic
  * ownership of outer panels (W column blocks of 128; panel q belongs to rank q % nranks), OWNER-ONLY storage -- a rank allocates,

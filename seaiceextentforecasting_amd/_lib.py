@@ -72,6 +72,7 @@ SIGNATURES = {
     "sigp_loo_grad_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _i64, _dp, _dp]),
     "sigp_loo_grad_ard": (C.c_int, [_h, C.c_int, _dp, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "sigp_loo_grad_ard_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _i64, _dp, _dp, _i64]),
+    "sigp_cv_grad_ard_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_small_run_loo": (C.c_int, [_h, _i64, _ip64, _dp, _dp, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_cv": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _dp]),
     "sigp_cv_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64, _dp]),

@@ -22,6 +22,11 @@
 //                            columns in which B's block row is not zero (6 x 128 n_pad^2 flops)
 // B lives in a band store: row i holds the three 128-column blocks around its own, [n_pad][384].  Rows and columns n .. n_pad of every
 // operand are masked.  No atomics anywhere: the same bits on every run.
+// Lockstep members (sigp_cv_grad_ard_batch): every kernel below takes the member from a grid dimension and adds the member's offsets -- P and
+// P B n_pad^2 apart, the band stores n_pad x 384 apart, the vectors LooArdGroupVecs::mstride() apart, eps_f F apart, q in the slot's result
+// rows -- to its pointers before anything is read: uniform values, no vector register, and a member executes the instructions a single fit
+// does.  B_f and beta_f lie at the (member, fold) pair index of cv_strip_finish_kernel and cv_close_kernel.  The single fit launches one
+// member with zero strides.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,8 +46,9 @@ static_assert(CVA_BAND == SL_BAND && CV_MAXW == SL_BLK, "score_layout.hpp lays t
 __device__ __forceinline__ int cva_first_fold(int x, int block, int gap) { return x >= gap ? (x - gap) / block : 0; }
 __device__ __forceinline__ int cva_last_fold(int x, int block, int gap, int F) { const int f = (x + gap) / block; return f < F ? f : F - 1; }
 
-// grid = folds of this pass, 256 threads, dynamic LDS = wp * mp doubles (wp / mp: the widest window / scored block of the launch rounded up
-// to 16).  X [fold][128][128] = M^-1 (lower; only the window's w x w corner is read, by SELECT), av [fold][128] = a_S, q = y^T A~ from *q.
+// grid = (folds of this pass, members), 256 threads, dynamic LDS = wp * mp doubles (wp / mp: the widest window / scored block of the launch rounded up
+// to 16).  X [pair][128][128] = M^-1 (lower; only the window's w x w corner is read, by SELECT), av [pair][128] = a_S, q = y^T A~ from
+// q[member * sQ]; B_f and beta_f at the pair index, eps_f at [member * sE][fold].
 //   t0 = X a_S, r = X^T t0, g_i = H_ii = sum_k X_ki^2, s, var, kappa, rbar, sbar        as cv_close_kernel forms them
 //   Hc = X^T X[:, C]          [w][m] into LDS: subtile (ti, tj) by one wave, D = A B^T with A = columns 16 ti .. of X, B = columns
 //                             c0 - r0 + 16 tj .. of X, K = the window's rows from 16 ti on
@@ -51,14 +57,17 @@ __device__ __forceinline__ int cva_last_fold(int x, int block, int gap, int F) {
 // A lane's accumulator register e is row lq + 4 e, column lr of the subtile (Num<double>::drow).  Rows beyond the window give zeros.
 __global__ __launch_bounds__(256) void cv_adj_fold_kernel(const double* __restrict__ X, const double* __restrict__ av, const double* __restrict__ q,
                                                           int mode, int crit, int n, int block, int gap, int f0, int wp, int mp,
-                                                          double* __restrict__ Bf, double* __restrict__ betaf, double* __restrict__ epsf) {
+                                                          double* __restrict__ Bf, double* __restrict__ betaf, double* __restrict__ epsf, long sQ = 0,
+                                                          long sE = 0) {
   extern __shared__ __attribute__((aligned(16))) double Hc[];       // [wp][mp]
   __shared__ double sa[CV_MAXW], st[CV_MAXW], sr[CV_MAXW], sg[CV_MAXW], srb[CV_MAXW], ssk[CV_MAXW], stt[CV_MAXW], sh[4], s_sc[2];
-  const long idx = blockIdx.x;
+  const long idx = (long)blockIdx.y * gridDim.x + blockIdx.x;
   X += idx * CV_MAXW * CV_MAXW;
+  av += idx * CV_MAXW;
   Bf += idx * (long)wp * wp;
   betaf += idx * wp;
-  const double qq = q[0];
+  epsf += (long)blockIdx.y * sE;
+  const double qq = q[(long)blockIdx.y * sQ];
   int r0, r1, c0, c1;
   cv_window(n, block, gap, f0 + (int)blockIdx.x, r0, r1, c0, c1);
   const int w = r1 - r0, m = c1 - c0, cl = c0 - r0;
@@ -66,7 +75,7 @@ __global__ __launch_bounds__(256) void cv_adj_fold_kernel(const double* __restri
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nt = (w + 15) >> 4, mt = (m + 15) >> 4;
   if (tid < CV_MAXW) {
-    sa[tid] = av[idx * CV_MAXW + tid];
+    sa[tid] = av[tid];
     st[tid] = 0.0; srb[tid] = 0.0; ssk[tid] = 0.0;
   }
   __syncthreads();
@@ -157,12 +166,19 @@ __global__ __launch_bounds__(256) void cv_adj_fold_kernel(const double* __restri
   }
 }
 
-// grid = the rows [row0, row0 + gridDim.x) that the folds [f0, f0 + nf) of this pass touch, 128 threads.  Entry (i, j) of B (band column
+// grid = (the rows [row0, row0 + gridDim.x) that the folds [f0, f0 + nf) of this pass touch, members), 128 threads; the member's B_f and
+// beta_f of the pass begin at pair member * nf, its band store and beta at member * sBand and member * sBeta.  Entry (i, j) of B (band column
 // jj = j - 128 (i / 128 - 1)) adds B_f[i - r0_f][j - r0_f], read from the computed lower triangle at (max, min), of every fold of the pass whose
-// window holds both rows, in ascending fold order, to what the earlier passes left there; beta_i likewise.  Rows and columns from n on stay zero.
+// window holds both rows, in ascending fold order, to what the earlier passes left there; beta_i likewise: one chain of additions from
+// zero in ascending fold order however the folds are split into passes, so the split does not show in the bits.  Rows and columns from n
+// on stay zero.
 __global__ __launch_bounds__(128) void cv_adj_gather_kernel(const double* __restrict__ Bf, const double* __restrict__ betaf, int wp, int n, int block,
                                                             int gap, int F, int f0, int nf, int row0, double* __restrict__ band,
-                                                            double* __restrict__ beta) {
+                                                            double* __restrict__ beta, long sBand = 0, long sBeta = 0) {
+  {
+    const long mb = blockIdx.y;
+    Bf += mb * nf * wp * wp; betaf += mb * nf * wp; band += mb * sBand; beta += mb * sBeta;
+  }
   const int i = row0 + (int)blockIdx.x;
   if (i >= n) return;
   const int jb = (i / SY_T - 1) * SY_T;
@@ -197,9 +213,11 @@ __global__ __launch_bounds__(128) void cv_adj_gather_kernel(const double* __rest
   }
 }
 
-// one block: eps = epsf[0] + epsf[1] + ..  in that order (chunks of 256 through LDS, added by thread 0)
-__global__ __launch_bounds__(256) void cv_adj_eps_kernel(const double* __restrict__ epsf, int F, double* __restrict__ eps) {
+// one block per member: eps = epsf[0] + epsf[1] + ..  in that order (chunks of 256 through LDS, added by thread 0)
+__global__ __launch_bounds__(256) void cv_adj_eps_kernel(const double* __restrict__ epsf, int F, double* __restrict__ eps, long sE = 0, long sW = 0) {
   __shared__ double sh[256];
+  epsf += (long)blockIdx.x * sE;
+  eps += (long)blockIdx.x * sW;
   double acc = 0.0;
   for (int f0 = 0; f0 < F; f0 += 256) {
     __syncthreads();
@@ -214,8 +232,13 @@ __global__ __launch_bounds__(256) void cv_adj_eps_kernel(const double* __restric
 }
 
 // One WAVE per row i < n_pad of the full P:  v_i = sum_{k < n} P_ik beta_k (zero for i >= n), and the entries of P in rows or columns
-// n .. n_pad are set to zero, so that the two products that follow see masked operands.
-__global__ __launch_bounds__(256) void cv_adj_v_kernel(double* __restrict__ P, long ld, int n, int n_pad, const double* __restrict__ beta, double* __restrict__ v) {
+// n .. n_pad are set to zero, so that the two products that follow see masked operands.  blockIdx.y = lockstep member.
+__global__ __launch_bounds__(256) void cv_adj_v_kernel(double* __restrict__ P, long ld, int n, int n_pad, const double* __restrict__ beta, double* __restrict__ v,
+                                                       long sP = 0, long sW = 0) {
+  {
+    const long mb = blockIdx.y;
+    P += mb * sP; beta += mb * sW; v += mb * sW;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave;
   if (i >= n_pad) return;
@@ -242,10 +265,14 @@ __global__ __launch_bounds__(256) void cv_adj_v_kernel(double* __restrict__ P, l
 // grid = (T, T) tiles (bj, bi) of C = P B, every one written whole.  Tile (bi, bj) = rows bi of P against rows bj of the band store (B is
 // symmetric: its rows are its columns) over the block columns k0 = max(bj - 1, 0) .. min(bj + 2, T) of P, which are the band columns from
 // 128 (k0 - bj + 1) on.  The tile loop is syrk128_tile's SET form: LDS-DMA staging, two-buffer pipeline, v_mfma_f64_16x16x4_f64; 64 KiB of
-// LDS, two workgroups per CU, as syrk128_kernel.
+// LDS, two workgroups per CU, as syrk128_kernel.  blockIdx.z = lockstep member.
 __global__ __launch_bounds__(256, 2) void cv_band_product_kernel(const double* __restrict__ P, long ldp, const double* __restrict__ band, double* __restrict__ C,
-                                                                 long ldc, int T) {
+                                                                 long ldc, int T, long sP = 0, long sBand = 0) {
   constexpr int KTe = Num<double>::KT;
+  {
+    const long mb = blockIdx.z;
+    P += mb * sP; band += mb * sBand; C += mb * sP;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* As = (double*)smem_raw;        // [2][128][KT]
   double* Bs = As + 2 * SY_T * KTe;      // [2][128][KT]

@@ -10,13 +10,14 @@
 //                       MliiParts            sigp_nlml_grad
 //                       MliiGroupParts       sigp_nlml_grad_batch
 //                       ArdParts             sigp_nlml_grad_ard, sigp_nlml_grad_ard_batch
-//                       LooArdGroupParts     sigp_loo_grad_ard_batch: ScoreParts of G members, then ArdParts of G members
+//                       LooArdGroupParts     sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch: ScoreParts of G members, then ArdParts of G members
 //   gV                  LooGradVecs          sigp_loo_grad(_batch)
 //                       LooArdVecs           sigp_loo_grad_ard, sigp_cv_grad_ard
-//                       LooArdGroupVecs      sigp_loo_grad_ard_batch: G LooArdVecs at an even member stride
+//                       LooArdGroupVecs      sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch: G LooArdVecs at an even member stride
 //   cvPart cvBlk cvVec  CvWork               cv_launch
 //   cvAdj               CvAdjStore           sigp_cv_grad_ard; it fills the CvAdjoint that cv_launch and the kernels take
-//   bStage              ArdStage             sigp_batch_run_ard, sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch
+//                       CvAdjGroupStore      sigp_cv_grad_ard_batch: the same pieces for the nb members of a lockstep group
+//   bStage              ArdStage             sigp_batch_run_ard, sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch
 // gU, gK, gD [G][n_pad][n_pad], scratchZ and ardXc are used whole: they have no layout beyond their size.
 // Everything is in doubles.  n_pad is a multiple of 128, dp of 64, wp of 16.
 #pragma once
@@ -153,14 +154,16 @@ struct CvWork {
 };
 
 // ---- cvAdj -----------------------------------------------------------------------------------------------------------------------------------
-// What cv_launch does for the gradient when it is given one of these (sigp_cv_grad_ard): the fold adjoints of each pass and their assembly.
+// What cv_launch does for the gradient when it is given one of these (sigp_cv_grad_ard, sigp_cv_grad_ard_batch): the fold adjoints of each
+// pass and their assembly.  Of a lockstep group: member m's band store, beta and eps_f at m times the strides; a single fit has zero strides.
 struct CvAdjoint {
   int crit;          // 0 nlpd, 1 sse
-  double* Bf;        // [folds of a pass][wp][wp]  (lower 16 x 16 subtiles written)
-  double* betaf;     // [folds of a pass][wp]
-  double* epsf;      // [F]
-  double* band;      // [n_pad][CVA_BAND], zero before the first pass
-  double* beta;      // [n_pad], zero before the first pass
+  double* Bf;        // [(member, fold) pairs of a pass][wp][wp]  (lower 16 x 16 subtiles written)
+  double* betaf;     // [pairs of a pass][wp]
+  double* epsf;      // [members][F]
+  double* band;      // [members][n_pad][CVA_BAND], zero before the first pass
+  double* beta;      // [n_pad] per member, zero before the first pass
+  long sBand = 0, sBeta = 0, sEps = 0;
 };
 
 // The adjoint store of F folds worked off in passes of FP: the band store [n_pad][384], B_f [FP][wp][wp] and beta_f [FP][wp] of one pass, eps_f [F]
@@ -172,7 +175,27 @@ struct CvAdjStore {
   __host__ __device__ double* betaf() const { return Bf() + FP * wp * wp; }
   __host__ __device__ double* epsf() const { return betaf() + FP * wp; }
   // ... as cv_launch takes it; beta [n_pad] lives with the pass's other vectors (LooArdVecs::beta)
-  __host__ __device__ CvAdjoint adjoint(int crit, double* beta) const { return CvAdjoint{crit, Bf(), betaf(), epsf(), band(), beta}; }
+  __host__ __device__ CvAdjoint adjoint(int crit, double* beta) const { return CvAdjoint{crit, Bf(), betaf(), epsf(), band(), beta, 0, 0, 0}; }
+};
+
+// ... of the nb members of a lockstep group, each worked off in passes of FP folds (cv_launch: FP = CvWork::blocks / nb): the band stores
+// [nb][n_pad][384], B_f [nb FP][wp][wp] and beta_f [nb FP][wp] of one pass at the (member, fold) pair index, eps_f [nb][F].  The layout
+// depends on nb, as CvWork's: every group lays its own view over the arena, which the entry grows for the groups it will run (of G members
+// and the tail).  One member is CvAdjStore, piece for piece.  The band stores are read in 16-byte pairs: their stride n_pad x 384 is even;
+// eps_f is read one double at a time.  beta lives with the pass's other vectors, at LooArdGroupVecs' even stride.
+struct CvAdjGroupStore {
+  double* base; long nb, n_pad, FP, wp, F;
+  __host__ __device__ static long size(long nb, long n_pad, long FP, long wp, long F) { return nb * (n_pad * SL_BAND + FP * (wp * wp + wp) + F); }
+  __host__ __device__ long band_stride() const { return n_pad * SL_BAND; }
+  __host__ __device__ long eps_stride() const { return F; }
+  __host__ __device__ double* band() const { return base; }
+  __host__ __device__ double* Bf() const { return band() + nb * band_stride(); }
+  __host__ __device__ double* betaf() const { return Bf() + nb * FP * wp * wp; }
+  __host__ __device__ double* epsf() const { return betaf() + nb * FP * wp; }
+  // ... as cv_launch takes it; beta = member 0's (LooArdGroupVecs::member(0).beta()), the others sBeta = LooArdGroupVecs::mstride() apart
+  __host__ __device__ CvAdjoint adjoint(int crit, double* beta, long sBeta) const {
+    return CvAdjoint{crit, Bf(), betaf(), epsf(), band(), beta, band_stride(), sBeta, eps_stride()};
+  }
 };
 
 // ---- bStage ----------------------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 // and finish kernel with the member on grid.y -- partials per (member, tile), fixed-order sums, no atomics.
 // Both entries run their groups one after another on slot 0, as the score entries do.  Profile classes: the staging SIGP_KC_KBUILD, the
 // gradient's work SIGP_KC_MLII.  The leave-one-out scores and their ARD gradients for groups: sigp_looardbatch.inc, on this file's staging.
-// Out of scope: ARD gradients of the leave-block-out scores for groups, sigp_small_*, the fp32 engine, sharded fits.  Included inside
+// The leave-block-out scores and their ARD gradients for groups: sigp_cvardbatch.inc.  Out of scope: sigp_small_*, the fp32 engine, sharded fits.  Included inside
 // extern "C" of sigp.hip, after sigp_ardgrad.inc.
 
 // the staging area of slot s (ArdStage, score_layout.hpp), sized for the slot's capacity

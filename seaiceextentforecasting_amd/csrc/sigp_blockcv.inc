@@ -54,8 +54,9 @@ static int cv_work_ensure(sigp_handle* h, long n, long block, long gap, int G, i
 }
 
 // the launcher the single and the lockstep entry points share (arguments as loo_launch; cw = cv_work of this nb); results in sp as loo_launch leaves them.
-// adj (sigp_cv_grad_ard, nb = 1 only; cvard.hpp): after every pass's closing solves, the fold adjoints of that pass and their assembly
-// into adj->band / adj->beta -- Xb and av are overwritten by the next pass.  With adj = nullptr the launches are those of sigp_cv.
+// adj (sigp_cv_grad_ard, sigp_cv_grad_ard_batch; cvard.hpp): after every pass's closing solves, the fold adjoints of that pass and their
+// assembly into every member's adj->band / adj->beta -- Xb and av are overwritten by the next pass.  With adj = nullptr the launches are
+// those of sigp_cv.
 static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD,
                      const double* y, long sY, const KParams* kps, const double* q, long sQ, int mode, ScoreParts sp, CvWork cw, int block, int gap,
                      const CvAdjoint* adj = nullptr) {
@@ -99,25 +100,26 @@ static int cv_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad,
                          (int)n, block, gap, (int)f0, sp.base, n_pad, sp.mstride());
       HIPCHK(h, hipGetLastError());
     }
-    if (adj && nb == 1) {
+    if (adj) {
       const int mp = (int)round_up(std::min<long>(n, block), 16);
       const int lds = wp * mp * (int)sizeof(double);
       {
         ProfScope ps(h, st, SIGP_KC_MLII, wf * (2.0 * wmax * wmax * mp + (adj->crit == 0 ? 1.0 * wmax * wmax * mp : 0.0) + 4.0 * wmax * wmax), wf * 8.0 * (1.5 * wmax * wmax + wmax));
         static AttrOnce a_attr;
         HIPCHK(h, a_attr.set(h->device, (const void*)cv_adj_fold_kernel, CV_MAXW * CV_MAXW * (int)sizeof(double)));
-        hipLaunchKernelGGL(cv_adj_fold_kernel, dim3(nf), dim3(256), (size_t)lds, st, (const double*)Xb, (const double*)av, q, mode, adj->crit, (int)n, block, gap,
-                           (int)f0, wp, mp, adj->Bf, adj->betaf, adj->epsf);
+        hipLaunchKernelGGL(cv_adj_fold_kernel, dim3(nf, (unsigned)nb), dim3(256), (size_t)lds, st, (const double*)Xb, (const double*)av, q, mode, adj->crit, (int)n, block, gap,
+                           (int)f0, wp, mp, adj->Bf, adj->betaf, adj->epsf, sQ, adj->sEps);
         HIPCHK(h, hipGetLastError());
       }
       {
         int r0, r1, c0, c1, rl0, rl1;
         cv_window((int)n, block, gap, (int)f0, r0, r1, c0, c1);
         cv_window((int)n, block, gap, (int)(f0 + nf - 1), rl0, rl1, c0, c1);
-        const double nterm = (2.0 * gap / block + 1.0);
-        ProfScope ps(h, st, SIGP_KC_MLII, (double)(rl1 - r0) * CVA_BAND * nterm, (double)(rl1 - r0) * CVA_BAND * 8.0 * (2.0 + nterm));
-        hipLaunchKernelGGL(cv_adj_gather_kernel, dim3((unsigned)(rl1 - r0)), dim3(128), 0, st, (const double*)adj->Bf, (const double*)adj->betaf, wp, (int)n, block, gap,
-                           (int)F, (int)f0, (int)nf, r0, adj->band, adj->beta);
+        // 2 gap / block + 1 terms per entry; the division last, so that the figures of nb members are nb times one member's where it is exact
+        const double ent = (double)nb * (rl1 - r0) * CVA_BAND;
+        ProfScope ps(h, st, SIGP_KC_MLII, ent * (2.0 * gap + block) / block, ent * 8.0 * (2.0 * gap + 3.0 * block) / block);
+        hipLaunchKernelGGL(cv_adj_gather_kernel, dim3((unsigned)(rl1 - r0), (unsigned)nb), dim3(128), 0, st, (const double*)adj->Bf, (const double*)adj->betaf, wp, (int)n, block, gap,
+                           (int)F, (int)f0, (int)nf, r0, adj->band, adj->beta, adj->sBand, adj->sBeta);
         HIPCHK(h, hipGetLastError());
       }
     }

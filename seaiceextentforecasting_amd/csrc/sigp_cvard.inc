@@ -15,7 +15,47 @@
 // Memory: sigp_loo_grad's single-fit buffers (gU, gK, gD, gV, gPart), ardXc, sigp_cv's workspaces and cvAdj: the band store, B_f / beta_f of one
 // pass and eps_f.  Profile class: SIGP_KC_MLII (on top of cv_launch's entries: two per pass, then U U^T, the n^2 passes, the banded
 // product, the product M, the ARD pass: one entry each).
-// Out of scope: the lockstep-batch entries, sigp_small_*, the reference kernel, the fp32 engine, sharded fits.
+// Out of scope: sigp_small_*, the reference kernel, the fp32 engine, sharded fits.  Lockstep groups: sigp_cv_grad_ard_batch
+// (sigp_cvardbatch.inc), which runs the steps below -- cv_adj_zero, cv_launch with the adjoint, cv_ard_products -- with a member axis.
+
+// The adjoint's accumulators of nb members before cv_launch's first pass: the band stores (contiguous) and every member's beta
+static int cv_adj_zero(sigp_handle* h, hipStream_t st, int nb, long n_pad, const CvAdjoint& adj) {
+  HIPCHK(h, hipMemsetAsync(adj.band, 0, (size_t)((nb - 1) * adj.sBand + n_pad * CVA_BAND) * sizeof(double), st));
+  for (int b = 0; b < nb; ++b) HIPCHK(h, hipMemsetAsync(adj.beta + b * adj.sBeta, 0, (size_t)n_pad * sizeof(double), st));
+  return SIGP_OK;
+}
+
+// The gradient's steps between cv_launch (with adj) and the ARD pass, for nb lockstep members: P into gK, a, eps and v into the members'
+// vectors (w = member 0's, the others sW apart; z = the members' solved ride row 0, sZ apart), P B into gD, M = (P B) P^T into gU.  One
+// member with zero strides is the single fit.  Four profile entries, their figures times nb.
+static int cv_ard_products(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, long F, const double* z, long sZ, const CvAdjoint& adj, LooArdVecs w, long sW) {
+  const long ld = n_pad, sP = n_pad * n_pad;
+  const int T = (int)(n_pad / NB);
+  int rc;
+  if ((rc = kinv_lower(h, st, nb, n_pad))) return rc;
+  {   // a = U z;  P -> full;  eps;  v = P beta (and the padding of P zeroed)
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * 4.0 * n_pad * n_pad, nb * 28.0 * n_pad * n_pad);
+    if ((rc = alpha_from_U(h, st, nb, z, sZ, w.a(), sW, n_pad))) return rc;
+    if ((rc = mirror_P(h, st, nb, n_pad))) return rc;
+    hipLaunchKernelGGL(cv_adj_eps_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)adj.epsf, (int)F, w.eps(), adj.sEps, sW);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(cv_adj_v_kernel, dim3((unsigned)(n_pad / 4), (unsigned)nb), dim3(256), 0, st, h->gK, ld, (int)n, (int)n_pad, (const double*)w.beta(), w.v(), sP, sW);
+    HIPCHK(h, hipGetLastError());
+  }
+  {   // P B: tile (bi, bj) = rows bi of P against rows bj of the band store, the K window of B's three block columns
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * (2.0 * n_pad * n_pad * CVA_BAND), nb * (8.0 * n_pad * n_pad));
+    static AttrOnce b_attr;
+    HIPCHK(h, b_attr.set(h->device, (const void*)cv_band_product_kernel, SY_LDS_BYTES));
+    hipLaunchKernelGGL(cv_band_product_kernel, dim3((unsigned)T, (unsigned)T, (unsigned)nb), dim3(256), SY_LDS_BYTES, st, (const double*)h->gK, ld, (const double*)adj.band, h->gD,
+                       ld, T, sP, adj.sBand);
+    HIPCHK(h, hipGetLastError());
+  }
+  {   // M = (P B) P^T: tile (bi, bj), bi >= bj, = rows bi of P B against rows bj of P (= its columns), the whole K span
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n_pad * n_pad * (n_pad + NB)), 0.0);
+    if ((rc = syrk_set(h, st, nb, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
+  }
+  return SIGP_OK;
+}
 
 int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int64_t block, int64_t gap, int sigma_mode, int criterion, double* mean,
                      double* var, double* score, double* grad) {
@@ -37,7 +77,6 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
   Slot& s = h->slots[0];
   hipStream_t st = s.s_upd;
   const long n = h->n, n_pad = h->n_pad, ld = n_pad;
-  const int T = (int)(n_pad / NB);
   const long F = (n + block - 1) / block, FP = std::min<long>(F, CV_PASS_BLOCKS);
   const long wp = round_up(std::min<long>(n, block + 2 * gap), 16);
   if ((rc = ard_scores_ensure(h, grad != nullptr))) return rc;
@@ -49,8 +88,7 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
   CvAdjoint adj{};
   if (grad) {
     adj = CvAdjStore{h->cvAdj, n_pad, FP, wp, F}.adjoint(criterion, w.beta());
-    HIPCHK(h, hipMemsetAsync(adj.band, 0, (size_t)n_pad * CVA_BAND * sizeof(double), st));
-    HIPCHK(h, hipMemsetAsync(adj.beta, 0, (size_t)n_pad * sizeof(double), st));
+    if ((rc = cv_adj_zero(h, st, 1, n_pad, adj))) return rc;
   }
   if ((rc = scores_stage_q(h, st, sp))) return rc;
   if ((rc = cv_launch(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, h->y, 0, nullptr, sp.q(), 0, sigma_mode, sp, cv_work(h, 1, n, block, gap), (int)block, (int)gap,
@@ -63,27 +101,7 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
   };
   if (!grad) return finish();
 
-  if ((rc = kinv_lower(h, st, 1, n_pad))) return rc;
-  {   // a = U z;  P -> full;  eps;  v = P beta (and the padding of P zeroed)
-    ProfScope ps(h, st, SIGP_KC_MLII, 4.0 * n_pad * n_pad, 28.0 * n_pad * n_pad);
-    if ((rc = alpha_from_U(h, st, 1, s.mat + n_pad * ld, 0, w.a(), 0, n_pad))) return rc;
-    if ((rc = mirror_P(h, st, 1, n_pad))) return rc;
-    hipLaunchKernelGGL(cv_adj_eps_kernel, dim3(1), dim3(256), 0, st, (const double*)adj.epsf, (int)F, w.eps());
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(cv_adj_v_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, st, h->gK, ld, (int)n, (int)n_pad, (const double*)w.beta(), w.v());
-    HIPCHK(h, hipGetLastError());
-  }
-  {   // P B: tile (bi, bj) = rows bi of P against rows bj of the band store, the K window of B's three block columns
-    ProfScope ps(h, st, SIGP_KC_MLII, 2.0 * n_pad * n_pad * CVA_BAND, 8.0 * n_pad * n_pad);
-    static AttrOnce b_attr;
-    HIPCHK(h, b_attr.set(h->device, (const void*)cv_band_product_kernel, SY_LDS_BYTES));
-    hipLaunchKernelGGL(cv_band_product_kernel, dim3((unsigned)T, (unsigned)T), dim3(256), SY_LDS_BYTES, st, (const double*)h->gK, ld, (const double*)adj.band, h->gD, ld, T);
-    HIPCHK(h, hipGetLastError());
-  }
-  {   // M = (P B) P^T: tile (bi, bj), bi >= bj, = rows bi of P B against rows bj of P (= its columns), the whole K span
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * (n_pad + NB), 0.0);
-    if ((rc = syrk_set(h, st, 1, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
-  }
+  if ((rc = cv_ard_products(h, st, 1, n, n_pad, F, s.mat + n_pad * ld, 0, adj, w, 0))) return rc;
   if ((rc = loo_ard_pass(h, st, kernel_id, w, ap, snt, grad))) return rc;
   return finish();
 }

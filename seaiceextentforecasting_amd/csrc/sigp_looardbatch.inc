@@ -18,96 +18,15 @@
 // Memory beside the slot: gU, gK, gD [G][n_pad][n_pad] as sigp_loo_grad_batch, the staging area, the centred features, LooArdGroupVecs and
 // LooArdGroupParts (score_layout.hpp).  Profile classes: the staging SIGP_KC_KBUILD, the gradient's work SIGP_KC_MLII (sigp_loo_grad_ard's
 // entries, their figures times nb).
-// Out of scope: the leave-block-out scores in groups (cv_launch's adjoint argument is single-member), sigp_small_*, the fp32 engine, sharded fits.
+// Out of scope: sigp_small_*, the fp32 engine, sharded fits.  The leave-block-out scores in groups: sigp_cv_grad_ard_batch.
+// The driver is ard_score_batch (sigp_cvardbatch.inc), which the two entries share: the leave-block-out form differs in the score's launches
+// (cv_launch with the adjoint) and in the steps up to M (cv_ard_products), so it is defined behind sigp_cvard.inc; cv = NULL runs the steps above.
+
+struct CvFolds { int64_t block, gap; };
+static int ard_score_batch(sigp_handle* h, const char* what, const CvFolds* cv, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta,
+                           int64_t ldtheta, int sigma_mode, int criterion, double* mean, double* var, int64_t nstride, double* score, double* grad, int64_t ldgrad);
 
 int sigp_loo_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta, int sigma_mode,
                             int criterion, double* mean, double* var, int64_t nstride, double* score, double* grad, int64_t ldgrad) {
-  if (!h || !theta || !score) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: bad argument (theta [count][ldtheta], score [count][2] required)");
-  int rc;
-  if ((rc = ard_batch_check(h, "loo_grad_ard_batch", first, count, kernel_id))) return rc;
-  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
-  if (criterion != SIGP_LOO_NLPD && criterion != SIGP_LOO_SSE) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: criterion must be SIGP_LOO_NLPD or SIGP_LOO_SSE");
-  if ((mean == nullptr) != (var == nullptr)) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: mean and var come together (both NULL: scores and gradients only)");
-  if (mean && nstride < h->b_n) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: mean / var [count][nstride >= %ld] required", h->b_n);
-  if (h->b_n < 2) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: leave-one-out needs n >= 2 training points");
-  const long n = h->b_n, d = h->b_d, dp = h->b_dp, n_pad = h->b_npad, ld = n_pad;
-  if (ntheta != d + 1) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: theta = (log l_1 .. log l_d, log sn~): %ld entries required (got %lld)", d + 1, (long long)ntheta);
-  if (ldtheta < ntheta) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: ldtheta = %lld below ntheta = %lld", (long long)ldtheta, (long long)ntheta);
-  if (grad && ldgrad < d + 1) return fail(h, SIGP_BAD_ARG, "loo_grad_ard_batch: ldgrad = %lld below d + 1 = %ld", (long long)ldgrad, d + 1);
-  HIPCHK(h, hipSetDevice(h->device));
-  const int G = (int)std::max<long>(1, std::min<long>(h->opt_group, count));
-  const long ntiles = kbuild_tiles(n_pad);
-  const double inf = std::numeric_limits<double>::infinity();
-  Slot& s = h->slots[0];
-  if ((rc = slot_reserve(h, s, n_pad, G))) return rc;
-  hipStream_t st = s.s_upd;
-  h->nslots = std::max(h->nslots, 1);
-  ArdStage a;
-  if ((rc = ard_stage_ensure(h, s, &a))) return rc;
-  if ((rc = scores_ensure(h, G, n_pad, grad ? LooArdGroupParts::size(G, n_pad, ntiles, dp, d + 1) : ScoreParts::size(G, n_pad)))) return rc;
-  if (grad) {
-    if ((rc = scores_grad_ensure(h, G, n_pad, LooArdGroupVecs::size(1, n_pad)))) return rc;
-    if ((rc = scores_mlii_ensure(h, 0, G, n_pad, dp))) return rc;
-  }
-  const LooArdGroupParts gp{h->gPart, G, n_pad, ntiles, dp, d + 1};   // (without a gradient only its ScoreParts are there, and only they are used)
-  const ScoreParts sp = gp.scores();
-  const ArdParts ap = gp.ard();
-  const LooArdGroupVecs gw{h->gV, n_pad, G};
-  const LooArdVecs w = gw.member(0);
-  const LooArdStrides ls{n_pad * n_pad, 512, gw.mstride(), ap.mstride(), d + 1};
-  std::vector<double> hdiv((size_t)(a.cap * (dp + 1))), one((size_t)G, 1.0), ell((size_t)G * d), snt((size_t)G), gh(grad ? (size_t)G * (d + 1) : 0);
-  std::vector<double> mv(mean ? (size_t)G * 2 * n_pad : 0), sc((size_t)G * 2);
-  std::vector<int> ds((size_t)G);
-  std::vector<char> ok((size_t)G);
-  for (int b = 0; b < G; ++b) ds[(size_t)b] = b;             // member b is "data set b" of the staging area
-  for (long g0 = 0; g0 < count; g0 += G) {
-    const int nb = (int)std::min<long>(G, count - g0);
-    for (int b = 0; b < nb; ++b) {
-      const double* th = theta + (g0 + b) * ldtheta;
-      bool good = true;
-      for (long k = 0; k < d; ++k) {
-        const double l = std::exp(th[k]);
-        ell[(size_t)(b * d + k)] = l;
-        if (!std::isfinite(l) || !(l > 0)) good = false;
-      }
-      snt[(size_t)b] = std::exp(th[d]);
-      if (!std::isfinite(snt[(size_t)b])) good = false;
-      if (!good) {                                           // the member rides along at harmless parameters; its results are dropped
-        std::fill(ell.begin() + b * d, ell.begin() + (b + 1) * d, 1.0);
-        snt[(size_t)b] = 1.0;
-      }
-      ok[(size_t)b] = good;
-    }
-    if ((rc = ard_stage_group(h, st, a, nb, ell.data(), d, snt.data(), first + g0, hdiv))) return rc;
-    if ((rc = batch_group_fit_on(h, s, nb, kernel_id, one.data(), snt.data(), ds.data(), a.X, a.y, a.Xs, 0))) return rc;
-    if ((rc = loo_launch(h, st, nb, n, n_pad, s.mat, s.matStride, s.dinv, s.dinvStride, a.y, n_pad, s.kps, s.res, 512, sigma_mode, sp))) return rc;
-    if (grad) {
-      if ((rc = kinv_lower(h, st, nb, n_pad))) return rc;
-      {   // a = U z;  P -> full;  beta, gamma, eps;  v = P beta and P Gamma
-        ProfScope ps(h, st, SIGP_KC_MLII, nb * 4.0 * n_pad * n_pad, nb * 36.0 * n_pad * n_pad);
-        if ((rc = alpha_from_U(h, st, nb, s.mat + n_pad * ld, s.matStride, w.a(), gw.mstride(), n_pad))) return rc;
-        if ((rc = mirror_P(h, st, nb, n_pad))) return rc;
-        hipLaunchKernelGGL(loo_ard_coef_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const double*)h->gK, ld, (int)n, (int)n_pad, (const double*)s.res, sigma_mode, criterion, w, ls);
-        HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(loo_ard_scale_kernel, dim3((unsigned)(n_pad / 4), (unsigned)nb), dim3(256), 0, st, (const double*)h->gK, h->gD, ld, (int)n, (int)n_pad, w, ls);
-        HIPCHK(h, hipGetLastError());
-      }
-      {   // M = (P Gamma) P^T, every member's lower tiles in one launch
-        ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n_pad * n_pad * (n_pad + NB)), 0.0);
-        if ((rc = syrk_set(h, st, nb, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
-      }
-      if ((rc = loo_ard_pass_members(h, st, nb, kernel_id, a.X, n_pad * dp, n, d, dp, n_pad, w, ls, ap.partial(), ap.grad(), 0.0, a.sn, gh.data()))) return rc;
-    }
-    if ((rc = batch_scores_fetch(h, st, nb, sp, mean ? mv.data() : nullptr, sc.data()))) return rc;
-    if ((rc = sync_slot(h, s))) return rc;
-    for (int b = 0; b < nb; ++b) {
-      const long i = g0 + b;
-      const bool good = ok[(size_t)b] && s.info_host[b] == 0;
-      batch_scores_scatter(i, good, &sc[(size_t)2 * b], mean ? &mv[(size_t)b * 2 * n_pad] : nullptr, n, n_pad, mean, var, nstride, score);
-      if (!grad) continue;
-      for (long k = 0; k <= d; ++k) grad[i * ldgrad + k] = good ? gh[(size_t)(b * (d + 1) + k)] : inf;
-    }
-  }
-  h->built = h->factored = h->fitted = false;               // slot 0 no longer holds the single-fit state
-  return SIGP_OK;
+  return ard_score_batch(h, "loo_grad_ard_batch", nullptr, first, count, kernel_id, theta, ntheta, ldtheta, sigma_mode, criterion, mean, var, nstride, score, grad, ldgrad);
 }

@@ -1071,16 +1071,23 @@ class GPR:
         group mates are unaffected.  The gradient pass is ``loo_ard``'s own code: where the lockstep factorisation has the single fit's
         bits (small orders), every fit carries the bits ``loo_ard`` returns for it."""
         if criterion not in L.LOO_CRITERION_IDS:
-            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
+            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse' (the leave-block-out scores 'cv_nlpd' / 'cv_sse': cv_ard_batch)")
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
         if grad not in (None, "exact"):
             raise ValueError("grad must be None or 'exact'")
+        cid = L.LOO_CRITERION_IDS[criterion]
+        return self._ard_score_batch("loo_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: self._lib.sigp_loo_grad_ard_batch(
+            self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+
+    def _ard_score_batch(self, what, theta, grad, group, predictions, cid, call):
+        """What ``loo_ard_batch`` and ``cv_ard_batch`` share after their own checks: the kernel / engine, the staged data, theta's width -- all
+        before any device call -- then the buffers, ``call(theta, F, d, n, mean, var, score, grad)`` and the result."""
         if self.kernel == "netdiffusion" or self.dtype != "f64":
             raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
         d, n = getattr(self, "_batch_d", None), getattr(self, "_batch_n", None)
         if d is None:
-            raise RuntimeError("loo_ard_batch: stage the data sets with upload_batch() first")
+            raise RuntimeError("%s: stage the data sets with upload_batch() first" % what)
         theta = L.f64(np.atleast_2d(theta), 2)
         if theta.shape[1] != d + 1:
             raise ValueError("theta must be [F, d + 1] = [F, %d] (log l_1 .. log l_d, log sn~), got %s" % (d + 1, theta.shape))
@@ -1090,13 +1097,64 @@ class GPR:
         g = np.zeros((F, d + 1)) if grad is not None else None
         mean = np.zeros((F, n)) if predictions else None
         var = np.zeros((F, n)) if predictions else None
-        self._check(self._lib.sigp_loo_grad_ard_batch(self._h, int(first), F, self._kid, L.ptr(theta), d + 1, d + 1, L.LOO_MODES[sigma_f], L.LOO_CRITERION_IDS[criterion],
-                                                      L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1), "loo_ard_batch")
+        self._check(call(theta, F, d, n, mean, var, score, g), what)
         self._fitted = False
-        value = score[:, L.LOO_CRITERION_IDS[criterion]].copy()
+        value = score[:, cid].copy()
         if not predictions:
             return value, g
         return dict(value=value, grad=g, mean=mean, var=var, nlpd=score[:, 0].copy(), sse=score[:, 1].copy())
+
+    def cv_ard_batch(self, theta, block, gap=0, first=0, criterion="cv_nlpd", sigma_f="refit", grad="exact", group=8, predictions=False):
+        """``cv_ard`` for many fits in one device call on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern, fp64):
+        theta [F, d + 1] = (log l_1 .. log l_d, log sn~) per FIT, fit i uses data set (first + i) % B -- two fits may share a data set and
+        differ in scales.  Lockstep groups of ``group`` fits (``sigp_cv_grad_ard_batch``): per group one staging launch, the fit and
+        ``cv_batch``'s launches at ell = 1 on the staged features with the fold adjoints of all (member, fold) pairs of a pass in one
+        launch, then ``cv_ard``'s gradient for all members at once (the banded product, one cubic product per member, one tile pass).
+        Returns (value [F], grad [F, d + 1] or None) with value = the leave-block-out negative log predictive density
+        (``criterion='cv_nlpd'``) or sum of squared errors (``'cv_sse'``) of ``cv(block, gap, sigma_f)``; ``grad=None``: values only, no
+        cubic work beyond ``cv_batch``'s.  ``predictions=True`` returns dict(value, grad, mean [F, n], var [F, n], nlpd [F], sse [F])
+        instead.  A fit whose K~ (or one of whose folds' blocks of K~^-1) is not SPD or whose exp(theta) overflows gets +inf in its value,
+        both scores and all its gradient entries and NaN predictions; its group mates are unaffected.  The folds' terms are added in
+        ascending fold order however a group splits them into passes, and the gradient pass is ``cv_ard``'s own code: where the lockstep
+        factorisation has the single fit's bits (small orders), every fit carries the bits ``cv_ard`` returns for it.
+        block + 2 gap <= 128 and every fold must leave a training row."""
+        if criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse' (the leave-one-out scores: loo_ard_batch)")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "_batch_n", None))
+        cid = L.CV_CRITERION_IDS[criterion]
+        return self._ard_score_batch("cv_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: self._lib.sigp_cv_grad_ard_batch(
+            self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, block, gap, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+
+    def cv_objective_batch(self, theta, block, gap=0, first=0, criterion="cv_nlpd", sigma_f="refit", group=8):
+        """A leave-block-out score over ONE common length scale for many fits in one device call: theta [F, 2] = (log l, log sn~) per fit
+        -> (value [F], grad [F, 2]).  It is ``cv_ard_batch`` at equal scales with d/dlog l = sum_k d/dlog l_k: per fit the bits
+        ``cv_objective`` returns for it where ``cv_ard_batch`` carries ``cv_ard``'s.  A fit whose exp(theta) is not finite (it rides along at
+        harmless parameters) or whose K~ is not SPD gets inf in its value and both gradient entries."""
+        if criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse'")
+        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "_batch_n", None))
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        d = getattr(self, "_batch_d", None)
+        if d is None:
+            raise RuntimeError("cv_objective_batch: stage the data sets with upload_batch() first")
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        if theta.ndim != 2 or theta.shape[1] != 2:
+            raise ValueError("theta must be [F, 2] = (log l, log sn~) per fit, got %s" % (theta.shape,))
+        with np.errstate(over="ignore"):
+            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
+        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
+        th = np.where(ok[:, None], np.concatenate([np.repeat(theta[:, :1], d, axis=1), theta[:, 1:]], axis=1), 0.0)
+        f, g = self.cv_ard_batch(th, block, gap=gap, first=first, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group)
+        f, g = np.array(f, dtype=np.float64), np.array([[np.sum(gi[:-1]), gi[-1]] for gi in g])       # row by row, as cv_objective adds them
+        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
+        f[~ok] = np.inf
+        g[~ok] = np.inf
+        return f, g
 
     def optimize_ard_batch(self, X, y, theta0, criterion="loo_nlpd", sigma_f="refit", group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0):
         """``optimize_ard`` for EVERY data set of a retrospective run at once: X [B, n, d], y [B, n] -> dict(x [F, d + 1], fun [F], nit [F],
@@ -1105,11 +1163,11 @@ class GPR:
         leave-one-out score (``loo_ard_batch`` with ``sigma_f``) -- with d + 1 hyper-parameters and few data the marginal likelihood overfits
         the relevance of features, and the predictive score is the honest objective; 'nlml' is ``optimize_batch(ard=True)``.  ``theta0`` is
         [F, d + 1], [d + 1], [F, 2] or [2] (the common log l is repeated for all d features); F = S B rows are S starts per data set, start
-        i on data set i % B, and all F results come back.  RBF / Matern, fp64.  The leave-block-out scores have no lockstep form:
-        ``optimize_ard(criterion='cv_*')`` minimises them one data set at a time."""
+        i on data set i % B, and all F results come back.  RBF / Matern, fp64.  The leave-block-out scores in lockstep:
+        ``optimize_cv_batch``."""
         from .optim import bfgs_lockstep
         if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS:
-            raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
+            raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse' (the leave-block-out scores 'cv_nlpd' / 'cv_sse': optimize_cv_batch)")
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
         if self.kernel == "netdiffusion" or self.dtype != "f64":
@@ -1118,6 +1176,16 @@ class GPR:
             return self.optimize_batch(X, y, theta0, group=group, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step, ard=True)
         X = L.f64(X, 3)
         B, d = X.shape[0], X.shape[2]
+        th0 = self._ard_starts(theta0, B, d)
+        self.upload_batch(X, y, None, group=group, concurrency=1)
+        return bfgs_lockstep(lambda t: self.loo_ard_batch(t, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol,
+                             ftol=ftol, max_step=max_step)
+
+    @staticmethod
+    def _ard_starts(theta0, B, d):
+        """theta0 [F, d + 1], [d + 1], [F, 2] or [2] -> the starts [F, d + 1] of a lockstep run over per-feature scales on B data sets: the
+        common log l repeated for every feature; F = S B rows are S starts per data set (start i on data set i % B), anything else is
+        broadcast to one start per data set."""
         p = d + 1
         th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
         if th0.ndim == 2 and th0.shape[1] == 2 and d != 1:      # (log l, log sn~): the common log l for every feature
@@ -1125,11 +1193,43 @@ class GPR:
         if th0.ndim != 2 or th0.shape[1] != p:
             raise ValueError("theta0 must hold d + 1 = %d entries per start, or 2 (log l is repeated for every feature)" % p)
         if th0.shape[0] != B and th0.shape[0] % B == 0:
-            th0 = np.array(th0)                                   # S starts per data set: start i uses data set i % B
+            return np.array(th0)                                  # S starts per data set: start i uses data set i % B
+        return np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, p))
+
+    def optimize_cv_batch(self, X, y, theta0, block, gap=0, criterion="cv_nlpd", sigma_f="refit", ard=True, group=8, maxiter=50, gtol=1e-5, ftol=1e-10,
+                          max_step=2.0):
+        """``optimize_ard(criterion='cv_*')`` for EVERY data set of a retrospective run at once: X [B, n, d], y [B, n] -> dict(x [F, d + 1],
+        fun [F], nit [F], converged [F], nfev = device calls), the lockstep BFGS of ``optimize_batch`` (``optim.bfgs_lockstep``) on the
+        leave-block-out score ``criterion`` ('cv_nlpd' | 'cv_sse') of ``cv(block, gap, sigma_f)`` -- the honest objective for ordered rows
+        such as consecutive years, where ``loo`` keeps a year's serially correlated neighbours in the training set and the marginal
+        likelihood overfits relevance at d + 1 hyper-parameters and a few dozen years.  Each round is ONE device call for all unfinished
+        starts (``cv_ard_batch``).  ``block`` has no default: it depends on the data's correlation length.
+        ``ard=True``: one length scale per feature and the noise; ``theta0`` is [F, d + 1], [d + 1], [F, 2] or [2] (the common log l is
+        repeated for all d features), as ``optimize_ard_batch`` takes it; F = S B rows are S starts per data set, start i on data set
+        i % B, and all F results come back.  ``ard=False``: one common length scale (``cv_objective_batch``), ``theta0`` [2] or [F, 2],
+        x [F, 2].  RBF / Matern, fp64; block + 2 gap <= 128 and every fold must leave a training row."""
+        from .optim import bfgs_lockstep
+        if criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse' (the leave-one-out scores and 'nlml': optimize_ard_batch)")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        X = L.f64(X, 3)
+        B, n, d = X.shape
+        block, gap = self._cv_args(block, gap, sigma_f, n=n)
+        if ard:
+            th0 = self._ard_starts(theta0, B, d)
         else:
-            th0 = np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, p))
+            th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
+            if th0.ndim != 2 or th0.shape[1] != 2:
+                raise ValueError("theta0 must hold 2 entries per start (log l, log sn~) with ard=False")
+            th0 = np.array(th0) if th0.shape[0] != B and th0.shape[0] % B == 0 else np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, 2))
         self.upload_batch(X, y, None, group=group, concurrency=1)
-        return bfgs_lockstep(lambda t: self.loo_ard_batch(t, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol,
+        if ard:
+            return bfgs_lockstep(lambda t: self.cv_ard_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter,
+                                 gtol=gtol, ftol=ftol, max_step=max_step)
+        return bfgs_lockstep(lambda t: self.cv_objective_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, group=group), th0, maxiter=maxiter, gtol=gtol,
                              ftol=ftol, max_step=max_step)
 
     def _loo_objective_batch(self, theta, criterion, sigma_f, group):
@@ -1165,11 +1265,11 @@ class GPR:
         ``ard=True`` (RBF / Matern, ``criterion='nlml'``): one length scale per feature, the same lockstep BFGS on ``nlml_ard_batch`` (d + 1
         parameters per start).  ``theta0`` is [F, d + 1], [d + 1], [F, 2] or [2]; with two entries the common log l is repeated for all d
         features.  Returns x [F, d + 1].  The leave-one-out scores over per-feature scales in lockstep: ``optimize_ard_batch``; the
-        leave-block-out scores have no lockstep form, ``optimize_ard`` minimises them one data set at a time."""
+        leave-block-out scores: ``optimize_cv_batch``."""
         from .optim import bfgs_lockstep, newton_lockstep
         if ard and criterion != "nlml":
             raise ValueError("optimize_batch(ard=True): criterion must be 'nlml' (optimize_ard_batch minimises the leave-one-out scores over per-feature "
-                             "scales in lockstep; optimize_ard the leave-one-out and leave-block-out scores, one data set at a time)")
+                             "scales in lockstep, optimize_cv_batch the leave-block-out scores; optimize_ard either, one data set at a time)")
         if ard and self.kernel == "netdiffusion":
             raise ValueError("optimize_batch(ard=True): per-feature length scales cover the RBF / Matern kernels")
         if criterion != "nlml" and criterion not in L.LOO_CRITERIA:
