@@ -57,6 +57,30 @@ int sigp_debug_run_strip(sigp_handle* h, int dtype, void* M, int64_t ld, const v
 int sigp_debug_run_link(sigp_handle* h, int dtype, void* M, int64_t ld, int c, const void* Linv, void* scratch, int rows_ride, int members, int64_t sM, int64_t sL,
                         int64_t sS, int64_t m_elems, int64_t linv_elems, int64_t scratch_elems);
 /* (the diagonal block: sigp_debug_time_diag with reps = 1, skip = 0 returns L and Linv of one block) */
+
+/*
+ * Run-and-return entries of the quadratic solve kernels (tests/test_hip_solve_kernels.py), same convention: host operands in, ONE launch with
+ * the grid rule the engine uses, every buffer back whole; SIGP_BAD_ARG, nothing launched, for a descriptor that would read or write outside
+ * the buffer sizes given in elements, for a row or member stride that is not a multiple of 16 bytes, and for a K (rowdot) or a column count
+ * (coldot) that is not a multiple of the 16-byte vector width (2 doubles / 4 floats): the kernels load whole vectors.
+ *
+ * rowdot_kernel:  Zout[r][j] (-)= sum_k (Zin + Zadd)[r][k] Mx[j ld + k],  j < nrows, r < nrhs (1 .. 4);  kmode 0: k in [0, K), 1: [0, j],
+ * 2: [j, K) (nrows <= K for 1 and 2);  sub = 1 subtracts from the prior content;  Zadd may be NULL (same shape as Zin; one member only: the
+ * kernel has no member stride for it);  pm_pw > 0: Zout is panel-major [panel][4][pm_pw], entry of row g = j_off + j of right-hand side r at
+ * ((g / pm_pw) 4 + r) pm_pw + g % pm_pw, otherwise row-major with ldzout;  `members` lockstep members sM / sZi / sZo elements apart.
+ */
+int sigp_debug_run_rowdot(sigp_handle* h, int dtype, const void* Mx, int64_t ld, int nrows, int K, int kmode, const void* Zin, int64_t ldzin, void* Zout, int64_t ldzout,
+                          int nrhs, int sub, const void* Zadd, int pm_pw, int j_off, int members, int64_t sM, int64_t sZi, int64_t sZo, int64_t m_elems,
+                          int64_t zin_elems, int64_t zout_elems);
+/* coldot_kernel:  Zout[r][j] -= sum_{k < K} Zin[r][k] Mx[k ld + j],  j < ncols, r < nrhs (1 .. 4) */
+int sigp_debug_run_coldot(sigp_handle* h, int dtype, const void* Mx, int64_t ld, int ncols, int K, const void* Zin, int64_t ldzin, void* Zout, int64_t ldzout, int nrhs,
+                          int64_t m_elems, int64_t zin_elems, int64_t zout_elems);
+/* The fp32 engine's block solves on the factor and inverse blocks the last single fp32 fit left on the handle.  rhs [nrhs][n] doubles (rounded to
+ * fp32, pad rows zeroed, as a refinement step hands its residuals over) is replaced by  which = 0: L~^-1 rhs (f32_block_forward),
+ * 1: L~^-T rhs (f32_block_backward),  2: L~^-T L~^-1 rhs (both). */
+int sigp_debug_f32_solve(sigp_handle* h, int which, double* rhs, int64_t n, int nrhs);
+/* which = 0: fU, the row-major inverse-transposes of the factor's 2048-column diagonal blocks;  1: fV, their transposes.  out [n_pad][n_pad] floats. */
+int sigp_debug_f32_get_inverse(sigp_handle* h, int which, float* out);
 #ifdef __cplusplus
 }
 #endif

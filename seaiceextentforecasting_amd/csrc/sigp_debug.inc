@@ -458,3 +458,136 @@ int sigp_debug_run_link(sigp_handle* h, int dtype, void* M, int64_t ld, int c, c
   if (dtype != SIGP_F64) return SIGP_BAD_ARG;
   return debug_run_link_t<double>(h, M, ld, c, Linv, scratch, rows_ride, members, sM, sL, sS, m_elems, linv_elems, scratch_elems);
 }
+
+// ---- run-and-return entries of the quadratic solve kernels (tests/test_hip_solve_kernels.py) ------------------------------------------------
+// rowdot_kernel / coldot_kernel: ONE launch with the grid rule the engine uses (one wave per matrix row, four per workgroup; one workgroup per
+// 16 vectors of columns) on the caller's operands, every buffer back whole.  The kernels load whole 16-byte vectors of Mx and of the
+// right-hand sides, so K (rowdot) and the column count (coldot) must be multiples of the vector width, like every row and member stride.
+}  // extern "C" (templates need C++ linkage)
+
+template <typename Real>
+static int debug_run_rowdot_t(sigp_handle* h, const void* Mx, long ld, int nrows, int K, int kmode, const void* Zin, long ldzin, void* Zout, long ldzout, int nrhs,
+                              int sub, const void* Zadd, int pm_pw, int j_off, int members, long sM, long sZi, long sZo, long m_elems, long zin_elems,
+                              long zout_elems) {
+  constexpr int NE = Num<Real>::NE;
+  constexpr long LIM = 1L << 20;
+  if (!h || !Mx || !Zin || !Zout) return SIGP_BAD_ARG;
+  if (nrows < 1 || nrows > LIM || K < 1 || K > LIM || K % NE) return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: K = %d is not a positive multiple of the vector width %d", K, NE);
+  if (kmode < 0 || kmode > 2 || nrhs < 1 || nrhs > TS_RHS || (sub != 0 && sub != 1) || members < 1 || members > 64)
+    return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: kmode / nrhs / sub / members");
+  if (kmode != 0 && nrows > K) return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: a triangular k range needs nrows <= K");
+  if (ld < K || ldzin < K || ld > LIM || ldzin > LIM || sM < 0 || sZi < 0 || sZo < 0 || std::max({sM, sZi, sZo}) > (1L << 40) || m_elems < 1 || zin_elems < 1 || zout_elems < 1)
+    return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: strides");
+  if (ld % NE || ldzin % NE || sM % NE || sZi % NE || sZo % NE) return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: a row or member stride is not a multiple of 16 bytes");
+  if (pm_pw < 0 || pm_pw > LIM || pm_pw % NE || j_off < 0 || j_off > LIM || (pm_pw == 0 && (j_off != 0 || ldzout < nrows || ldzout > LIM || ldzout % NE)))
+    return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: output layout");
+  if (Zadd && members > 1) return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: Zadd has no member stride (the kernel reads ONE Zadd for every member)");
+  const long g_hi = (long)j_off + nrows - 1;
+  const long out_hi = pm_pw > 0 ? ((g_hi / pm_pw) * TS_RHS + nrhs - 1) * pm_pw + g_hi % pm_pw : (long)(nrhs - 1) * ldzout + nrows - 1;
+  if ((members - 1) * sM + (long)(nrows - 1) * ld + K - 1 >= m_elems || (members - 1) * sZi + (long)(nrhs - 1) * ldzin + K - 1 >= zin_elems ||
+      (members - 1) * sZo + out_hi >= zout_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: the descriptor reaches outside the operand buffers");
+  if (members > 1 && sZo <= out_hi) return fail(h, SIGP_BAD_ARG, "debug_run_rowdot: members would write the same entries");
+  HIPCHK(h, hipSetDevice(h->device));
+  DebugDeviceBuf dM, dI, dA, dO;
+  HIPCHK(h, hipMalloc(&dM.p, (size_t)m_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dM.p, Mx, (size_t)m_elems * sizeof(Real), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dI.p, (size_t)zin_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dI.p, Zin, (size_t)zin_elems * sizeof(Real), hipMemcpyHostToDevice));
+  if (Zadd) {
+    HIPCHK(h, hipMalloc(&dA.p, (size_t)zin_elems * sizeof(Real)));
+    HIPCHK(h, hipMemcpy(dA.p, Zadd, (size_t)zin_elems * sizeof(Real), hipMemcpyHostToDevice));
+  }
+  HIPCHK(h, hipMalloc(&dO.p, (size_t)zout_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dO.p, Zout, (size_t)zout_elems * sizeof(Real), hipMemcpyHostToDevice));
+  hipStream_t st = h->slots[0].s_upd;
+  hipLaunchKernelGGL(rowdot_kernel<Real>, dim3((unsigned)((nrows + 3) / 4), (unsigned)members), dim3(256), 0, st, (const Real*)dM.p, ld, nrows, K, kmode, (const Real*)dI.p,
+                     ldzin, (Real*)dO.p, ldzout, nrhs, sub, (const Real*)dA.p, pm_pw, j_off, sM, sZi, sZo);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(Zout, dO.p, (size_t)zout_elems * sizeof(Real), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+template <typename Real>
+static int debug_run_coldot_t(sigp_handle* h, const void* Mx, long ld, int ncols, int K, const void* Zin, long ldzin, void* Zout, long ldzout, int nrhs, long m_elems,
+                              long zin_elems, long zout_elems) {
+  constexpr int NE = Num<Real>::NE, CW = 16 * NE;
+  constexpr long LIM = 1L << 20;
+  if (!h || !Mx || !Zin || !Zout) return SIGP_BAD_ARG;
+  if (ncols < 1 || ncols > LIM || ncols % NE) return fail(h, SIGP_BAD_ARG, "debug_run_coldot: the column count %d is not a positive multiple of the vector width %d", ncols, NE);
+  if (K < 1 || K > LIM || nrhs < 1 || nrhs > TS_RHS) return fail(h, SIGP_BAD_ARG, "debug_run_coldot: K / nrhs");
+  if (ld < ncols || ldzin < K || ldzout < ncols || ld > LIM || ldzin > LIM || ldzout > LIM || m_elems < 1 || zin_elems < 1 || zout_elems < 1)
+    return fail(h, SIGP_BAD_ARG, "debug_run_coldot: strides");
+  if (ld % NE || ldzin % NE || ldzout % NE) return fail(h, SIGP_BAD_ARG, "debug_run_coldot: a row stride is not a multiple of 16 bytes");
+  if ((long)(K - 1) * ld + ncols - 1 >= m_elems || (long)(nrhs - 1) * ldzin + K - 1 >= zin_elems || (long)(nrhs - 1) * ldzout + ncols - 1 >= zout_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_coldot: the descriptor reaches outside the operand buffers");
+  HIPCHK(h, hipSetDevice(h->device));
+  DebugDeviceBuf dM, dI, dO;
+  HIPCHK(h, hipMalloc(&dM.p, (size_t)m_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dM.p, Mx, (size_t)m_elems * sizeof(Real), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dI.p, (size_t)zin_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dI.p, Zin, (size_t)zin_elems * sizeof(Real), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dO.p, (size_t)zout_elems * sizeof(Real)));
+  HIPCHK(h, hipMemcpy(dO.p, Zout, (size_t)zout_elems * sizeof(Real), hipMemcpyHostToDevice));
+  hipStream_t st = h->slots[0].s_upd;
+  hipLaunchKernelGGL(coldot_kernel<Real>, dim3((unsigned)((ncols + CW - 1) / CW)), dim3(256), 0, st, (const Real*)dM.p, ld, ncols, K, (const Real*)dI.p, ldzin, (Real*)dO.p,
+                     ldzout, nrhs);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(Zout, dO.p, (size_t)zout_elems * sizeof(Real), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+extern "C" {
+
+int sigp_debug_run_rowdot(sigp_handle* h, int dtype, const void* Mx, int64_t ld, int nrows, int K, int kmode, const void* Zin, int64_t ldzin, void* Zout, int64_t ldzout,
+                          int nrhs, int sub, const void* Zadd, int pm_pw, int j_off, int members, int64_t sM, int64_t sZi, int64_t sZo, int64_t m_elems,
+                          int64_t zin_elems, int64_t zout_elems) {
+  if (dtype == SIGP_F32)
+    return debug_run_rowdot_t<float>(h, Mx, ld, nrows, K, kmode, Zin, ldzin, Zout, ldzout, nrhs, sub, Zadd, pm_pw, j_off, members, sM, sZi, sZo, m_elems, zin_elems, zout_elems);
+  if (dtype != SIGP_F64) return SIGP_BAD_ARG;
+  return debug_run_rowdot_t<double>(h, Mx, ld, nrows, K, kmode, Zin, ldzin, Zout, ldzout, nrhs, sub, Zadd, pm_pw, j_off, members, sM, sZi, sZo, m_elems, zin_elems, zout_elems);
+}
+
+int sigp_debug_run_coldot(sigp_handle* h, int dtype, const void* Mx, int64_t ld, int ncols, int K, const void* Zin, int64_t ldzin, void* Zout, int64_t ldzout, int nrhs,
+                          int64_t m_elems, int64_t zin_elems, int64_t zout_elems) {
+  if (dtype == SIGP_F32) return debug_run_coldot_t<float>(h, Mx, ld, ncols, K, Zin, ldzin, Zout, ldzout, nrhs, m_elems, zin_elems, zout_elems);
+  if (dtype != SIGP_F64) return SIGP_BAD_ARG;
+  return debug_run_coldot_t<double>(h, Mx, ld, ncols, K, Zin, ldzin, Zout, ldzout, nrhs, m_elems, zin_elems, zout_elems);
+}
+
+// The fp32 engine's block solves on the factor and the inverse blocks the last fp32 fit left on the handle: rhs [nrhs][n] (doubles; rounded to
+// fp32 and the pad rows zeroed by convert_rows_kernel, as a refinement step hands its residuals over) is replaced by
+// which = 0: L~^-1 rhs (f32_block_forward), 1: L~^-T rhs (f32_block_backward), 2: L~^-T L~^-1 rhs (both, as a refinement step runs them).
+int sigp_debug_f32_solve(sigp_handle* h, int which, double* rhs, int64_t n, int nrhs) {
+  if (!h || !rhs || which < 0 || which > 2 || nrhs < 1 || nrhs > TS_RHS) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F32 || !h->fitted || n != h->n || !h->fU || h->cap_f_npad < h->n_pad) return fail(h, SIGP_BAD_ARG, "debug_f32_solve: the handle holds no fp32 fit of order %ld", (long)n);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->slots[0].s_upd;
+  const long n_pad = h->n_pad, ld = n_pad, tot = (long)nrhs * n_pad;
+  int rc;
+  HIPCHK(h, hipMemcpy2DAsync(h->rq, (size_t)ld * sizeof(double), rhs, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
+  float* in = which == 1 ? h->fXw : h->fZ;
+  hipLaunchKernelGGL((convert_rows_kernel<double, float>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const double*)h->rq, ld, in, ld, nrhs, (int)n_pad, (int)n);
+  HIPCHK(h, hipGetLastError());
+  if (which != 1 && (rc = f32_block_forward(h, st, n_pad, nrhs, h->fZ, h->fXw))) return rc;
+  if (which != 0 && (rc = f32_block_backward(h, st, n_pad, nrhs, h->fXw, h->fZ))) return rc;
+  const float* res = which == 0 ? h->fXw : h->fZ;
+  hipLaunchKernelGGL((convert_rows_kernel<float, double>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, res, ld, h->rq, ld, nrhs, (int)n_pad, (int)n);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpy2DAsync(rhs, (size_t)n * sizeof(double), h->rq, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nrhs, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  return SIGP_OK;
+}
+
+// the inverse blocks of the last fp32 fit: which = 0 fU (row-major upper triangular inverse-transposes of the 2048-column diagonal blocks),
+// 1 fV (their transposes); out [n_pad][n_pad] floats (n_pad = 128 sigp_num_blocks)
+int sigp_debug_f32_get_inverse(sigp_handle* h, int which, float* out) {
+  if (!h || !out || which < 0 || which > 1) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F32 || !h->fitted || !h->fU || h->cap_f_npad < h->n_pad) return fail(h, SIGP_BAD_ARG, "debug_f32_get_inverse: the handle holds no fp32 fit");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->slots[0].s_upd));
+  HIPCHK(h, hipMemcpy(out, which == 0 ? h->fU : h->fV, (size_t)h->n_pad * h->n_pad * sizeof(float), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
