@@ -87,7 +87,25 @@ int sigp_kernel_build_from_sigma(sigp_handle* h, const double* Sigma, int64_t ld
  * and alpha~, sigma_f, nlML, the predictions, loo / cv and the gradients lose the same factor against an fp64 LAPACK fit of the same matrix.
  * A smooth kernel on ordered, densely sampled inputs (RBF / Matern, long length scale) puts cond(K11) within a factor 3 of cond(K~) ~ n / sn~
  * (the three rows above: sn~ = 1e-4, 1e-8, 1e-11 at l = 3 on 257 .. 640 sorted points of [0, 10]).  A matrix of the same cond(K~) whose
- * diagonal blocks are benign is not affected. */
+ * diagonal blocks are benign is not affected.
+ *
+ * Option "accurate_solve" = 1 (sigp_set_option; off by default, fp64 engine, single-GPU fits and lockstep groups) puts ONE residual-correction step
+ * behind every such product with an inverted 128 x 128 diagonal block:  X1 = A W^T, R = A - X1 L^T, X = X1 + R W^T  (W the stored inverse, L the
+ * diagonal block itself, of which only the lower triangle is read), all three products in one launch per block column with A, X1 and R held on
+ * chip (csrc/refined_solve.hpp).  Covered: the column solves of the factorisation -- the ride-along rows with them, so z = L~^-1 y and
+ * v = L~^-1 k* --, the forward block solves of sigp_predict / sigp_predict_cov and the backward block solves of sigp_get_alpha.  With it, on the
+ * same matrices (measured, tests/test_hip_accurate_solve.py, docs/EXPERIMENTS.md "Accurate solves"):
+ *     cond(K11) ~ 1e6, 1e10, 1e13 (sn~ = 1e-4, 1e-8, 1e-11)      rho <= 1.3 times LAPACK's; every matrix factors (sn~ = 1e-13 included)
+ *     alpha~, sigma_f, nlML, predictions (ride-along and general)    within 5.1 times LAPACK's error against a long-double fit
+ *     loo, cv, the exact MLII gradient                               within 5.3 times LAPACK's (their U = L~^-T and fold solves stay explicit inverses,
+ *                                                                    by nature; they start from an accurate factor)
+ * What the option overrides while it is on: "panel_mode" (every panel as panel_mode 0: a strip solve is a product with the inverse of a panel's
+ * whole top triangle) and bit 2 of "panel_chain" (no fused link: its column solve is a plain product); the other bits of panel_chain, "schedule"
+ * and "outer_blocks" keep their meaning, and the first two their "same bits" guarantee.  With the option at 0 the library issues exactly the
+ * launches it issues without this paragraph.  Cost: the column solves triple their flops (they are about 384 / n of a fit's) and single fits lose
+ * the fused link; measured in docs/EXPERIMENTS.md.  Out of scope: the fp32 engine (sigp_set_option answers SIGP_BAD_ARG on an fp32 handle; it
+ * refines against K~ itself), sharded fits (sigp_dist_fit with the option set: SIGP_BAD_ARG), sigp_small_*, and U = L~^-T by recursive doubling
+ * with the fold solves of sigp_cv (see above). */
 int sigp_potrf(sigp_handle* h, int64_t* info);
 
 /* K7,K8,K12: A~ = K~^-1 y, sigma_f = y^T A~/n (north/June1st.py:266-268), nlML (north/June1st.py:246).
@@ -567,6 +585,9 @@ int sigp_synchronize(sigp_handle* h);
  *   lookahead [1]         factor the next panel on the panel stream while the trailing update runs
  *   schedule [0]          0 right-looking outer panels, 1 left-looking (same factor bit for bit)
  *   panel_mode [2]        rows below a panel's top block: 0 recursion, 1 strip solve, 2 strips when strips x members >= strip_min [512]
+ *   accurate_solve [0]    1: one residual-correction step behind every product with an inverted diagonal block in the factorisation's column solves
+ *                         and in the block solves of sigp_predict / sigp_predict_cov / sigp_get_alpha (see sigp_potrf: LAPACK-grade accuracy on
+ *                         ill-conditioned diagonal blocks; overrides panel_mode and bit 2 of panel_chain while on; 0 / 1, fp64 handles only)
  *   diag_tiles [1]        symmetric trailing updates: a diagonal 128 x 128 tile loads, multiplies and stores only the 36 of its 64 16 x 16 pairs on or below
  *                         the diagonal (nothing reads the rest; same lower halves bit for bit; 0 = whole tiles, for A/B timing)
  *   ride_tiles [1]        trailing updates: while at most 16 rows of the ride-along block are in use (y and up to 15 test points), its tiles stage and

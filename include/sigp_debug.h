@@ -56,6 +56,13 @@ int sigp_debug_run_strip(sigp_handle* h, int dtype, void* M, int64_t ld, const v
  * below it are solved in place.  M and scratch come back whole. */
 int sigp_debug_run_link(sigp_handle* h, int dtype, void* M, int64_t ld, int c, const void* Linv, void* scratch, int rows_ride, int members, int64_t sM, int64_t sL,
                         int64_t sS, int64_t m_elems, int64_t linv_elems, int64_t scratch_elems);
+/* refined_solve_kernel (option accurate_solve; fp64 only): A [rows][lda >= 128] per member is replaced, in ONE launch through launch_refined_solve, by
+ * X = A W^T + (A - (A W^T) L^T) W^T (trans = 0: X L^T = A) or X = A W + (A - (A W) L) W (trans = 1: X L = A); W [128][ldw] the inverse block, L [128][ldl]
+ * the diagonal block, of which only the lower triangle is read; members sA / sW / sL elements apart (sW, sL may be 0: one block for all).  Any
+ * rows >= 1.  SIGP_BAD_ARG, nothing launched: a descriptor that leaves the buffers, a stride that is not a multiple of 16 bytes, members that
+ * share rows.  A comes back whole. */
+int sigp_debug_run_refined_solve(sigp_handle* h, int trans, void* A, int64_t lda, int rows, const void* W, int64_t ldw, const void* L, int64_t ldl, int members,
+                                 int64_t sA, int64_t sW, int64_t sL, int64_t a_elems, int64_t w_elems, int64_t l_elems);
 /* (the diagonal block: sigp_debug_time_diag with reps = 1, skip = 0 returns L and Linv of one block) */
 
 /*

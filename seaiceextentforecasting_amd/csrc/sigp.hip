@@ -23,6 +23,7 @@
 #include "kernels_misc.hpp"
 #include "potrf_diag.hpp"
 #include "chain_link.hpp"
+#include "refined_solve.hpp"
 #include "smallgp.hpp"
 #include "syrk128.hpp"
 #include "predcov.hpp"
@@ -226,6 +227,8 @@ struct sigp_handle {
   int opt_strip_min = 512;
   int opt_diag_tiles = 1;    // symmetric trailing updates: a diagonal tile multiplies the 36 of 64 16 x 16 pairs on or below its diagonal (0 = the whole tile; same lower halves)
   int opt_ride_tiles = 1;    // trailing updates: tiles of the ride-along block row multiply its first 16 rows only when no more are in use (y + <= 15 test points)
+  int opt_accurate = 0;      // accurate_solve: every product with an inverted diagonal block in the factorisation's column solves and in the block solves of
+                             // predict / predict_cov / get_alpha takes one residual-correction step (refined_solve.hpp); panels then run unfused and unstripped
   int opt_strip_tri = 1;     // strip solves skip the zero tile-slices of the inverse diagonal blocks (0 = multiply the whole 128 x 128 block: same bits, 9 % more MFMAs)
   int opt_update_dbg = 0;    // debug library: ablation bits OR-ed into the trailing updates' dbg word (8 no C load, 16 no C store: timing only, results garbage)
   int opt_c_dma = 0;         // trailing update: bring the C tile in by LDS-DMA instead of 64 accumulator-layout loads per lane (A/B switch)
@@ -676,7 +679,13 @@ static int solve_rows_forward_t(sigp_handle* h, hipStream_t st, const Real* Mat,
     g.A = Z + (long)kb * NB; g.lda = ld; g.B = dinvp + (long)kb * NB * NB; g.ldb = NB; g.C = Z + (long)kb * NB; g.ldc = ld;
     g.K = NB; g.r0 = 0; g.r1 = RIDE / 32; g.c0 = 0; g.c1 = 1; g.lower = 0;
     g.batch = nchunks; g.sA = g.sC = (long)RIDE * ld; g.sB = 0;
-    int rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, st, g);
+    int rc;
+    if constexpr (std::is_same<Real, double>::value) {
+      if (h->opt_accurate) {
+        RefinedArgs a{Z + (long)kb * NB, ld, (long)RIDE * ld, dinvp + (long)kb * NB * NB, (long)NB, 0L, Mat + (long)kb * NB * (ld + 1), ld, 0L, RIDE};
+        rc = launch_refined_solve<false>(h, st, a, nchunks);
+      } else rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, st, g);
+    } else rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, st, g);
     if (rc) return rc;
     if (kb + 1 < T) {
       GemmArgsT<Real> u{};
@@ -701,7 +710,13 @@ static int solve_rows_backward_t(sigp_handle* h, hipStream_t st, const Real* Mat
     GemmArgsT<Real> g{};
     g.A = Z + (long)kb * NB; g.lda = ld; g.B = dinvp + (long)kb * NB * NB; g.ldb = NB; g.C = Z + (long)kb * NB; g.ldc = ld;
     g.K = NB; g.r0 = 0; g.r1 = RIDE / 32; g.c0 = 0; g.c1 = 1; g.lower = 0;
-    int rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, true>(h, st, g);
+    int rc;
+    if constexpr (std::is_same<Real, double>::value) {
+      if (h->opt_accurate) {
+        RefinedArgs a{Z + (long)kb * NB, ld, 0L, dinvp + (long)kb * NB * NB, (long)NB, 0L, Mat + (long)kb * NB * (ld + 1), ld, 0L, RIDE};
+        rc = launch_refined_solve<true>(h, st, a, 1);
+      } else rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, true>(h, st, g);
+    } else rc = launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, true>(h, st, g);
     if (rc) return rc;
     if (kb > 0) {
       GemmArgsT<Real> u{};
@@ -884,6 +899,11 @@ int sigp_set_option(sigp_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "loo_grad_tri")) { h->opt_loo_grad_tri = value != 0; return SIGP_OK; }
   if (!strcmp(name, "diag_tiles")) { h->opt_diag_tiles = value != 0; return SIGP_OK; }
   if (!strcmp(name, "ride_tiles")) { h->opt_ride_tiles = value != 0; return SIGP_OK; }
+  if (!strcmp(name, "accurate_solve")) {
+    if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "accurate_solve: the fp64 engine's option (the fp32 engine refines against K~ itself)");
+    if (value != 0 && value != 1) return fail(h, SIGP_BAD_ARG, "accurate_solve: 0 or 1 required (got %lld)", (long long)value);
+    h->opt_accurate = (int)value; return SIGP_OK;
+  }
   if (!strcmp(name, "strip_tri")) { h->opt_strip_tri = value != 0; return SIGP_OK; }
   if (!strcmp(name, "strip_min")) { if (value < 1) return SIGP_BAD_ARG; h->opt_strip_min = (int)value; return SIGP_OK; }
   if (!strcmp(name, "schedule")) { if (value < 0 || value > 1) return SIGP_BAD_ARG; h->opt_schedule = (int)value; return SIGP_OK; }

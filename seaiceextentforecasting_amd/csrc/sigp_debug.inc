@@ -459,6 +459,37 @@ int sigp_debug_run_link(sigp_handle* h, int dtype, void* M, int64_t ld, int c, c
   return debug_run_link_t<double>(h, M, ld, c, Linv, scratch, rows_ride, members, sM, sL, sS, m_elems, linv_elems, scratch_elems);
 }
 
+int sigp_debug_run_refined_solve(sigp_handle* h, int trans, void* A, int64_t lda, int rows, const void* W, int64_t ldw, const void* L, int64_t ldl, int members,
+                                 int64_t sA, int64_t sW, int64_t sL, int64_t a_elems, int64_t w_elems, int64_t l_elems) {
+  constexpr long LIM = 1L << 20;
+  if (!h || !A || !W || !L) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "debug_run_refined_solve: fp64 only");
+  if ((trans != 0 && trans != 1) || rows < 1 || rows > LIM || members < 1 || members > 64) return fail(h, SIGP_BAD_ARG, "debug_run_refined_solve: trans / rows / members");
+  if (lda < NB || ldw < NB || ldl < NB || lda > LIM || ldw > LIM || ldl > LIM || sA < 0 || sW < 0 || sL < 0 || std::max({sA, sW, sL}) > (1L << 40) || a_elems < 1 ||
+      w_elems < 1 || l_elems < 1)
+    return fail(h, SIGP_BAD_ARG, "debug_run_refined_solve: strides");
+  if (lda % 2 || ldw % 2 || ldl % 2 || sA % 2 || sW % 2 || sL % 2) return fail(h, SIGP_BAD_ARG, "debug_run_refined_solve: a row or member stride is not a multiple of 16 bytes");
+  const long a_hi = (long)(rows - 1) * lda + NB - 1;
+  if ((members - 1) * sA + a_hi >= a_elems || (members - 1) * sW + (long)(NB - 1) * ldw + NB - 1 >= w_elems || (members - 1) * sL + (long)(NB - 1) * ldl + NB - 1 >= l_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_refined_solve: the descriptor reaches outside the operand buffers");
+  if (members > 1 && sA <= a_hi) return fail(h, SIGP_BAD_ARG, "debug_run_refined_solve: members would write the same entries");
+  HIPCHK(h, hipSetDevice(h->device));
+  DebugDeviceBuf dA, dW, dL;
+  HIPCHK(h, hipMalloc(&dA.p, (size_t)a_elems * sizeof(double)));
+  HIPCHK(h, hipMemcpy(dA.p, A, (size_t)a_elems * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dW.p, (size_t)w_elems * sizeof(double)));
+  HIPCHK(h, hipMemcpy(dW.p, W, (size_t)w_elems * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dL.p, (size_t)l_elems * sizeof(double)));
+  HIPCHK(h, hipMemcpy(dL.p, L, (size_t)l_elems * sizeof(double), hipMemcpyHostToDevice));
+  hipStream_t st = h->slots[0].s_upd;
+  const RefinedArgs a{(double*)dA.p, lda, sA, (const double*)dW.p, ldw, sW, (const double*)dL.p, ldl, sL, rows};
+  const int rc = trans ? launch_refined_solve<true>(h, st, a, members) : launch_refined_solve<false>(h, st, a, members);
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(A, dA.p, (size_t)a_elems * sizeof(double), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
 // ---- run-and-return entries of the quadratic solve kernels (tests/test_hip_solve_kernels.py) ------------------------------------------------
 // rowdot_kernel / coldot_kernel: ONE launch with the grid rule the engine uses (one wave per matrix row, four per workgroup; one workgroup per
 // 16 vectors of columns) on the caller's operands, every buffer back whole.  The kernels load whole 16-byte vectors of Mx and of the

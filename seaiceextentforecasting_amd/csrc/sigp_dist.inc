@@ -83,6 +83,7 @@ int sigp_dist_fit(sigp_handle* h, int kernel_id, double ell, double sn_tilde, co
                   double* out, double* mean, double* var) {
   if (!h || h->n == 0 || !out) return fail(h, SIGP_BAD_ARG, "dist_fit: call set_train first");
   if (h->ard_on) return fail(h, SIGP_BAD_ARG, "dist_fit: per-feature length scales are set (single-GPU fits only)");
+  if (h->opt_accurate) return fail(h, SIGP_BAD_ARG, "dist_fit: option accurate_solve is set (single-GPU fp64 fits only)");
   if (W < 1 || W > 64) return fail(h, SIGP_BAD_ARG, "dist_fit: panel width must be 1..64 blocks");
   if (!(sn_tilde >= 0)) return fail(h, SIGP_BAD_ARG, "sn_tilde >= 0 required");
   if (h->m > 0 && (!mean || !var)) return fail(h, SIGP_BAD_ARG, "dist_fit: mean / var buffers required for the ride-along test points");

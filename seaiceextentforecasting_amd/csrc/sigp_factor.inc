@@ -74,10 +74,30 @@ int launch_column_solve(sigp_handle* h, hipStream_t st, GemmArgsT<Real> g, long 
   g.r1 = (int)rows * 4;                // few rows: 32-row tiles for parallelism
   return launch_gemm_cfg<Real, 32, 128, 1, 4, GEMM_SET, false>(h, st, g);
 }
+// ---- primitive 2, refined (option accurate_solve, fp64): X = A inv(L)^T (TRANS: A inv(L)) with ONE residual-correction step against the
+// diagonal block L itself, in place, one launch (refined_solve.hpp).  The launcher of every refined solve of the library: the
+// factorisation's columns, the block solves of sigp_predict / sigp_predict_cov / sigp_get_alpha, and the debug library's run-and-return entry.
+template <bool TRANS>
+int launch_refined_solve(sigp_handle* h, hipStream_t st, const RefinedArgs& a, int nb) {
+  if (a.rows <= 0 || nb <= 0) return SIGP_OK;
+  static AttrOnce r_attr;
+  ProfScope ps(h, st, SIGP_KC_TRSM, nb * 3.0 * 2.0 * a.rows * NB * NB, nb * (2.0 * a.rows * NB + 2.0 * NB * NB) * 8);
+  HIPCHK(h, r_attr.set(h->device, (const void*)refined_solve_kernel<TRANS>, refined_lds_bytes()));
+  hipLaunchKernelGGL(refined_solve_kernel<TRANS>, dim3((unsigned)((a.rows + RS_TM - 1) / RS_TM), (unsigned)nb), dim3(256), refined_lds_bytes(), st, a);
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
 // rows_below 128-row blocks under the diagonal block of column c (the ride block is one of them when the rows reach it):
 // L[c+1.., c] = A[c+1.., c] inv(L_cc)^T
 template <typename Real>
 int solve_column(sigp_handle* h, const FactorView<Real>& v, hipStream_t st, int c, int rows_below) {
+  if constexpr (std::is_same<Real, double>::value) {
+    if (h->opt_accurate) {             // option accurate_solve: the product and one residual correction against L_cc, one launch
+      if (rows_below <= 0) return SIGP_OK;
+      RefinedArgs a{v.at(c + 1, c), v.ld, v.matStride, v.dinv_at(c), (long)NB, v.dinvStride, v.at(c, c), v.ld, v.matStride, rows_below * NB};
+      return launch_refined_solve<false>(h, st, a, v.nb);
+    }
+  }
   GemmArgsT<Real> g{};
   g.A = v.at(c + 1, c); g.lda = v.ld; g.sA = v.matStride;
   g.B = v.dinv_at(c); g.ldb = NB; g.sB = v.dinvStride;
@@ -152,7 +172,8 @@ int chain_panel(sigp_handle* h, const FactorView<Real>& v, hipStream_t sp, int J
     const int rows_below = rlim - (c + 1);
     const bool last = i + 1 >= Wp;
     // (the link's ride solves any number of rows, 16 per workgroup; beyond link_rows 128-row blocks x members the stand-alone LDS-DMA solve is the better kernel)
-    const bool fused = !last && (h->opt_panel_chain & 4) != 0 && rows_below >= 1 && (long)rows_below * nb < h->opt_link_rows;
+    // (option accurate_solve: no fused link -- its column solve is a plain product with the inverse block)
+    const bool fused = !last && !h->opt_accurate && (h->opt_panel_chain & 4) != 0 && rows_below >= 1 && (long)rows_below * nb < h->opt_link_rows;
     if (!fused) {
       if ((rc = solve_column(h, v, sp, c, rows_below))) return rc;
       if (on_col && (rc = (*on_col)(c))) return rc;
@@ -249,7 +270,8 @@ struct PotrfRun {
   // is not strip-solved); panel_strips = the Mt products + strip kernel for the rows below the top block (no-op otherwise)
   bool use_strips(int J0, int Wp) const {
     const int below = R - (J0 + Wp);             // row blocks under the panel's top block (the ride block is one of them)
-    return std::is_same<Real, double>::value && Wp > 1 && Wp <= MT_W && below > 0 &&
+    // (option accurate_solve: no strip solves -- a strip is a product with the inverse of the panel's whole top triangle)
+    return std::is_same<Real, double>::value && !h->opt_accurate && Wp > 1 && Wp <= MT_W && below > 0 &&
            (h->opt_panel_mode == 1 || (h->opt_panel_mode == 2 && (long)below * v.nb >= h->opt_strip_min));
   }
   int panel_top(int J0, int Wp) const {

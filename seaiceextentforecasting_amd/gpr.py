@@ -30,7 +30,7 @@ class LinAlgError(np.linalg.LinAlgError):
 
 class GPR:
     def __init__(self, kernel="netdiffusion", dtype="f64", device=0, outer_blocks=None, lookahead=None, schedule=None,
-                 panel_mode=None, expm="pade"):
+                 panel_mode=None, expm="pade", accurate=None):
         if kernel not in L.KERNEL_IDS:
             raise ValueError("kernel must be one of %s" % sorted(L.KERNEL_IDS))
         if dtype not in ("f64", "f32"):
@@ -64,6 +64,8 @@ class GPR:
             self.set_option("schedule", {"right": 0, "left": 1}[schedule])
         if panel_mode is not None:    # "recursive" | "strips" | "auto": how the rows below a panel's top block are solved
             self.set_option("panel_mode", {"recursive": 0, "strips": 1, "auto": 2}[panel_mode])
+        if accurate is not None:      # True: one residual-correction step behind every product with an inverted diagonal block (option accurate_solve)
+            self.set_option("accurate_solve", int(bool(accurate)))
 
     # ---- plumbing ------------------------------------------------------------------------------
     def _check(self, rc, what):
