@@ -41,7 +41,7 @@ enum { SIGP_MAT_K = 0, SIGP_MAT_L = 1 };
  * gemm_mfma_kernel<64,64> (updates with few tiles), syrk128_kernel (inner + trailing updates), epilogue_kernel */
 enum { SIGP_KC_KBUILD = 0, SIGP_KC_DIAG = 1, SIGP_KC_TRSM = 2, SIGP_KC_UPDATE_SMALL = 3,
        SIGP_KC_SYRK128 = 4, SIGP_KC_EPILOGUE = 5, SIGP_KC_SMALL = 6 /* smallgp_kernel */,
-       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard; sigp_loo's two + U U^T, the n^2 passes, the product P diag(gamma) P and the tile pass of sigp_loo_grad_ard; sigp_cv's entries + per pass the fold adjoints and their assembly, then U U^T, the n^2 passes, the banded product P B, the product (P B) P and the tile pass of sigp_cv_grad_ard */, SIGP_KC_COUNT = 8 };
+       SIGP_KC_MLII = 7 /* triangular inversion + U U^T of sigp_nlml_grad; triangular inversion + row pass of sigp_loo; triangular inversion + the fold steps of sigp_cv; + U U^T, the triangular product and the n^2 passes of sigp_loo_grad; triangular inversion + U U^T + the tile pass of sigp_nlml_grad_ard; sigp_loo's two + U U^T, the n^2 passes, the product P diag(gamma) P and the tile pass of sigp_loo_grad_ard; sigp_cv's entries + per pass the fold adjoints and their assembly, then U U^T, the n^2 passes, the banded product P B, the product (P B) P and the tile pass of sigp_cv_grad_ard; the scan and the row pass of sigp_hindcast; + the adjoint's n^2 passes, triangular inversion, W = U C, the product U W^T and the tile pass of sigp_hindcast_grad_ard */, SIGP_KC_COUNT = 8 };
 
 #define SIGP_MAX_RIDE 127 /* test points that can ride along one factorisation */
 
@@ -500,6 +500,59 @@ int sigp_cv_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t
 int sigp_cv_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
                            int64_t block, int64_t gap, int sigma_mode, int criterion, double* mean, double* var, int64_t nstride, double* score,
                            double* grad, int64_t ldgrad);
+
+/* Expanding-window (rolling-origin) hindcast validation: the score the reference's retrospective loop reports -- train on the years before
+ * t, forecast year t, for every t (September1st_retro.py:176-248) -- with the hyper-parameters (and, for the reference kernel, M and the
+ * feature columns) held, from ONE fit.  Rows are in time order, 0-based.  Row t is scored when s = t - lead + 1 >= min_train; its training
+ * set is rows [0, s): lead = 1 is one step ahead, and lead - 1 rows between the training set and the target are withheld.  The Cholesky
+ * factor of the first s rows is the leading block of L~ and the first s entries of z = L~^-1 y are that prefix's solved vector, so
+ *     y_t - mean_t = sum_{j=s..t} L~_tj z_j,    var_t = sigma_t sum_{j=s..t} L~_tj^2    (with the noise, like fvar),
+ *     sigma_t = (sum_{j<s} z_j^2) / s  (SIGP_LOO_REFIT: sigma_f profiled on the training rows alone, what a fit on rows [0, s) returns)
+ *            or q / n                  (SIGP_LOO_FIXED: the full fit's sigma_f, its own bits),
+ *     score[0] = sum_t log(2 pi var_t)/2 + (y_t - mean_t)^2 / (2 var_t),   score[1] = sum_t (y_t - mean_t)^2   over the scored rows,
+ * added in a fixed order (no atomics: the same bits on every run).  Rows that are not scored get NaN in mean / var.  No L~^-T is formed:
+ * one scan of z^2 and one pass over n segments of at most lead entries.
+ * sigp_hindcast: after sigp_fit / sigp_fit_predict, any kernel; mean [n], var [n], score [2].  The factor, z and q are only read:
+ * sigp_predict / sigp_get_alpha / sigp_loo / sigp_cv afterwards return the bits they returned before.  SIGP_BAD_ARG: an fp32 handle, a
+ * sharded fit, not fitted, lead < 1, lead > SIGP_HINDCAST_MAX_LEAD, min_train < 1, no scored row (min_train + lead - 1 > n - 1), a bad
+ * sigma_mode.  Device work is accounted under SIGP_KC_MLII (the scan and the row pass: one entry each).
+ * Out of scope: gradients for lockstep groups, gradients in sigp_small_*, the reference kernel's gradient, the fp32 engine, sharded fits. */
+enum { SIGP_HINDCAST_MAX_LEAD = 128, SIGP_HINDCAST_SMALL_MAX_LEAD = 32 };
+int sigp_hindcast(sigp_handle* h, int64_t lead, int64_t min_train, int sigma_mode, double* mean, double* var, double* score);
+/* ... for lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2; the retro loop's refits per grid point,
+ * September1st_retro.py:176-248, for many grid points at once): arguments and errors as sigp_loo_batch, and sigp_hindcast's checks on
+ * lead, min_train and sigma_mode.  A non-SPD member gets +inf scores and NaN rows; its group mates keep their bits.  The handle is left
+ * unfitted, as after the other batch entries. */
+int sigp_hindcast_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* ell, const double* sn_tilde, int64_t lead,
+                        int64_t min_train, int sigma_mode, double* mean, double* var, int64_t nstride, double* score);
+/* One more flavour of the one-workgroup kernel (sigp_small_upload / sigp_small_run: the reference's own kernel at the reference's own size,
+ * one workgroup per fit): the retro loop's rolling-origin refits (September1st_retro.py:176-248) for every queued (data set, l, sn~) in the
+ * same single launch as the fits.  Arguments, outputs and conventions as sigp_small_run_loo: out6 [nprob][6] = sigma_f, nlML, info, sigma_n,
+ * hindcast nlpd, hindcast sse; hc_mean / hc_var [nprob][nstride >= the largest n] (NaN where a row is not scored and beyond a set's n).
+ * L~ and z are read where the factorisation left them in LDS; no inverse is formed.  A non-SPD K~ gives +inf in both scores.
+ * SIGP_BAD_ARG: what sigp_small_run_loo refuses, lead < 1, lead > SIGP_HINDCAST_SMALL_MAX_LEAD, min_train < 1, a bad sigma_mode, and a named
+ * data set without a scored row (min_train + lead - 1 > n - 1).  The other four instantiations of the kernel keep their instructions. */
+int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead,
+                            int64_t min_train, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* hc_mean,
+                            double* hc_var, int64_t nstride);
+/* The hindcast scores AND the exact derivatives of one of them with respect to theta = (log l_1 .. log l_d, log sn~) (RBF / Matern-5/2,
+ * fp64), so that the length scales can be chosen by the score the retro loop reports (September1st_retro.py:176-248) instead of a grid.
+ * theta, ntheta = d + 1, criterion (SIGP_LOO_NLPD / SIGP_LOO_SSE) and mean / var [n] (both or neither) as sigp_loo_grad_ard.  Sets the
+ * scales, fits with ell = 1 through sigp_fit_predict's own launches and runs sigp_hindcast's launches: score [2] and mean / var carry the
+ * bits sigp_hindcast returns on that fit.  grad = NULL: scores only, no L~^-T and no cubic work.
+ * The gradient is one symmetric adjoint G = d score / d K~, the reverse-mode derivative of the Cholesky factorisation: with
+ * kappa_t = 1/(2 var_t) - r_t^2/(2 var_t^2), rho_t = r_t/var_t (nlpd) or kappa_t = 0, rho_t = 2 r_t (sse), r_t = y_t - mean_t,
+ *     B_tj = rho_t z_j + 2 kappa_t sigma_t L~_tj  (s_t <= j <= t),   zbar_j = sum_{t: s_t <= j <= t} rho_t L~_tj + 2 z_j sum_{t: s_t > j} kappa_t w_t / s_t
+ *     (FIXED: 2 z_j (sum_t kappa_t w_t) / n),   A = L~^T B - zbar z^T on its lower triangle,   C_ij = C_ji = A_ij / 2 (i >= j),   G = U C U^T, U = L~^-T,
+ *     grad[k] = sum_ij G_ij h_ij (u_ik - u_jk)^2 (h as in sigp_nlml_grad_ard),   grad[d] = sn~ tr G.
+ * Cost on top of the values: U = L~^-T (n^3/3) and G = U W^T on the lower 128-tiles (n^3/3) are the cubic steps -- 2 n^3 / 3 against the
+ * 5 n^3 / 3 of sigp_loo_grad_ard; W = U C needs no cubic product (the banded part of C is a banded product of 2 n^2 lead flops, its
+ * rank-one part two fixed-order scans along each row of U); then sigp_loo_grad_ard's tile pass with G as its matrix, all d components at
+ * once.  Memory: sigp_loo_grad's single-fit buffers and the centred features.  SIGP_KC_MLII, one entry per step.
+ * SIGP_BAD_ARG: as sigp_loo_grad_ard, and sigp_hindcast's checks.  SIGP_NOT_SPD (K~ not SPD or exp(theta) overflowed): score and grad
+ * +inf, mean / var NaN.  Afterwards the handle is fitted at exp(theta) with the scales set, as after sigp_loo_grad_ard. */
+int sigp_hindcast_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int64_t lead, int64_t min_train, int sigma_mode,
+                           int criterion, double* mean, double* var, double* score, double* grad);
 
 /* One large fit sharded over the GPUs of a node (BASELINE configs[3] fp64, configs[4] fp32 + fp64 refinement): 1-D block-cyclic
  * ownership of outer panels (W column blocks of 128; panel q belongs to rank q % nranks), OWNER-ONLY storage -- a rank allocates,

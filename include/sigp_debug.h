@@ -88,6 +88,11 @@ int sigp_debug_run_coldot(sigp_handle* h, int dtype, const void* Mx, int64_t ld,
 int sigp_debug_f32_solve(sigp_handle* h, int which, double* rhs, int64_t n, int nrhs);
 /* which = 0: fU, the row-major inverse-transposes of the factor's 2048-column diagonal blocks;  1: fV, their transposes.  out [n_pad][n_pad] floats. */
 int sigp_debug_f32_get_inverse(sigp_handle* h, int which, float* out);
+/* The adjoint G = d score / d K~ of a hindcast score (include/sigp.h: sigp_hindcast_grad_ard) on the single fp64 fit the handle holds, by
+ * sigp_hindcast_grad_ard's own launches up to its ARD pass: the lower 128-tiles into out [n][ldo] as the product wrote them (the
+ * diagonal tiles whole: their two halves agree to rounding, not bit for bit), zeros in the tiles above.  criterion SIGP_LOO_NLPD /
+ * SIGP_LOO_SSE; lead, min_train, sigma_mode as sigp_hindcast. */
+int sigp_debug_run_hindcast_adjoint(sigp_handle* h, int64_t lead, int64_t min_train, int sigma_mode, int criterion, double* out, int64_t ldo);
 #ifdef __cplusplus
 }
 #endif

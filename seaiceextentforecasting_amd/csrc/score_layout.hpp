@@ -14,6 +14,8 @@
 //   gV                  LooGradVecs          sigp_loo_grad(_batch)
 //                       LooArdVecs           sigp_loo_grad_ard, sigp_cv_grad_ard
 //                       LooArdGroupVecs      sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch: G LooArdVecs at an even member stride
+//                       HindcastVecs         sigp_hindcast, sigp_hindcast_batch (G of them, size() apart)
+//                       HindcastArdVecs      sigp_hindcast_grad_ard: HindcastVecs, then LooArdVecs
 //   cvPart cvBlk cvVec  CvWork               cv_launch
 //   cvAdj               CvAdjStore           sigp_cv_grad_ard; it fills the CvAdjoint that cv_launch and the kernels take
 //                       CvAdjGroupStore      sigp_cv_grad_ard_batch: the same pieces for the nb members of a lockstep group
@@ -132,6 +134,29 @@ struct LooArdGroupVecs {
   __host__ __device__ static long size(long G, long n_pad) { return G * (4 * n_pad + 2); }
   __host__ __device__ long mstride() const { return 4 * n_pad + 2; }
   __host__ __device__ LooArdVecs member(long b) const { return LooArdVecs{base + b * mstride(), n_pad}; }
+};
+
+// Per-member vector workspace of the hindcast entries (hindcast.hpp): cum (prefix sums of z^2), then -- the gradient alone -- r, w, rho,
+// ks (= kappa sigma), suf, zbar [n_pad each].  Read one double at a time.
+struct HindcastVecs {
+  double* base; long n_pad;
+  __host__ __device__ static long size(long n_pad) { return 7 * n_pad; }
+  __host__ __device__ double* cum() const { return base; }
+  __host__ __device__ double* r() const { return base + n_pad; }
+  __host__ __device__ double* w() const { return base + 2 * n_pad; }
+  __host__ __device__ double* rho() const { return base + 3 * n_pad; }
+  __host__ __device__ double* ks() const { return base + 4 * n_pad; }
+  __host__ __device__ double* suf() const { return base + 5 * n_pad; }
+  __host__ __device__ double* zbar() const { return base + 6 * n_pad; }
+};
+
+// sigp_hindcast_grad_ard: HindcastVecs of the one member, then the LooArdVecs the ARD pass takes (a, v and eps are zero here: the adjoint is
+// the matrix G alone).  7 n_pad is even, so the LooArdVecs' 16-byte reads stay aligned.
+struct HindcastArdVecs {
+  double* base; long n_pad;
+  __host__ __device__ static long size(long n_pad) { return HindcastVecs::size(n_pad) + LooArdVecs::size(n_pad); }
+  __host__ __device__ HindcastVecs hc() const { return HindcastVecs{base, n_pad}; }
+  __host__ __device__ LooArdVecs ard() const { return LooArdVecs{base + HindcastVecs::size(n_pad), n_pad}; }
 };
 
 // ---- cvPart, cvBlk, cvVec ----------------------------------------------------------------------------------------------------------------------

@@ -32,6 +32,7 @@
 #include "ardgrad.hpp"
 #include "looard.hpp"
 #include "cvard.hpp"
+#include "hindcast.hpp"
 #include "score_layout.hpp"
 
 using namespace sigp;
@@ -792,7 +793,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 600; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch
+int sigp_version(void) { return 610; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -1817,6 +1818,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_looardbatch.inc"   // sigp_loo_grad_ard_batch: ... for lockstep groups on the resident batch data
 #include "sigp_cvard.inc"     // sigp_cv_grad_ard: exact per-feature gradients of the leave-block-out scores
 #include "sigp_cvardbatch.inc"    // sigp_cv_grad_ard_batch: ... for lockstep groups; the driver it shares with sigp_loo_grad_ard_batch
+#include "sigp_hindcast.inc"   // sigp_hindcast, sigp_hindcast_batch, sigp_hindcast_grad_ard: expanding-window hindcast validation and its exact ARD gradient
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"

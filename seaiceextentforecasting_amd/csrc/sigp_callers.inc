@@ -59,11 +59,14 @@ int sigp_small_set_dweights(sigp_handle* h, const double* dlam_pool, int64_t cou
 
 static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out,
                           double* mean, double* var, int64_t mstride, bool grad, int loo_mode = -1, double* loo_mean = nullptr,
-                          double* loo_var = nullptr, int64_t nstride = 0, int64_t cv_block = 0, int64_t cv_gap = 0) {
+                          double* loo_var = nullptr, int64_t nstride = 0, int64_t cv_block = 0, int64_t cv_gap = 0, int64_t hc_lead = 0,
+                          int64_t hc_min_train = 0) {
   if (!h || h->sm_sets.empty()) return fail(h, SIGP_BAD_ARG, "small_run: call sigp_small_upload first");
+  const bool hc = hc_lead != 0;                        // hindcast validation: rows and scores travel like the leave-one-out ones
   const bool cv = cv_block != 0 || cv_gap != 0;       // leave-block-out: rows and scores travel like the leave-one-out ones
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
   const bool loo = loo_mode >= 0;
+  if (hc && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: hc_mean / hc_var [nprob][nstride >= %d] required", h->sm_nmax);
   if (loo && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_%s: %s_mean / %s_var [nprob][nstride >= %d] required", cv ? "cv" : "loo", cv ? "cv" : "loo", cv ? "cv" : "loo", h->sm_nmax);
   constexpr long SM_LDS_MAX = 160 * 1024 - 64;
   if (cv && h->sm_lds + SM_CV_EXTRA_BYTES > SM_LDS_MAX) return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes", h->sm_nmax, h->sm_mmax, SM_CV_EXTRA_BYTES);
@@ -74,7 +77,10 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   for (int64_t i = 0; i < nprob; ++i) {
     if (set_index[i] < 0 || set_index[i] >= (int64_t)h->sm_sets.size()) return fail(h, SIGP_BAD_ARG, "small_run: fit %ld names data set %ld of %zu", (long)i, (long)set_index[i], h->sm_sets.size());
     if (!(sn_tilde[i] >= 0) || !std::isfinite(ell[i])) return fail(h, SIGP_BAD_ARG, "small_run: finite ell and sn_tilde >= 0 required");
-    if (loo && h->sm_sets[(size_t)set_index[i]].n < 2) return fail(h, SIGP_BAD_ARG, "small_run_%s: fit %ld names a data set of one point; cross-validation needs n >= 2", cv ? "cv" : "loo", (long)i);
+    if (hc && hc_min_train + hc_lead - 1 > h->sm_sets[(size_t)set_index[i]].n - 1)
+      return fail(h, SIGP_BAD_ARG, "small_run_hindcast: fit %ld names a data set without a scored row (min_train + lead - 1 = %lld > n - 1 = %d)", (long)i,
+                  (long long)(hc_min_train + hc_lead - 1), h->sm_sets[(size_t)set_index[i]].n - 1);
+    if (loo && !hc && h->sm_sets[(size_t)set_index[i]].n < 2) return fail(h, SIGP_BAD_ARG, "small_run_%s: fit %ld names a data set of one point; cross-validation needs n >= 2", cv ? "cv" : "loo", (long)i);
     if (cv && !cv_checked[(size_t)set_index[i]]) {
       if (const char* why = cv_check_folds(h->sm_sets[(size_t)set_index[i]].n, cv_block, cv_gap, SIGP_CV_SMALL_MAX_WINDOW))
         return fail(h, SIGP_BAD_ARG, "small_run_cv: fit %ld: %s (block = %lld, gap = %lld, n = %d, SIGP_CV_SMALL_MAX_WINDOW = %d)", (long)i, why, (long long)cv_block, (long long)cv_gap,
@@ -107,7 +113,10 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   double* d_var = d_mean + nprob * ms;
   double* d_lmean = d_var + nprob * ms;        // [nprob][ns] each; NaN beyond a set's n (the memset above)
   double* d_lvar = d_lmean + nprob * ns;
-  if (cv) {
+  if (hc) {
+    static AttrOnce attr256h;
+    HIPCHK(h, attr256h.set(h->device, (const void*)smallgp_kernel<256, false, false, false, true>, 160 * 1024 - 64));
+  } else if (cv) {
     static AttrOnce attr256c;
     HIPCHK(h, attr256c.set(h->device, (const void*)smallgp_kernel<256, false, false, true>, 160 * 1024 - 64));
   } else if (loo) {
@@ -120,14 +129,18 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
       const SmallSet& s = h->sm_sets[(size_t)pb.set];
       fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n * (1 + s.m);
       if (grad) fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.N;      // X = L~^-1, X A, A^T a~
-      if (loo) fl += (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n;                                 // X = L~^-1, its column norms and X^T z
+      if (hc) fl += 4.0 * s.n * hc_lead + 2.0 * s.n * s.n;                                         // the row segments and the prefix sums of z^2
+      else if (loo) fl += (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n;                            // X = L~^-1, its column norms and X^T z
       if (cv) fl += (double)s.n * s.n * (cv_block + 2.0 * cv_gap);                                  // the folds' P_SS from X's columns
     }
     ProfScope ps(h, st, SIGP_KC_SMALL, fl, 0.0);
     // orders up to 64 (the reference's n <= 45): one wavefront per fit; larger: four
     // measured on the reference-size grid (48 000 fits, n = 6 .. 45): four wavefronts per fit 1.02 ms, one wavefront per fit 1.71 ms
     const double* d_dlam = h->sm_has_dlam ? h->sm_dlam : nullptr;
-    if (cv)
+    if (hc)
+      hipLaunchKernelGGL((smallgp_kernel<256, false, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A,
+                         h->sm_y, h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)hc_lead, (int)hc_min_train);
+    else if (cv)
       hipLaunchKernelGGL((smallgp_kernel<256, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)(h->sm_lds + SM_CV_EXTRA_BYTES), st, h->sm_sets_dev, h->sm_probs,
                          h->sm_A, h->sm_y, h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)cv_block, (int)cv_gap);
     else if (loo)
@@ -285,3 +298,13 @@ int sigp_detrend(sigp_handle* h, const double* data, int64_t P, int64_t T, int64
   return SIGP_OK;
 }
 
+
+// sigp_small_run with the expanding-window hindcast validation of every fit in the same single launch (smallgp_kernel<256, false, false, false, true>:
+// L~ and z are read where the factorisation left them in LDS; no inverse is formed)
+int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead, int64_t min_train,
+                            int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* hc_mean, double* hc_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (lead < 1 || lead > SIGP_HINDCAST_SMALL_MAX_LEAD) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: 1 <= lead <= %d required (got %lld)", (int)SIGP_HINDCAST_SMALL_MAX_LEAD, (long long)lead);
+  if (min_train < 1) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: min_train >= 1 required (got %lld)", (long long)min_train);
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, hc_mean, hc_var, nstride, 0, 0, lead, min_train);
+}

@@ -622,3 +622,30 @@ int sigp_debug_f32_get_inverse(sigp_handle* h, int which, float* out) {
   HIPCHK(h, hipMemcpy(out, which == 0 ? h->fU : h->fV, (size_t)h->n_pad * h->n_pad * sizeof(float), hipMemcpyDeviceToHost));
   return SIGP_OK;
 }
+
+// G = d score / d K~ of a hindcast score on the single fp64 fit (hindcast.hpp; sigp_hindcast_grad_ard's launches up to the ARD pass): its lower
+// 128-tiles into out [n][ldo] as the product wrote them -- the diagonal tiles whole, both halves -- and zeros in the tiles above.
+int sigp_debug_run_hindcast_adjoint(sigp_handle* h, int64_t lead, int64_t min_train, int sigma_mode, int criterion, double* out, int64_t ldo) {
+  if (!h || !out || ldo < h->n) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F64 || !h->fitted) return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_adjoint: the handle holds no fp64 fit");
+  if (criterion != SIGP_LOO_NLPD && criterion != SIGP_LOO_SSE) return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_adjoint: bad criterion");
+  int rc;
+  if ((rc = hindcast_check(h, "debug_run_hindcast_adjoint", h->n, lead, min_train, sigma_mode, SIGP_HINDCAST_MAX_LEAD))) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  Slot& s = h->slots[0];
+  hipStream_t st = s.s_upd;
+  const long n = h->n, n_pad = h->n_pad;
+  if ((rc = ensure(h, &h->gV, &h->cap_gV, HindcastArdVecs::size(n_pad)))) return rc;
+  if ((rc = scores_ensure(h, 1, n_pad, ScoreParts::size(1, n_pad)))) return rc;
+  if ((rc = scores_grad_ensure(h, 1, n_pad, 0))) return rc;
+  const ScoreParts sp{h->gPart, 1, n_pad};
+  const HindcastVecs hv{h->gV, n_pad};
+  if ((rc = scores_stage_q(h, st, sp))) return rc;
+  if ((rc = hindcast_launch(h, st, 1, n, n_pad, s.mat, 0, h->y, 0, nullptr, sp.q(), 0, lead, min_train, sigma_mode, sp, hv, 0, 1))) return rc;
+  if ((rc = hindcast_adjoint(h, st, lead, min_train, sigma_mode, criterion, sp.q(), hv))) return rc;
+  HIPCHK(h, hipMemcpy2DAsync(out, (size_t)ldo * sizeof(double), h->gD, (size_t)n_pad * sizeof(double), (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, st));
+  if ((rc = sync_slot(h, s))) return rc;
+  for (long i = 0; i < n; ++i)
+    for (long j = (i / NB + 1) * NB; j < n; ++j) out[i * ldo + j] = 0.0;
+  return SIGP_OK;
+}

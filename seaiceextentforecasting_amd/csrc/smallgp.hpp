@@ -89,7 +89,12 @@ __device__ inline double smallgp_allsum(double v, double* sh) {
 // behind the plain layout:  P_SS(i, j) = sum_{k >= max} X(k, r0 + i) X(k, r0 + j),  P_SS = M M^T column by column,  W = M^-1 (one thread per
 // column),  t = W a~_S,  r = W^T t,  h_i = sum_k W(k, i)^2;  mean = y - r,  var = s h with s = (zz - t.t) / (n - w) (loo_fixed = 0) or sigma_f;
 // outputs as LOO's, written for the scored rows of each fold.  A failed pivot of a P_SS: +inf in both scores and NaN rows.
-template <int NT, bool GRAD = false, bool LOO = false, bool CV = false>
+// HC = true (OW = 6; never together with GRAD, LOO or CV): expanding-window hindcast validation (hindcast.hpp) from L~ and z as they lie in LDS
+// after the factorisation -- no inverse is formed.  cv_block carries `lead`, cv_gap `min_train`:  row t is scored when s = t - lead + 1 >=
+// min_train;  r_t = sum_{j=s..t} L~(t,j) z_j,  w_t = sum_{j=s..t} L~(t,j)^2,  mean_t = y_t - r_t,  var_t = sigma_t w_t with sigma_t =
+// (sum_{j<s} z_j^2) / s (loo_fixed = 0: sigma_f profiled on the training rows alone) or sigma_f (loo_fixed = 1); one thread per row, every
+// sum in ascending j.  Outputs as LOO's; rows that are not scored get NaN.  A non-SPD K~ gives +inf in both scores.
+template <int NT, bool GRAD = false, bool LOO = false, bool CV = false, bool HC = false>
 __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict__ sets, const SmallProb* __restrict__ probs,
                                                       const double* __restrict__ Apool, const double* __restrict__ ypool,
                                                       const double* __restrict__ lampool, int ch, double* __restrict__ out,
@@ -97,8 +102,9 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
                                                       const double* __restrict__ dlampool, double* __restrict__ loo_mean = nullptr,
                                                       double* __restrict__ loo_var = nullptr, int nstride = 0, int loo_fixed = 0, int cv_block = 0,
                                                       int cv_gap = 0) {
-  static_assert(!(GRAD && LOO) && !(CV && (GRAD || LOO)), "one launch forms the MLII gradients, the leave-one-out or the leave-block-out predictions");
-  constexpr int OW = GRAD ? 8 : (LOO || CV) ? 6 : 4;
+  static_assert(!(GRAD && LOO) && !(CV && (GRAD || LOO)) && !(HC && (GRAD || LOO || CV)),
+                "one launch forms the MLII gradients, the leave-one-out, the leave-block-out or the hindcast predictions");
+  constexpr int OW = GRAD ? 8 : (LOO || CV || HC) ? 6 : 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const SmallProb pb = probs[blockIdx.x];
   const SmallSet st = sets[pb.set];
@@ -198,7 +204,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     } else {
       o[0] = inf; o[1] = inf; o[2] = (double)info; o[3] = inf;
       if (GRAD) { o[4] = inf; o[5] = inf; o[6] = inf; o[7] = inf; }     // north/June1st.py:254-256
-      if (LOO || CV) { o[4] = inf; o[5] = inf; }
+      if (LOO || CV || HC) { o[4] = inf; o[5] = inf; }
     }
   }
   for (int j = 0; j < m; ++j) {
@@ -213,6 +219,36 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     }
   }
 
+  if constexpr (HC) {
+    if (info != 0) return;           // uniform
+    const int lead = cv_block, min_train = cv_gap;
+    double tn = 0.0, ts = 0.0;
+    for (int t = tid; t < n; t += NT) {
+      const int s = t - lead + 1;
+      double mu = qnan, v = qnan;
+      if (s >= min_train) {
+        const double* row = Kp + t * ldk;
+        double r = 0.0, w = 0.0;
+        for (int j = s; j <= t; ++j) { r = fma(row[j], z[j], r); w = fma(row[j], row[j], w); }
+        double sig = sf;
+        if (!loo_fixed) {
+          double c = 0.0;
+          for (int j = 0; j < s; ++j) c = fma(z[j], z[j], c);
+          sig = c / (double)s;
+        }
+        v = sig * w;
+        mu = ypool[st.y_off + t] - r;
+        tn += 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
+        ts = fma(r, r, ts);
+      }
+      loo_mean[(long)blockIdx.x * nstride + t] = mu;
+      loo_var[(long)blockIdx.x * nstride + t] = v;
+    }
+    const double nlpd = smallgp_allsum<NT>(tn, red);
+    const double sse = smallgp_allsum<NT>(ts, red);
+    if (tid == 0) { out[(long)blockIdx.x * OW + 4] = nlpd; out[(long)blockIdx.x * OW + 5] = sse; }
+    return;
+  }
   if constexpr (GRAD || LOO || CV) {
     if (info != 0) return;           // uniform
     double* at = red + 16;           // [n] a~ = L~^-T z

@@ -364,6 +364,88 @@ class GPR:
             nlpd, sse = r["nlpd"], r["sse"]
         return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
 
+    # ---- expanding-window hindcast validation ----------------------------------------------------
+    def _hindcast_args(self, lead, min_train, sigma_f, n=None, d=None):
+        """the checks ``hindcast`` and its relatives share; ``min_train=None`` means max(2, d + 1).  Returns (lead, min_train)."""
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        lead = int(lead)
+        if lead < 1 or lead > L.HINDCAST_MAX_LEAD:
+            raise ValueError("hindcast: 1 <= lead <= %d required" % L.HINDCAST_MAX_LEAD)
+        if min_train is None:
+            min_train = 2 if d is None else max(2, d + 1)
+        min_train = int(min_train)
+        if min_train < 1:
+            raise ValueError("hindcast: min_train >= 1 required")
+        if n is not None and min_train + lead - 1 > n - 1:
+            raise ValueError("hindcast: no row is scored (min_train + lead - 1 = %d > n - 1 = %d)" % (min_train + lead - 1, n - 1))
+        return lead, min_train
+
+    def hindcast(self, lead=1, min_train=None, sigma_f="refit"):
+        """Expanding-window (rolling-origin) hindcast validation of the current fit with (l, sn~) (and, for the reference kernel, M and the
+        feature columns) held: what the retrospective loop reports -- ``fit`` on rows [0, s) followed by ``predict`` of row t = s + lead - 1,
+        for every t with s >= ``min_train`` -- read out of the factor already on the device (``sigp_hindcast``: the factor of a prefix is
+        the leading block of L~; one pass over n row segments, no inverse).  Rows are taken in time order; ``lead`` - 1 rows between the
+        training set and the target are withheld.  ``min_train=None`` means max(2, d + 1).
+
+        sigma_f='refit'  the signal variance is profiled on the training rows [0, s) alone: identical to real refits on the prefixes;
+        sigma_f='fixed'  the full fit's sigma_f is kept.  The means do not depend on the mode.
+
+        Returns dict(mean [n], var [n] (with the noise, like fvar; NaN where a row is not scored), nlpd, sse, mse, skill over the scored
+        rows, scored = slice(min_train + lead - 1, n)) with skill = 1 - sse / sum((y - mean(y))^2) over the scored rows.  The fit stays as
+        it is: ``predict`` / ``loo`` / ``cv`` afterwards work unchanged."""
+        if not self._fitted:
+            if sigma_f not in L.LOO_MODES:
+                raise ValueError("sigma_f must be 'refit' or 'fixed'")
+            raise RuntimeError("hindcast: call fit() first")
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n, self.d)
+        mean, var, score = np.zeros(self.n), np.zeros(self.n), np.zeros(2)
+        self._check(self._lib.sigp_hindcast(self._h, lead, min_train, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), L.ptr(score)), "hindcast")
+        return self._hindcast_result(mean, var, score, lead, min_train)
+
+    def _hindcast_result(self, mean, var, score, lead, min_train):
+        scored = slice(min_train + lead - 1, self.n)
+        ys = self._y[scored]
+        nlpd, sse = float(score[0]), float(score[1])
+        return dict(mean=mean, var=var, nlpd=nlpd, sse=sse, mse=sse / len(ys), skill=1.0 - sse / float(np.sum((ys - ys.mean()) ** 2)) if len(ys) > 1 else np.nan,
+                    scored=scored)
+
+    def hindcast_batch(self, ell, sn_tilde, lead=1, min_train=None, first=0, sigma_f="refit", group=8, predictions=True):
+        """``hindcast`` for many (data set, l, sn~) on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern), in lockstep
+        groups of ``group`` fits (``sigp_hindcast_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F]) and, with
+        ``predictions``, mean [F, n], var [F, n] (NaN where a row is not scored); a non-SPD member gets +inf / NaN.  ``min_train=None``
+        means max(2, d + 1) with d of the staged data sets, as in ``hindcast``."""
+        if self.kernel == "netdiffusion":
+            raise ValueError("hindcast_batch covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(hindcast=...)")
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, getattr(self, "_batch_n", None), getattr(self, "_batch_d", None))
+        ell, sn, F, n, score, mean, var = self._batch_score_args("hindcast_batch", ell, sn_tilde, group, predictions)
+        self._check(self._lib.sigp_hindcast_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), lead, min_train, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
+                                                  L.ptr(score)), "hindcast_batch")
+        return self._batch_score_result(score, mean, var)
+
+    def hindcast_grid(self, X, y, ells, sns, lead=1, min_train=None, sigma_f="refit", group=8, M=None):
+        """The hindcast scores on the (l, sn~) grid for one data set, shaped like ``loo_grid``: dict(nlpd, sse), each [len(ells), len(sns)],
+        +inf where K~ is not SPD.  Reference kernel (n <= 128, lead <= 32): one launch, one workgroup per grid point
+        (``SmallBatch.run(hindcast=...)``).  ``min_train=None`` means max(2, d + 1), as in ``hindcast``."""
+        ells = np.asarray(ells, dtype=np.float64).reshape(-1)
+        sns = np.asarray(sns, dtype=np.float64).reshape(-1)
+        E, S = np.meshgrid(ells, sns, indexing="ij")
+        Xa = np.asarray(X)
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, Xa.shape[0], Xa.shape[1])
+        if self.kernel == "netdiffusion":
+            from .smallbatch import SmallBatch
+            sb = SmallBatch(self)
+            ds = sb.add_dataset(X, y, None, M)
+            for e, s_ in zip(E.reshape(-1), S.reshape(-1)):
+                sb.add_fit(ds, e, s_, expm=self._expm)
+            r = sb.run(hindcast=dict(lead=lead, min_train=min_train, sigma_f=sigma_f))
+            nlpd, sse = r["hindcast_nlpd"], r["hindcast_sse"]
+        else:
+            self.upload_batch(L.f64(X, 2), y, None, group=group)
+            r = self.hindcast_batch(E.reshape(-1), S.reshape(-1), lead=lead, min_train=min_train, sigma_f=sigma_f, group=group, predictions=False)
+            nlpd, sse = r["nlpd"], r["sse"]
+        return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
+
     # ---- leave-block-out cross-validation --------------------------------------------------------
     @staticmethod
     def cv_folds(n, block, gap=0):
@@ -589,6 +671,38 @@ class GPR:
         del r["spd"]
         return r if predictions else (r["value"], r["grad"])
 
+    def hindcast_ard(self, theta, lead=1, min_train=None, criterion="hindcast_nlpd", sigma_f="refit", grad="exact", predictions=False):
+        """An expanding-window hindcast score with per-feature (ARD) length scales as an optimiser's objective: theta = (log l_1 .. log l_d,
+        log sn~) -> (value, grad [d + 1]) with value = the negative log predictive density (``criterion='hindcast_nlpd'``) or sum of
+        squared errors (``'hindcast_sse'``) of ``hindcast(lead, min_train, sigma_f)`` on the fit at exp(theta), and its exact gradient
+        (``sigp_hindcast_grad_ard``: the reverse-mode adjoint of the Cholesky factorisation and one pass for all d components);
+        ``grad=None``: value only (second entry None, no inverse and no cubic work).  A non-SPD K~ or an overflowing exp(theta) gives
+        ``(inf, [inf] * (d + 1))``.  ``predictions=True`` returns dict(value, grad, mean [n], var [n], nlpd, sse) instead: the bits
+        ``hindcast`` returns on that fit.  ``min_train=None`` means max(2, d + 1).  Afterwards the handle is fitted at exp(theta) with the
+        scales set, as after ``loo_ard``.  RBF / Matern, fp64."""
+        if criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse'")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        has = getattr(self, "_has_data", False)
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n if has else None, self.d if has else None)
+        cid = L.HINDCAST_CRITERION_IDS[criterion]
+        r = self._ard_call("hindcast_ard", theta, grad, cid, predictions, lambda th, mean, var, score, g: self._lib.sigp_hindcast_grad_ard(
+            self._h, self._kid, L.ptr(th), th.shape[0], lead, min_train, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
+        del r["spd"]
+        return r if predictions else (r["value"], r["grad"])
+
+    def hindcast_objective(self, theta, lead=1, min_train=None, criterion="hindcast_nlpd", sigma_f="refit"):
+        """A hindcast score as an optimiser's objective over ONE common length scale: theta = (log l, log sn~) -> (value, grad [2]).  It is
+        ``hindcast_ard`` at equal scales with d/dlog l = sum_k d/dlog l_k, as ``cv_objective``.  RBF / Matern, fp64."""
+        if self.kernel == "netdiffusion":
+            raise ValueError("hindcast_objective covers the RBF / Matern kernels (the reference kernel's hindcast scores have no gradient)")
+        theta = np.asarray(theta, dtype=np.float64).reshape(2)
+        d = getattr(self, "d", None) if getattr(self, "_has_data", False) else None
+        v, g = self.hindcast_ard(theta if d is None else np.concatenate([np.full(d, theta[0]), theta[1:]]), lead=lead, min_train=min_train, criterion=criterion,
+                                 sigma_f=sigma_f)
+        return v, np.array([np.sum(g[:-1]), g[-1]])
+
     def cv_objective(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit"):
         """A leave-block-out score as an optimiser's objective over ONE common length scale: theta = (log l, log sn~) -> (value, grad [2])
         with value = the ``criterion`` ('cv_nlpd' | 'cv_sse') of ``cv(block, gap, sigma_f)`` on the fit at exp(theta).  It is ``cv_ard`` at equal
@@ -601,9 +715,11 @@ class GPR:
         v, g = self.cv_ard(theta if d is None else np.concatenate([np.full(d, theta[0]), theta[1:]]), block, gap=gap, criterion=criterion, sigma_f=sigma_f)
         return v, np.array([np.sum(g[:-1]), g[-1]])
 
-    def optimize_ard(self, theta0, criterion="nlml", sigma_f="refit", method="L-BFGS-B", grad="exact", block=5, gap=0, **kw):
+    def optimize_ard(self, theta0, criterion="nlml", sigma_f="refit", method="L-BFGS-B", grad="exact", block=5, gap=0, lead=1, min_train=None, **kw):
         """Minimise ``criterion`` over one length scale per feature and the noise: 'nlml' (``nlml_ard``; what ``optimize(ard=True)`` does),
-        'loo_nlpd' or 'loo_sse' (``loo_ard`` with ``sigma_f``), 'cv_nlpd' or 'cv_sse' (``cv_ard`` with ``block``, ``gap`` and ``sigma_f``) -- with
+        'loo_nlpd' or 'loo_sse' (``loo_ard`` with ``sigma_f``), 'cv_nlpd' or 'cv_sse' (``cv_ard`` with ``block``, ``gap`` and ``sigma_f``),
+        'hindcast_nlpd' or 'hindcast_sse' (``hindcast_ard`` with ``lead``, ``min_train`` and ``sigma_f``: the score the retrospective loop
+        reports) -- with
         d + 1 hyper-parameters and few data the marginal likelihood overfits the relevance of features, and the predictive score is the honest
         objective; for ordered rows (consecutive years) the leave-block-out one, since ``loo`` keeps a row's correlated neighbours in the
         training set.  ``theta0`` = (log l_1 .. log l_d, log sn~), or (log l, log sn~)
@@ -611,12 +727,17 @@ class GPR:
         go to SciPy as they are.  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
         from scipy.optimize import minimize
 
-        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS and criterion not in L.CV_CRITERION_IDS:
-            raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd' or 'cv_sse'")
+        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS and criterion not in L.CV_CRITERION_IDS and criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd', 'cv_sse', 'hindcast_nlpd' or 'hindcast_sse'")
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
         if grad not in (None, "exact"):
             raise ValueError("optimize_ard takes grad='exact' or None")
+        if criterion in L.HINDCAST_CRITERION_IDS:
+            has = getattr(self, "_has_data", False)
+            lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n if has else None, self.d if has else None)
+            if self.kernel == "netdiffusion" or self.dtype != "f64":
+                raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
         if criterion in L.CV_CRITERION_IDS:
             block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
             if self.kernel == "netdiffusion" or self.dtype != "f64":
@@ -632,6 +753,8 @@ class GPR:
             objective = lambda th: self.nlml_ard(th, grad=grad)
         elif criterion in L.CV_CRITERION_IDS:
             objective = lambda th: self.cv_ard(th, block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad=grad)
+        elif criterion in L.HINDCAST_CRITERION_IDS:
+            objective = lambda th: self.hindcast_ard(th, lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f, grad=grad)
         else:
             objective = lambda th: self.loo_ard(th, criterion=criterion, sigma_f=sigma_f, grad=grad)
         if grad is None:
@@ -677,14 +800,15 @@ class GPR:
             return inf2
         return np.float64(r[key]), r[key + "_grad"]
 
-    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", ard=False, block=5, gap=0, **kw):
+    def optimize(self, theta0, method="L-BFGS-B", grad="exact", criterion="nlml", sigma_f="refit", ard=False, block=5, gap=0, lead=1, min_train=None, **kw):
         """The reference's commented-out optimiser call (north/June1st.py:259-262:
         ``minimize(MLII, x0=[log l0, log sn0], method='CG', jac=True)``) against the device engine.
         ``grad='exact'`` (default) feeds the true derivative of the profiled nlML; ``grad='ref'`` reproduces the
         reference's MLII contract verbatim (its "gradient" is not the derivative, so CG stalls as in SURVEY App. C-7).
         ``criterion='loo_nlpd'`` / ``'loo_sse'`` minimises that leave-one-out score instead (``loo_objective`` with ``sigma_f``; grad
         'exact' or None); ``criterion='cv_nlpd'`` / ``'cv_sse'`` the leave-block-out score of ``cv(block, gap, sigma_f)`` (``cv_objective``;
-        RBF / Matern).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``.
+        RBF / Matern); ``criterion='hindcast_nlpd'`` / ``'hindcast_sse'`` the expanding-window hindcast score of ``hindcast(lead, min_train,
+        sigma_f)`` (``hindcast_objective``; RBF / Matern).  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``.
         ``ard=True``: one length scale per feature, by ``nlml_ard``'s exact gradient -- ``theta0`` = (log l_1 .. log l_d, log sn~), or
         (log l, log sn~) with log l broadcast to every feature; ``criterion`` must be 'nlml' here (``optimize_ard`` takes the others); the relevance of feature k is read from
         ``result.x[k]`` (a large log l_k: the feature does not matter).  ``bounds`` and the other keywords go to SciPy as they are."""
@@ -692,7 +816,7 @@ class GPR:
 
         if ard:
             if criterion != "nlml":
-                raise ValueError("ard=True: criterion must be 'nlml' (optimize_ard minimises the leave-one-out scores over per-feature scales)")
+                raise ValueError("ard=True: criterion must be 'nlml' (optimize_ard minimises the leave-one-out, leave-block-out and hindcast scores -- loo_ard, cv_ard, hindcast_ard -- over per-feature scales)")
             if grad not in (None, "exact"):
                 raise ValueError("ard=True takes grad='exact' or None")
             if not self._has_data:
@@ -736,9 +860,30 @@ class GPR:
                 return float(v), np.asarray(g, dtype=np.float64)
 
             res = minimize(fun, th0, method=method, jac=grad is not None, **kw)
+        elif criterion in L.HINDCAST_CRITERION_IDS:
+            if grad not in (None, "exact"):
+                raise ValueError("a hindcast criterion takes grad='exact' or None")
+            if self.kernel == "netdiffusion":
+                raise ValueError("criterion 'hindcast_nlpd' / 'hindcast_sse' covers the RBF / Matern kernels (the reference kernel: hindcast after fit)")
+            if self.dtype != "f64":
+                raise ValueError("criterion 'hindcast_nlpd' / 'hindcast_sse': fp64 engine only")
+            has = getattr(self, "_has_data", False)
+            lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n if has else None, self.d if has else None)
+            if not self._has_data:
+                raise RuntimeError("optimize: no data staged; call fit() or set_data() first")
+            th0 = np.asarray(theta0, dtype=np.float64).reshape(2)
+
+            def fun(th):
+                if grad is None:
+                    return float(self.hindcast_ard(np.concatenate([np.full(self.d, th[0]), th[1:]]), lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f,
+                                                   grad=None)[0])
+                v, g = self.hindcast_objective(th, lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f)
+                return float(v), np.asarray(g, dtype=np.float64)
+
+            res = minimize(fun, th0, method=method, jac=grad is not None, **kw)
         elif criterion != "nlml":
             if criterion not in L.LOO_CRITERIA:
-                raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd' or 'cv_sse'")
+                raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd', 'cv_sse', 'hindcast_nlpd' or 'hindcast_sse'")
             if grad not in (None, "exact"):
                 raise ValueError("a leave-one-out criterion takes grad='exact' or None")
 

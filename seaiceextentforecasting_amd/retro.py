@@ -82,10 +82,11 @@ def retro_forecast(script, SIC, SIEs_dt, SIEs_trend, fmin, fmax, SST=None, gp=No
             gp.close()
 
 
-_CRITERIA = {"nlml": (None, "nlml"), "loo_nlpd": ("refit", "loo_nlpd"), "loo_sse": ("refit", "loo_sse"), "cv_nlpd": ("refit", "cv_nlpd"), "cv_sse": ("refit", "cv_sse")}
+_CRITERIA = {"nlml": (None, "nlml"), "loo_nlpd": ("refit", "loo_nlpd"), "loo_sse": ("refit", "loo_sse"), "cv_nlpd": ("refit", "cv_nlpd"), "cv_sse": ("refit", "cv_sse"),
+             "hindcast_nlpd": ("refit", "hindcast_nlpd"), "hindcast_sse": ("refit", "hindcast_sse")}
 
 
-def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sns=SGRID, gp=None, criterion="nlml", block=5, gap=0):
+def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sns=SGRID, gp=None, criterion="nlml", block=5, gap=0, lead=1, min_train=2):
     """The hyper-parameter search the reference's tables imply (north/June1st.py:210-211: indices into
     ``logspace(-7,2,20) x logspace(-3,9,20)``): nlML (north/June1st.py:246) of every (region, year) of the retro loop at
     every grid point -- 3 x years x 400 fits in one device launch, one eigendecomposition of M per (region, year).
@@ -102,7 +103,15 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
     (block + 2 gap <= 32; every (region, year) must keep a training year in every fold) -- the remedy for the optimism of leave-one-out
     on a serially correlated series.  The same things are held fixed as above: features, standardisation and M come from the full training
     set of the (region, year), (l, sn~) are held, sigma_f is re-profiled per fold; features are not re-selected per left-out block.
-    ``block`` and ``gap`` are ignored by the other criteria."""
+    ``block`` and ``gap`` are ignored by the other criteria.
+
+    ``criterion`` = "hindcast_nlpd" or "hindcast_sse": the expanding-window hindcast scores instead
+    (``SmallBatch.run(hindcast=dict(lead=lead, min_train=min_train))``, still one launch): within the training set of a (region, year), year t
+    is forecast ``lead`` steps ahead from the years [0, t - lead] alone, for every t with at least ``min_train`` training years (lead <= 32;
+    every (region, year) must have a scored year) -- the rolling-origin form of the retro loop itself (September1st_retro.py:176-248).  The
+    same things are held fixed as above: features, standardisation and M come from the full training set of the (region, year), (l, sn~)
+    are held, sigma_f is re-profiled on each prefix; features are not re-selected per origin.  ``lead`` and ``min_train`` are ignored by
+    the other criteria."""
     if criterion not in _CRITERIA:
         raise ValueError("criterion must be one of %s" % sorted(_CRITERIA))
     loo, key = _CRITERIA[criterion]
@@ -110,6 +119,9 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
     if criterion.startswith("cv_"):
         block, gap = GPR._cv_args(block, gap, loo, max_window=32)
         cv, loo = dict(block=block, gap=gap, sigma_f=loo), None
+    hc = None
+    if criterion.startswith("hindcast_"):
+        hc, loo = dict(lead=int(lead), min_train=int(min_train), sigma_f=loo), None
     tab = SCRIPT_TABLE[script]
     own = gp is None
     gp = gp or GPR(kernel="netdiffusion")
@@ -125,7 +137,7 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
                 for e in ells:
                     for s_ in sns:
                         sb.add_fit(ds, e, s_, expm="eigh")
-        nl = (sb.run(cv=cv) if cv is not None else sb.run() if loo is None else sb.run(loo=loo))[key].reshape(len(tab["regions"]), ny, len(ells), len(sns))
+        nl = (sb.run(hindcast=hc) if hc is not None else sb.run(cv=cv) if cv is not None else sb.run() if loo is None else sb.run(loo=loo))[key].reshape(len(tab["regions"]), ny, len(ells), len(sns))
         return {region: nl[k] for k, region in enumerate(tab["regions"])}
     finally:
         if own:

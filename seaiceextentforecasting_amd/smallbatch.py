@@ -124,7 +124,7 @@ class SmallBatch:
         self._fits = []
         self._packed = None
 
-    def run(self, grad=False, loo=None, cv=None):
+    def run(self, grad=False, loo=None, cv=None, hindcast=None):
         """All queued fits in one launch -> dict(sigma_f, nlml, info, sigma_n, mean [F, mmax], var [F, mmax]); with ``grad=True``
         also grad_ref [F, 2] (the reference's MLII formulae, north/June1st.py:248-252) and grad_exact [F, 2] (the derivative of the
         profiled nlML w.r.t. (log l, log sn~)); +inf where K~ is not positive definite (:254-256).
@@ -138,7 +138,29 @@ class SmallBatch:
         ``cv=dict(block=, gap=0, sigma_f="refit")``: the same single launch cross-validates every fit leave-block-out instead
         (``sigp_small_run_cv``; folds and modes as ``GPR.cv``, block + 2 gap <= 32, every fold of every data set must leave a training row):
         cv_mean, cv_var [F, nmax] (NaN beyond a data set's n), cv_nlpd, cv_sse [F] (+inf / NaN rows where K~ or a fold's block of K~^-1 is
-        not positive definite).  Mutually exclusive with ``loo`` and ``grad``."""
+        not positive definite).  Mutually exclusive with ``loo`` and ``grad``.
+
+        ``hindcast=dict(lead=1, min_train=2, sigma_f="refit")``: the same single launch validates every fit by the expanding-window hindcast
+        instead (``sigp_small_run_hindcast``; rows and modes as ``GPR.hindcast``, lead <= 32, every data set must have a scored row:
+        min_train + lead - 1 <= n - 1): hindcast_mean, hindcast_var [F, nmax] (NaN where a row is not scored and beyond a data set's n),
+        hindcast_nlpd, hindcast_sse [F] (+inf / NaN rows where K~ is not positive definite).  L~ and z are read where the factorisation left
+        them; no inverse is formed.  Mutually exclusive with ``grad``, ``loo`` and ``cv``."""
+        if hindcast is not None:
+            if loo is not None or grad or cv is not None:
+                raise ValueError("one launch forms the gradients, the leave-one-out, the leave-block-out or the hindcast predictions: run them separately")
+            if not isinstance(hindcast, dict) or set(hindcast) - {"lead", "min_train", "sigma_f"}:
+                raise ValueError("hindcast must be dict(lead=1, min_train=2, sigma_f='refit')")
+            hc_mode = hindcast.get("sigma_f", "refit")
+            if hc_mode not in L.LOO_MODES:
+                raise ValueError("sigma_f must be 'refit' or 'fixed'")
+            hc_lead, hc_mt = int(hindcast.get("lead", 1)), int(hindcast.get("min_train", 2))
+            if hc_lead < 1 or hc_lead > L.HINDCAST_SMALL_MAX_LEAD:
+                raise ValueError("hindcast: 1 <= lead <= %d required" % L.HINDCAST_SMALL_MAX_LEAD)
+            if hc_mt < 1:
+                raise ValueError("hindcast: min_train >= 1 required")
+            for X, _, _, _ in self._data:
+                if hc_mt + hc_lead - 1 > X.shape[0] - 1:
+                    raise ValueError("hindcast: a data set of %d rows has no scored row (min_train + lead - 1 = %d)" % (X.shape[0], hc_mt + hc_lead - 1))
         if loo is not None and loo not in L.LOO_MODES:
             raise ValueError("loo must be None, 'refit' or 'fixed'")
         if loo is not None and grad:
@@ -163,6 +185,15 @@ class SmallBatch:
         ms = max(self._mmax, 1)
         out = np.zeros((F, 8 if grad else 4)); mean = np.full((F, ms), np.nan); var = np.full((F, ms), np.nan)
         gp = self.gp
+        if hindcast is not None:
+            nmax = max(s[1].shape[0] for s in self._sets)
+            out = np.zeros((F, 6)); hmean = np.full((F, nmax), np.nan); hvar = np.full((F, nmax), np.nan)
+            gp._check(gp._lib.sigp_small_run_hindcast(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), hc_lead, hc_mt, L.LOO_MODES[hc_mode], L.ptr(out), L.ptr(mean), L.ptr(var), ms,
+                                                      L.ptr(hmean), L.ptr(hvar), nmax), "small_run_hindcast")
+            gp._fitted = False
+            return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
+                        mean=mean[:, :self._mmax], var=var[:, :self._mmax], hindcast_mean=hmean, hindcast_var=hvar,
+                        hindcast_nlpd=out[:, 4].copy(), hindcast_sse=out[:, 5].copy())
         if cv is not None:
             nmax = max(s[1].shape[0] for s in self._sets)
             out = np.zeros((F, 6)); cmean = np.full((F, nmax), np.nan); cvar = np.full((F, nmax), np.nan)
