@@ -444,7 +444,12 @@ int sigp_cv_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, c
  * LDS as in sigp_small_run_loo, then per fold P_SS from its columns, a |S| x |S| Cholesky and the solves in LDS): out6 [nprob][6] =
  * sigma_f, nlML, info, sigma_n, nlpd, sse; cv_mean / cv_var [nprob][nstride >= largest n of the upload], NaN beyond a set's n.
  * block + 2 gap <= SIGP_CV_SMALL_MAX_WINDOW; every fold of every named data set must leave a training row.  info > 0 or a failed pivot of
- * a P_SS: nlpd = sse = +inf and NaN rows. */
+ * a P_SS: nlpd = sse = +inf and NaN rows.
+ * LDS: the folds need 17 152 bytes behind the plain image, so this launch picks its OWN feature chunk -- the largest of {the upload's, 16, 8}
+ * that leaves them.  Largest order of the upload by its largest m: 128 (m <= 2), 127 (m = 3 .. 5), 126 (m = 6), 125 (m = 7, 8); beyond it
+ * SIGP_BAD_ARG (the handle stays usable for the other launches).  Where that chunk is smaller than the upload's (largest order from 119 at
+ * m = 0, 118 at m = 1, 2, 114 at m = 8) and a set has more features than it, K~ is summed in shorter pieces: sigma_f, nlML, sigma_n, mean
+ * and var of this launch agree with sigp_small_run's to rounding, not bit for bit. */
 int sigp_small_run_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block,
                       int64_t gap, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var,
                       int64_t nstride);

@@ -69,7 +69,15 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   if (hc && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: hc_mean / hc_var [nprob][nstride >= %d] required", h->sm_nmax);
   if (loo && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_%s: %s_mean / %s_var [nprob][nstride >= %d] required", cv ? "cv" : "loo", cv ? "cv" : "loo", cv ? "cv" : "loo", h->sm_nmax);
   constexpr long SM_LDS_MAX = 160 * 1024 - 64;
-  if (cv && h->sm_lds + SM_CV_EXTRA_BYTES > SM_LDS_MAX) return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes", h->sm_nmax, h->sm_mmax, SM_CV_EXTRA_BYTES);
+  // the leave-block-out launch picks its own feature chunk: the largest of {the upload's, 16, 8} whose image leaves room for the folds
+  int cv_ch = 0; long cv_lds = 0;
+  if (cv) {
+    cv_ch = h->sm_ch;
+    while (cv_ch > 8 && smallgp_lds_bytes(h->sm_nmax, h->sm_mmax, cv_ch) + SM_CV_EXTRA_BYTES > SM_LDS_MAX) cv_ch /= 2;
+    cv_lds = smallgp_lds_bytes(h->sm_nmax, h->sm_mmax, cv_ch) + SM_CV_EXTRA_BYTES;
+    if (cv_lds > SM_LDS_MAX)
+      return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes (feature chunk 8: %ld of %ld bytes)", h->sm_nmax, h->sm_mmax, SM_CV_EXTRA_BYTES, cv_lds, SM_LDS_MAX);
+  }
   std::vector<char> cv_checked(cv ? h->sm_sets.size() : 0, 0);
   if (h->sm_mmax > 0 && (!mean || !var || mstride < h->sm_mmax)) return fail(h, SIGP_BAD_ARG, "small_run: mean / var [nprob][mstride >= %d] required", h->sm_mmax);
   HIPCHK(h, hipSetDevice(h->device));
@@ -141,8 +149,8 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
       hipLaunchKernelGGL((smallgp_kernel<256, false, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A,
                          h->sm_y, h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)hc_lead, (int)hc_min_train);
     else if (cv)
-      hipLaunchKernelGGL((smallgp_kernel<256, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)(h->sm_lds + SM_CV_EXTRA_BYTES), st, h->sm_sets_dev, h->sm_probs,
-                         h->sm_A, h->sm_y, h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)cv_block, (int)cv_gap);
+      hipLaunchKernelGGL((smallgp_kernel<256, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)cv_lds, st, h->sm_sets_dev, h->sm_probs,
+                         h->sm_A, h->sm_y, h->sm_lam, cv_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)cv_block, (int)cv_gap);
     else if (loo)
       hipLaunchKernelGGL((smallgp_kernel<256, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y,
                          h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode);

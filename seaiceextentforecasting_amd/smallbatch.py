@@ -138,7 +138,11 @@ class SmallBatch:
         ``cv=dict(block=, gap=0, sigma_f="refit")``: the same single launch cross-validates every fit leave-block-out instead
         (``sigp_small_run_cv``; folds and modes as ``GPR.cv``, block + 2 gap <= 32, every fold of every data set must leave a training row):
         cv_mean, cv_var [F, nmax] (NaN beyond a data set's n), cv_nlpd, cv_sse [F] (+inf / NaN rows where K~ or a fold's block of K~^-1 is
-        not positive definite).  Mutually exclusive with ``loo`` and ``grad``.
+        not positive definite).  Mutually exclusive with ``loo`` and ``grad``.  The folds' LDS limits the largest order of the batch by its
+        largest m: 128 (m <= 2), 127 (m = 3 .. 5), 126 (m = 6), 125 (m = 7, 8); beyond it ValueError, and the batch still runs every other
+        launch.  To fit, the launch may build K~ from shorter feature chunks than ``run()`` does (largest order from 119 at m = 0, 118 at
+        m = 1, 2, 114 at m = 8): where a set then has more features than the chunk, sigma_f, nlml, sigma_n, mean and var of this launch agree
+        with ``run()``'s to rounding, not bit for bit.
 
         ``hindcast=dict(lead=1, min_train=2, sigma_f="refit")``: the same single launch validates every fit by the expanding-window hindcast
         instead (``sigp_small_run_hindcast``; rows and modes as ``GPR.hindcast``, lead <= 32, every data set must have a scored row:
