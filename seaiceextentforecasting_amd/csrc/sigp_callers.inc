@@ -26,10 +26,8 @@ int sigp_small_upload(sigp_handle* h, int64_t nsets, const int64_t* n, const int
     nmax = std::max(nmax, s.n); mmax = std::max(mmax, s.m);
   }
   // feature chunk: the largest of 32 / 16 / 8 whose LDS image fits beside the bordered matrix of the largest data set
-  constexpr long LDS_MAX = 160 * 1024 - 64;
-  int ch = 32;
-  while (ch > 8 && smallgp_lds_bytes(nmax, mmax, ch) > LDS_MAX) ch /= 2;
-  if (smallgp_lds_bytes(nmax, mmax, ch) > LDS_MAX) return fail(h, SIGP_BAD_ARG, "small_upload: n = %d with m = %d does not fit in LDS", nmax, mmax);
+  const int ch = small_pick_chunk(nmax, mmax, SmallFlavour::Plain, 32);
+  if (!ch) return fail(h, SIGP_BAD_ARG, "small_upload: n = %d with m = %d does not fit in LDS", nmax, mmax);
   int rc;
   if ((rc = ensure(h, &h->sm_A, &h->cap_sm_A, totA))) return rc;
   if ((rc = ensure(h, &h->sm_y, &h->cap_sm_y, toty))) return rc;
@@ -41,7 +39,7 @@ int sigp_small_upload(sigp_handle* h, int64_t nsets, const int64_t* n, const int
   HIPCHK(h, hipMemcpy(h->sm_y, y_pool, (size_t)toty * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->sm_lam, lam_pool, (size_t)totl * sizeof(double), hipMemcpyHostToDevice));
   h->sm_sets.swap(sets);
-  h->sm_ch = ch; h->sm_mmax = mmax; h->sm_nmax = nmax; h->sm_lds = smallgp_lds_bytes(nmax, mmax, ch);
+  h->sm_ch = ch; h->sm_mmax = mmax; h->sm_nmax = nmax; h->sm_lds = SmallLayout{nmax, mmax, ch, SmallFlavour::Plain}.bytes();
   h->sm_lam_len = totl; h->sm_has_dlam = false;
   return SIGP_OK;
 }
@@ -57,26 +55,61 @@ int sigp_small_set_dweights(sigp_handle* h, const double* dlam_pool, int64_t cou
   return SIGP_OK;
 }
 
+// what a launch forms besides the fits, and where it goes
+struct SmallRequest {
+  SmallFlavour flavour = SmallFlavour::Plain;
+  int sigma_mode = 0;                                  // Loo, Cv, Hindcast: SIGP_LOO_REFIT / SIGP_LOO_FIXED
+  int64_t block = 0, gap = 0;                          // Cv
+  int64_t lead = 0, min_train = 0;                     // Hindcast
+  double *row_mean = nullptr, *row_var = nullptr;      // Loo, Cv, Hindcast: the caller's [nprob][pitch]
+  int64_t pitch = 0;
+};
+
+extern "C++" {
+// one launch of smallgp_kernel<NT, F> over nprob fits; the kernel's dynamic-LDS limit is lifted once per device
+template <int NT, SmallFlavour F>
+static hipError_t small_launch(sigp_handle* h, hipStream_t st, int64_t nprob, long lds, int ch, double* d_out, double* d_mean, double* d_var, int ms, const SmallExtras& x) {
+  static AttrOnce attr;
+  const hipError_t e = attr.set(h->device, (const void*)smallgp_kernel<NT, F>, (int)SM_LDS_MAX);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((smallgp_kernel<NT, F>), dim3((unsigned)nprob), dim3(NT), (size_t)lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y, h->sm_lam, ch, d_out, d_mean, d_var, ms,
+                     h->sm_has_dlam ? h->sm_dlam : nullptr, x);
+  return hipGetLastError();
+}
+}  // extern "C++"
+
+// adds the flops of one fit of the set s in the flavour of rq
+static void small_count_flops(double& fl, const SmallSet& s, const SmallRequest& rq) {
+  const double n = s.n, inverse = n * n * n / 3;      // X = L~^-1
+  fl += n * n * s.N + n * n * n / 3 + 2.0 * n * n * (1 + s.m);
+  switch (rq.flavour) {
+    case SmallFlavour::Plain: break;
+    case SmallFlavour::Grad: fl += n * n * s.N + inverse + 2.0 * n * s.N; break;      // X A, A^T a~
+    case SmallFlavour::Loo: fl += inverse + 2.0 * n * n; break;                       // X's column norms and X^T z
+    case SmallFlavour::Cv: fl += inverse + 2.0 * n * n; fl += n * n * (rq.block + 2.0 * rq.gap); break;   // ... and the folds' P_SS from X's columns
+    case SmallFlavour::Hindcast: fl += 4.0 * n * rq.lead + 2.0 * n * n; break;        // the row segments and the prefix sums of z^2
+  }
+}
+
 static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out,
-                          double* mean, double* var, int64_t mstride, bool grad, int loo_mode = -1, double* loo_mean = nullptr,
-                          double* loo_var = nullptr, int64_t nstride = 0, int64_t cv_block = 0, int64_t cv_gap = 0, int64_t hc_lead = 0,
-                          int64_t hc_min_train = 0) {
+                          double* mean, double* var, int64_t mstride, const SmallRequest& rq) {
   if (!h || h->sm_sets.empty()) return fail(h, SIGP_BAD_ARG, "small_run: call sigp_small_upload first");
-  const bool hc = hc_lead != 0;                        // hindcast validation: rows and scores travel like the leave-one-out ones
-  const bool cv = cv_block != 0 || cv_gap != 0;       // leave-block-out: rows and scores travel like the leave-one-out ones
+  const SmallFlavour F = rq.flavour;
+  const bool cv = F == SmallFlavour::Cv, hc = F == SmallFlavour::Hindcast, rows = small_has_rows(F);
+  const char* cvloo = cv ? "cv" : "loo";
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
-  const bool loo = loo_mode >= 0;
-  if (hc && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: hc_mean / hc_var [nprob][nstride >= %d] required", h->sm_nmax);
-  if (loo && (!loo_mean || !loo_var || nstride < h->sm_nmax)) return fail(h, SIGP_BAD_ARG, "small_run_%s: %s_mean / %s_var [nprob][nstride >= %d] required", cv ? "cv" : "loo", cv ? "cv" : "loo", cv ? "cv" : "loo", h->sm_nmax);
-  constexpr long SM_LDS_MAX = 160 * 1024 - 64;
+  if (rows && (!rq.row_mean || !rq.row_var || rq.pitch < h->sm_nmax)) {
+    if (hc) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: hc_mean / hc_var [nprob][nstride >= %d] required", h->sm_nmax);
+    return fail(h, SIGP_BAD_ARG, "small_run_%s: %s_mean / %s_var [nprob][nstride >= %d] required", cvloo, cvloo, cvloo, h->sm_nmax);
+  }
   // the leave-block-out launch picks its own feature chunk: the largest of {the upload's, 16, 8} whose image leaves room for the folds
-  int cv_ch = 0; long cv_lds = 0;
+  int ch = h->sm_ch; long lds = h->sm_lds;
   if (cv) {
-    cv_ch = h->sm_ch;
-    while (cv_ch > 8 && smallgp_lds_bytes(h->sm_nmax, h->sm_mmax, cv_ch) + SM_CV_EXTRA_BYTES > SM_LDS_MAX) cv_ch /= 2;
-    cv_lds = smallgp_lds_bytes(h->sm_nmax, h->sm_mmax, cv_ch) + SM_CV_EXTRA_BYTES;
-    if (cv_lds > SM_LDS_MAX)
-      return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes (feature chunk 8: %ld of %ld bytes)", h->sm_nmax, h->sm_mmax, SM_CV_EXTRA_BYTES, cv_lds, SM_LDS_MAX);
+    ch = small_pick_chunk(h->sm_nmax, h->sm_mmax, F, h->sm_ch);
+    lds = SmallLayout{h->sm_nmax, h->sm_mmax, ch ? ch : 8, F}.bytes();
+    if (!ch)
+      return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes (feature chunk 8: %ld of %ld bytes)", h->sm_nmax, h->sm_mmax,
+                  lds - SmallLayout{h->sm_nmax, h->sm_mmax, 8, SmallFlavour::Plain}.bytes(), lds, SM_LDS_MAX);
   }
   std::vector<char> cv_checked(cv ? h->sm_sets.size() : 0, 0);
   if (h->sm_mmax > 0 && (!mean || !var || mstride < h->sm_mmax)) return fail(h, SIGP_BAD_ARG, "small_run: mean / var [nprob][mstride >= %d] required", h->sm_mmax);
@@ -85,21 +118,22 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   for (int64_t i = 0; i < nprob; ++i) {
     if (set_index[i] < 0 || set_index[i] >= (int64_t)h->sm_sets.size()) return fail(h, SIGP_BAD_ARG, "small_run: fit %ld names data set %ld of %zu", (long)i, (long)set_index[i], h->sm_sets.size());
     if (!(sn_tilde[i] >= 0) || !std::isfinite(ell[i])) return fail(h, SIGP_BAD_ARG, "small_run: finite ell and sn_tilde >= 0 required");
-    if (hc && hc_min_train + hc_lead - 1 > h->sm_sets[(size_t)set_index[i]].n - 1)
+    const int n = h->sm_sets[(size_t)set_index[i]].n;
+    if (hc && rq.min_train + rq.lead - 1 > n - 1)
       return fail(h, SIGP_BAD_ARG, "small_run_hindcast: fit %ld names a data set without a scored row (min_train + lead - 1 = %lld > n - 1 = %d)", (long)i,
-                  (long long)(hc_min_train + hc_lead - 1), h->sm_sets[(size_t)set_index[i]].n - 1);
-    if (loo && !hc && h->sm_sets[(size_t)set_index[i]].n < 2) return fail(h, SIGP_BAD_ARG, "small_run_%s: fit %ld names a data set of one point; cross-validation needs n >= 2", cv ? "cv" : "loo", (long)i);
+                  (long long)(rq.min_train + rq.lead - 1), n - 1);
+    if (rows && !hc && n < 2) return fail(h, SIGP_BAD_ARG, "small_run_%s: fit %ld names a data set of one point; cross-validation needs n >= 2", cvloo, (long)i);
     if (cv && !cv_checked[(size_t)set_index[i]]) {
-      if (const char* why = cv_check_folds(h->sm_sets[(size_t)set_index[i]].n, cv_block, cv_gap, SIGP_CV_SMALL_MAX_WINDOW))
-        return fail(h, SIGP_BAD_ARG, "small_run_cv: fit %ld: %s (block = %lld, gap = %lld, n = %d, SIGP_CV_SMALL_MAX_WINDOW = %d)", (long)i, why, (long long)cv_block, (long long)cv_gap,
-                    h->sm_sets[(size_t)set_index[i]].n, SIGP_CV_SMALL_MAX_WINDOW);
+      if (const char* why = cv_check_folds(n, rq.block, rq.gap, SIGP_CV_SMALL_MAX_WINDOW))
+        return fail(h, SIGP_BAD_ARG, "small_run_cv: fit %ld: %s (block = %lld, gap = %lld, n = %d, SIGP_CV_SMALL_MAX_WINDOW = %d)", (long)i, why, (long long)rq.block, (long long)rq.gap,
+                    n, SIGP_CV_SMALL_MAX_WINDOW);
       cv_checked[(size_t)set_index[i]] = 1;
     }
     probs[(size_t)i] = SmallProb{(int)set_index[i], 0, ell[i], sn_tilde[i]};
   }
   const long ms = std::max<int64_t>(mstride, 1);
-  const long ns = loo ? (long)nstride : 0;
-  const long ow = grad ? 8 : loo ? 6 : 4;
+  const long ns = rows ? (long)rq.pitch : 0;
+  const long ow = small_out_width(F);
   const long per = ow + 2 * ms + 2 * ns;
   if (h->cap_sm_probs < nprob) {
     if (h->sm_probs) HIPCHK(h, hipFree(h->sm_probs));
@@ -112,58 +146,27 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   hipStream_t st = h->slots[0].s_upd;
   HIPCHK(h, hipMemcpyAsync(h->sm_probs, probs.data(), probs.size() * sizeof(SmallProb), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemsetAsync(h->sm_out, 0xff, (size_t)(nprob * per) * sizeof(double), st));   // NaN wherever a set has fewer test points than mstride
-  static AttrOnce attr64, attr256, attr256g;
-  HIPCHK(h, attr64.set(h->device, (const void*)smallgp_kernel<64, false>, 160 * 1024 - 64));
-  HIPCHK(h, attr256.set(h->device, (const void*)smallgp_kernel<256, false>, 160 * 1024 - 64));
-  HIPCHK(h, attr256g.set(h->device, (const void*)smallgp_kernel<256, true>, 160 * 1024 - 64));
   double* d_out = h->sm_out;
   double* d_mean = h->sm_out + nprob * ow;
   double* d_var = d_mean + nprob * ms;
   double* d_lmean = d_var + nprob * ms;        // [nprob][ns] each; NaN beyond a set's n (the memset above)
   double* d_lvar = d_lmean + nprob * ns;
-  if (hc) {
-    static AttrOnce attr256h;
-    HIPCHK(h, attr256h.set(h->device, (const void*)smallgp_kernel<256, false, false, false, true>, 160 * 1024 - 64));
-  } else if (cv) {
-    static AttrOnce attr256c;
-    HIPCHK(h, attr256c.set(h->device, (const void*)smallgp_kernel<256, false, false, true>, 160 * 1024 - 64));
-  } else if (loo) {
-    static AttrOnce attr256l;
-    HIPCHK(h, attr256l.set(h->device, (const void*)smallgp_kernel<256, false, true>, 160 * 1024 - 64));
-  }
   {
     double fl = 0;
-    for (const auto& pb : probs) {
-      const SmallSet& s = h->sm_sets[(size_t)pb.set];
-      fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n * (1 + s.m);
-      if (grad) fl += (double)s.n * s.n * s.N + (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.N;      // X = L~^-1, X A, A^T a~
-      if (hc) fl += 4.0 * s.n * hc_lead + 2.0 * s.n * s.n;                                         // the row segments and the prefix sums of z^2
-      else if (loo) fl += (double)s.n * s.n * s.n / 3 + 2.0 * s.n * s.n;                            // X = L~^-1, its column norms and X^T z
-      if (cv) fl += (double)s.n * s.n * (cv_block + 2.0 * cv_gap);                                  // the folds' P_SS from X's columns
-    }
+    for (const auto& pb : probs) small_count_flops(fl, h->sm_sets[(size_t)pb.set], rq);
     ProfScope ps(h, st, SIGP_KC_SMALL, fl, 0.0);
-    // orders up to 64 (the reference's n <= 45): one wavefront per fit; larger: four
-    // measured on the reference-size grid (48 000 fits, n = 6 .. 45): four wavefronts per fit 1.02 ms, one wavefront per fit 1.71 ms
-    const double* d_dlam = h->sm_has_dlam ? h->sm_dlam : nullptr;
-    if (hc)
-      hipLaunchKernelGGL((smallgp_kernel<256, false, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A,
-                         h->sm_y, h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)hc_lead, (int)hc_min_train);
-    else if (cv)
-      hipLaunchKernelGGL((smallgp_kernel<256, false, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)cv_lds, st, h->sm_sets_dev, h->sm_probs,
-                         h->sm_A, h->sm_y, h->sm_lam, cv_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode, (int)cv_block, (int)cv_gap);
-    else if (loo)
-      hipLaunchKernelGGL((smallgp_kernel<256, false, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y,
-                         h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam, d_lmean, d_lvar, (int)ns, loo_mode);
-    else if (grad)
-      hipLaunchKernelGGL((smallgp_kernel<256, true>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y,
-                         h->sm_lam, h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam);
-    else if (h->sm_nmax <= 64 && h->opt_small_nt64)
-      hipLaunchKernelGGL((smallgp_kernel<64, false>), dim3((unsigned)nprob), dim3(64), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y, h->sm_lam,
-                         h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam);
-    else
-      hipLaunchKernelGGL((smallgp_kernel<256, false>), dim3((unsigned)nprob), dim3(256), (size_t)h->sm_lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y, h->sm_lam,
-                         h->sm_ch, d_out, d_mean, d_var, (int)ms, d_dlam);
-    HIPCHK(h, hipGetLastError());
+    const SmallExtras x{d_lmean, d_lvar, (int)ns, rq.sigma_mode, (int)rq.block, (int)rq.gap, (int)rq.lead, (int)rq.min_train};
+    decltype(&small_launch<256, SmallFlavour::Plain>) launch = nullptr;
+    switch (F) {
+      // four wavefronts per fit at every order; one per fit (orders up to 64) is a measurement switch: on the reference-size grid
+      // (48 000 fits, n = 6 .. 45) four wavefronts per fit take 1.02 ms, one wavefront per fit 1.71 ms
+      case SmallFlavour::Plain: launch = h->sm_nmax <= 64 && h->opt_small_nt64 ? small_launch<64, SmallFlavour::Plain> : small_launch<256, SmallFlavour::Plain>; break;
+      case SmallFlavour::Grad: launch = small_launch<256, SmallFlavour::Grad>; break;
+      case SmallFlavour::Loo: launch = small_launch<256, SmallFlavour::Loo>; break;
+      case SmallFlavour::Cv: launch = small_launch<256, SmallFlavour::Cv>; break;
+      case SmallFlavour::Hindcast: launch = small_launch<256, SmallFlavour::Hindcast>; break;
+    }
+    HIPCHK(h, launch(h, st, nprob, lds, ch, d_out, d_mean, d_var, (int)ms, x));
   }
   HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)nprob * ow * sizeof(double), hipMemcpyDeviceToHost, st));
   if (h->sm_mmax > 0) {
@@ -171,7 +174,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
     HIPCHK(h, hipMemcpyAsync(mean, d_mean, (size_t)nprob * ms * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(var, d_var, (size_t)nprob * ms * sizeof(double), hipMemcpyDeviceToHost, st));
   }
-  if (loo) {
+  if (rows) {
     // tens of MB for a retro grid: through pinned memory of the handle's own (a pageable destination of that size makes the
     // runtime pin and unpin the caller's pages: 25 ms around a 1 ms launch), then one host copy into the caller's arrays
     const long tot = 2 * nprob * ns;
@@ -184,36 +187,57 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
     HIPCHK(h, hipMemcpyAsync(h->sm_loo_host, d_lmean, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPCHK(h, hipStreamSynchronize(st));
-  if (loo) {
-    memcpy(loo_mean, h->sm_loo_host, (size_t)nprob * ns * sizeof(double));
-    memcpy(loo_var, h->sm_loo_host + nprob * ns, (size_t)nprob * ns * sizeof(double));
+  if (rows) {
+    memcpy(rq.row_mean, h->sm_loo_host, (size_t)nprob * ns * sizeof(double));
+    memcpy(rq.row_var, h->sm_loo_host + nprob * ns, (size_t)nprob * ns * sizeof(double));
   }
   return SIGP_OK;
 }
 
 int sigp_small_run(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out,
                    double* mean, double* var, int64_t mstride) {
-  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out, mean, var, mstride, false);
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out, mean, var, mstride, SmallRequest{});
 }
 
 int sigp_small_run_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, double* out8,
                         double* mean, double* var, int64_t mstride) {
-  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, true);
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::Grad;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, rq);
 }
 
-// sigp_small_run with the leave-one-out cross-validation of every fit in the same single launch (smallgp_kernel<256, false, true>)
+// sigp_small_run with the leave-one-out cross-validation of every fit in the same single launch (SmallFlavour::Loo)
 int sigp_small_run_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode,
                        double* out6, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride) {
   if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_loo: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
-  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, loo_mean, loo_var, nstride);
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::Loo; rq.sigma_mode = sigma_mode;
+  rq.row_mean = loo_mean; rq.row_var = loo_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
 }
 
-// sigp_small_run with the leave-block-out cross-validation of every fit in the same single launch (smallgp_kernel<256, false, false, true>)
+// sigp_small_run with the leave-block-out cross-validation of every fit in the same single launch (SmallFlavour::Cv)
 int sigp_small_run_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block, int64_t gap, int sigma_mode,
                       double* out6, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var, int64_t nstride) {
   if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_cv: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
   if (block < 1 || gap < 0) return fail(h, SIGP_BAD_ARG, "small_run_cv: block >= 1 and gap >= 0 required");
-  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, cv_mean, cv_var, nstride, block, gap);
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::Cv; rq.sigma_mode = sigma_mode; rq.block = block; rq.gap = gap;
+  rq.row_mean = cv_mean; rq.row_var = cv_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
+}
+
+// sigp_small_run with the expanding-window hindcast validation of every fit in the same single launch (SmallFlavour::Hindcast:
+// L~ and z are read where the factorisation left them in LDS; no inverse is formed)
+int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead, int64_t min_train,
+                            int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* hc_mean, double* hc_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (lead < 1 || lead > SIGP_HINDCAST_SMALL_MAX_LEAD) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: 1 <= lead <= %d required (got %lld)", (int)SIGP_HINDCAST_SMALL_MAX_LEAD, (long long)lead);
+  if (min_train < 1) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: min_train >= 1 required (got %lld)", (long long)min_train);
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::Hindcast; rq.sigma_mode = sigma_mode; rq.lead = lead; rq.min_train = min_train;
+  rq.row_mean = hc_mean; rq.row_var = hc_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
 }
 
 // ---- ComplexNetworks tau(): cell-to-cell correlation matrix + thresholded mean (ComplexNetworks.py:31-47) ------------
@@ -306,13 +330,3 @@ int sigp_detrend(sigp_handle* h, const double* data, int64_t P, int64_t T, int64
   return SIGP_OK;
 }
 
-
-// sigp_small_run with the expanding-window hindcast validation of every fit in the same single launch (smallgp_kernel<256, false, false, false, true>:
-// L~ and z are read where the factorisation left them in LDS; no inverse is formed)
-int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead, int64_t min_train,
-                            int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* hc_mean, double* hc_var, int64_t nstride) {
-  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
-  if (lead < 1 || lead > SIGP_HINDCAST_SMALL_MAX_LEAD) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: 1 <= lead <= %d required (got %lld)", (int)SIGP_HINDCAST_SMALL_MAX_LEAD, (long long)lead);
-  if (min_train < 1) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: min_train >= 1 required (got %lld)", (long long)min_train);
-  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, false, sigma_mode, hc_mean, hc_var, nstride, 0, 0, lead, min_train);
-}

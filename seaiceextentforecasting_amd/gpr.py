@@ -347,6 +347,11 @@ class GPR:
         [len(ells), len(sns)], +inf where K~ is not SPD.  Reference kernel (n <= 128): one launch, one workgroup per grid point."""
         if sigma_f not in L.LOO_MODES:
             raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        return self._score_grid(X, y, ells, sns, group, M, "loo", sigma_f, lambda E, S: self.loo_batch(E, S, sigma_f=sigma_f, group=group, predictions=False))
+
+    def _score_grid(self, X, y, ells, sns, group, M, prefix, small_arg, batch):
+        """what ``loo_grid``, ``cv_grid`` and ``hindcast_grid`` do behind their own checks: the (l, sn~) mesh for one data set through
+        ``SmallBatch.run(prefix=small_arg)`` (reference kernel) or ``upload_batch`` and ``batch(E, S)``; dict(nlpd, sse), each [len(ells), len(sns)]"""
         ells = np.asarray(ells, dtype=np.float64).reshape(-1)
         sns = np.asarray(sns, dtype=np.float64).reshape(-1)
         E, S = np.meshgrid(ells, sns, indexing="ij")
@@ -356,11 +361,11 @@ class GPR:
             ds = sb.add_dataset(X, y, None, M)
             for e, s_ in zip(E.reshape(-1), S.reshape(-1)):
                 sb.add_fit(ds, e, s_, expm=self._expm)
-            r = sb.run(loo=sigma_f)
-            nlpd, sse = r["loo_nlpd"], r["loo_sse"]
+            r = sb.run(**{prefix: small_arg})
+            nlpd, sse = r[prefix + "_nlpd"], r[prefix + "_sse"]
         else:
             self.upload_batch(L.f64(X, 2), y, None, group=group)
-            r = self.loo_batch(E.reshape(-1), S.reshape(-1), sigma_f=sigma_f, group=group, predictions=False)
+            r = batch(E.reshape(-1), S.reshape(-1))
             nlpd, sse = r["nlpd"], r["sse"]
         return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
 
@@ -427,24 +432,10 @@ class GPR:
         """The hindcast scores on the (l, sn~) grid for one data set, shaped like ``loo_grid``: dict(nlpd, sse), each [len(ells), len(sns)],
         +inf where K~ is not SPD.  Reference kernel (n <= 128, lead <= 32): one launch, one workgroup per grid point
         (``SmallBatch.run(hindcast=...)``).  ``min_train=None`` means max(2, d + 1), as in ``hindcast``."""
-        ells = np.asarray(ells, dtype=np.float64).reshape(-1)
-        sns = np.asarray(sns, dtype=np.float64).reshape(-1)
-        E, S = np.meshgrid(ells, sns, indexing="ij")
         Xa = np.asarray(X)
         lead, min_train = self._hindcast_args(lead, min_train, sigma_f, Xa.shape[0], Xa.shape[1])
-        if self.kernel == "netdiffusion":
-            from .smallbatch import SmallBatch
-            sb = SmallBatch(self)
-            ds = sb.add_dataset(X, y, None, M)
-            for e, s_ in zip(E.reshape(-1), S.reshape(-1)):
-                sb.add_fit(ds, e, s_, expm=self._expm)
-            r = sb.run(hindcast=dict(lead=lead, min_train=min_train, sigma_f=sigma_f))
-            nlpd, sse = r["hindcast_nlpd"], r["hindcast_sse"]
-        else:
-            self.upload_batch(L.f64(X, 2), y, None, group=group)
-            r = self.hindcast_batch(E.reshape(-1), S.reshape(-1), lead=lead, min_train=min_train, sigma_f=sigma_f, group=group, predictions=False)
-            nlpd, sse = r["nlpd"], r["sse"]
-        return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
+        return self._score_grid(X, y, ells, sns, group, M, "hindcast", dict(lead=lead, min_train=min_train, sigma_f=sigma_f),
+                                lambda E, S: self.hindcast_batch(E, S, lead=lead, min_train=min_train, sigma_f=sigma_f, group=group, predictions=False))
 
     # ---- leave-block-out cross-validation --------------------------------------------------------
     @staticmethod
@@ -511,22 +502,8 @@ class GPR:
         grid point (``SmallBatch.run(cv=...)``); the other kernels go through ``cv_batch``."""
         small = self.kernel == "netdiffusion"
         block, gap = self._cv_args(block, gap, sigma_f, max_window=L.CV_SMALL_MAX_WINDOW if small else L.CV_MAX_WINDOW, n=np.shape(X)[0])
-        ells = np.asarray(ells, dtype=np.float64).reshape(-1)
-        sns = np.asarray(sns, dtype=np.float64).reshape(-1)
-        E, S = np.meshgrid(ells, sns, indexing="ij")
-        if small:
-            from .smallbatch import SmallBatch
-            sb = SmallBatch(self)
-            ds = sb.add_dataset(X, y, None, M)
-            for e, s_ in zip(E.reshape(-1), S.reshape(-1)):
-                sb.add_fit(ds, e, s_, expm=self._expm)
-            r = sb.run(cv=dict(block=block, gap=gap, sigma_f=sigma_f))
-            nlpd, sse = r["cv_nlpd"], r["cv_sse"]
-        else:
-            self.upload_batch(L.f64(X, 2), y, None, group=group)
-            r = self.cv_batch(E.reshape(-1), S.reshape(-1), block, gap=gap, sigma_f=sigma_f, group=group, predictions=False)
-            nlpd, sse = r["nlpd"], r["sse"]
-        return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
+        return self._score_grid(X, y, ells, sns, group, M, "cv", dict(block=block, gap=gap, sigma_f=sigma_f),
+                                lambda E, S: self.cv_batch(E, S, block, gap=gap, sigma_f=sigma_f, group=group, predictions=False))
 
     # ---- MLII (north/June1st.py:235-257) -------------------------------------------------------
     def nlml(self, theta, grad="ref"):

@@ -186,41 +186,37 @@ class SmallBatch:
             arr = np.asarray(self._fits, dtype=np.float64)
             self._packed = (np.ascontiguousarray(arr[:, 0], dtype=np.int64), np.ascontiguousarray(arr[:, 1]), np.ascontiguousarray(arr[:, 2]))
         si, ell, sn = self._packed
-        ms = max(self._mmax, 1)
-        out = np.zeros((F, 8 if grad else 4)); mean = np.full((F, ms), np.nan); var = np.full((F, ms), np.nan)
-        gp = self.gp
         if hindcast is not None:
+            flavour, extra = "hindcast", (hc_lead, hc_mt, L.LOO_MODES[hc_mode])
+        elif cv is not None:
+            flavour, extra = "cv", (cv_block, cv_gap, L.LOO_MODES[cv_mode])
+        elif loo is not None:
+            flavour, extra = "loo", (L.LOO_MODES[loo],)
+        else:
+            flavour, extra = ("grad" if grad else "plain"), ()
+        prefix, fn, what, width = self._FLAVOURS[flavour]
+        ms = max(self._mmax, 1)
+        out = np.zeros((F, width)); mean = np.full((F, ms), np.nan); var = np.full((F, ms), np.nan)
+        args = extra + (L.ptr(out), L.ptr(mean), L.ptr(var), ms)
+        if prefix:       # a prediction per training row
             nmax = max(s[1].shape[0] for s in self._sets)
-            out = np.zeros((F, 6)); hmean = np.full((F, nmax), np.nan); hvar = np.full((F, nmax), np.nan)
-            gp._check(gp._lib.sigp_small_run_hindcast(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), hc_lead, hc_mt, L.LOO_MODES[hc_mode], L.ptr(out), L.ptr(mean), L.ptr(var), ms,
-                                                      L.ptr(hmean), L.ptr(hvar), nmax), "small_run_hindcast")
-            gp._fitted = False
-            return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
-                        mean=mean[:, :self._mmax], var=var[:, :self._mmax], hindcast_mean=hmean, hindcast_var=hvar,
-                        hindcast_nlpd=out[:, 4].copy(), hindcast_sse=out[:, 5].copy())
-        if cv is not None:
-            nmax = max(s[1].shape[0] for s in self._sets)
-            out = np.zeros((F, 6)); cmean = np.full((F, nmax), np.nan); cvar = np.full((F, nmax), np.nan)
-            gp._check(gp._lib.sigp_small_run_cv(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), cv_block, cv_gap, L.LOO_MODES[cv_mode], L.ptr(out), L.ptr(mean), L.ptr(var), ms,
-                                                L.ptr(cmean), L.ptr(cvar), nmax), "small_run_cv")
-            gp._fitted = False
-            return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
-                        mean=mean[:, :self._mmax], var=var[:, :self._mmax], cv_mean=cmean, cv_var=cvar,
-                        cv_nlpd=out[:, 4].copy(), cv_sse=out[:, 5].copy())
-        if loo is not None:
-            nmax = max(s[1].shape[0] for s in self._sets)
-            out = np.zeros((F, 6)); lmean = np.full((F, nmax), np.nan); lvar = np.full((F, nmax), np.nan)
-            gp._check(gp._lib.sigp_small_run_loo(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), L.LOO_MODES[loo], L.ptr(out), L.ptr(mean), L.ptr(var), ms,
-                                                 L.ptr(lmean), L.ptr(lvar), nmax), "small_run_loo")
-            gp._fitted = False
-            return dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
-                        mean=mean[:, :self._mmax], var=var[:, :self._mmax], loo_mean=lmean, loo_var=lvar,
-                        loo_nlpd=out[:, 4].copy(), loo_sse=out[:, 5].copy())
-        fn = gp._lib.sigp_small_run_grad if grad else gp._lib.sigp_small_run
-        gp._check(fn(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), L.ptr(out), L.ptr(mean), L.ptr(var), ms), "small_run")
+            rmean = np.full((F, nmax), np.nan); rvar = np.full((F, nmax), np.nan)
+            args += (L.ptr(rmean), L.ptr(rvar), nmax)
+        gp = self.gp
+        gp._check(getattr(gp._lib, fn)(gp._h, F, L.iptr(si), L.ptr(ell), L.ptr(sn), *args), what)
         gp._fitted = False
         res = dict(sigma_f=out[:, 0], nlml=out[:, 1], info=out[:, 2].astype(np.int64), sigma_n=out[:, 3],
                    mean=mean[:, :self._mmax], var=var[:, :self._mmax])
+        if prefix:
+            res.update({prefix + "_mean": rmean, prefix + "_var": rvar, prefix + "_nlpd": out[:, 4].copy(), prefix + "_sse": out[:, 5].copy()})
         if grad:
             res["grad_ref"], res["grad_exact"] = out[:, 4:6].copy(), out[:, 6:8].copy()
         return res
+
+    # flavour -> (prefix of its result keys, entry point (its arguments beyond the common ones go ahead of ``out``), the name errors carry,
+    # doubles per fit of ``out``)
+    _FLAVOURS = {"plain": (None, "sigp_small_run", "small_run", 4),
+                 "grad": (None, "sigp_small_run_grad", "small_run", 8),
+                 "loo": ("loo", "sigp_small_run_loo", "small_run_loo", 6),
+                 "cv": ("cv", "sigp_small_run_cv", "small_run_cv", 6),
+                 "hindcast": ("hindcast", "sigp_small_run_hindcast", "small_run_hindcast", 6)}

@@ -33,7 +33,7 @@ HC_SETTINGS = ((1, 1), (1, 2), (2, 3), (32, 1))
 MODES = ("refit", "fixed")
 LDS_MAX = 160 * 1024 - 64                       # bytes of LDS one workgroup may ask for
 CV_W = 32                                       # SM_CVW
-CV_EXTRA = (2 * CV_W * (CV_W + 1) + CV_W) * 8   # SM_CV_EXTRA_BYTES
+CV_EXTRA = (2 * CV_W * (CV_W + 1) + CV_W) * 8   # Pw, Ww and tv of SmallLayout: what the leave-block-out image adds
 
 
 # ---- the arithmetic ---------------------------------------------------------------------------------------------------------------------
@@ -49,7 +49,7 @@ F64 = Arith("fp64 LAPACK", np.float64, np.linalg.cholesky, lambda L, B: solve_tr
             lambda L, B: solve_triangular(L.T, B, lower=False), _f64_inv, np.linalg.inv)
 
 
-# ---- LDS of a launch (csrc/smallgp.hpp: smallgp_lds_bytes, SM_CV_EXTRA_BYTES) ----------------------------------------------------------------
+# ---- LDS of a launch (csrc/smallgp_layout.hpp: SmallLayout::bytes, small_pick_chunk; test_small_cases_host.py holds them to it) ---------------
 def lds_bytes(n, m, ch):
     return ((n + 1 + m) * (n | 1) + (n + m) * (ch + 1) + ch + 4 * 8 + 16 + n) * 8
 
@@ -64,7 +64,7 @@ def upload_chunk(nmax, mmax):
 
 def cv_chunk(nmax, mmax, before_fix=False):
     """the feature chunk of the leave-block-out launch (None: refused): the largest of {upload's, 16, 8} not above the upload's that leaves
-    SM_CV_EXTRA_BYTES; ``before_fix``: the upload's chunk or nothing, as the parent did"""
+    CV_EXTRA; ``before_fix``: the upload's chunk or nothing, as the parent did"""
     up = upload_chunk(nmax, mmax)
     if up is None:
         return None

@@ -1,9 +1,9 @@
 """CPU tier of the one-workgroup kernel's case table (tests/small_cases.py): the long-double closed forms that the GPU tier
 (tests/test_hip_small_flavours.py) measures the device against are pinned to REAL long-double refits, the table meets its condition cap
 through the real ``SmallBatch`` staging, every layout listed for a batch is admissible for every set of it, the fp64 comparator's own
-error is a usable unit, and the LDS anchors of the leave-block-out launch follow from ``smallgp_lds_bytes``."""
+error is a usable unit, and the LDS anchors of the leave-block-out launch follow from ``SmallLayout`` (csrc/smallgp_layout.hpp)."""
 import os
-import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -168,14 +168,66 @@ def test_every_layout_of_a_batch_is_admissible_for_every_set_of_it():
         assert any(c.N > (b.cv_chunk or b.chunk) for c in b.cases) and any(c.expm == "pade" for c in b.cases), b.name
 
 
-def test_lds_anchors_of_the_leave_block_out_launch():
-    """from smallgp_lds_bytes + SM_CV_EXTRA_BYTES against 160 KiB - 64: the parent refused n >= 119 (m = 0), 118 (m = 1, 2), 114 (m = 8);
+LAYOUT_PROGRAM = r'''
+#include <cstdio>
+#include <initializer_list>
+#include "smallgp_layout.hpp"
+using namespace sigp;
+
+int main() {
+  const SmallFlavour fl[] = {SmallFlavour::Plain, SmallFlavour::Grad, SmallFlavour::Loo, SmallFlavour::Cv, SmallFlavour::Hindcast};
+  std::printf("K %d %d %d %d %ld\n", SM_NMAX, SM_MMAX, SM_CVW, SM_CVP, SM_LDS_MAX);
+  for (int f = 0; f < 5; ++f) std::printf("F %d %d %d\n", f, small_out_width(fl[f]), (int)small_has_rows(fl[f]));
+  for (int n = 1; n <= SM_NMAX; ++n)
+    for (int m = 0; m <= SM_MMAX; ++m) {
+      for (int ch : {8, 16, 32})
+        for (int f = 0; f < 5; ++f) {
+          const SmallLayout l{n, m, ch, fl[f]};
+          std::printf("L %d %d %d %d %ld %d %d %ld %ld %ld %ld %ld %ld %ld %ld %ld\n", n, m, ch, f, l.bytes(), l.ldk(), l.lda(), l.Kp(), l.Ac(), l.wk(), l.kss(), l.red(), l.at(),
+                      l.Pw(), l.Ww(), l.tv());
+        }
+      const int up = small_pick_chunk(n, m, SmallFlavour::Plain, 32);
+      std::printf("C %d %d %d %d\n", n, m, up, up ? small_pick_chunk(n, m, SmallFlavour::Cv, up) : 0);
+    }
+  return 0;
+}
+'''
+
+
+def test_lds_anchors_of_the_leave_block_out_launch(tmp_path):
+    """from SmallLayout::bytes() against 160 KiB - 64: the parent refused n >= 119 (m = 0), 118 (m = 1, 2), 114 (m = 8);
     with the launch's own chunk the limits are 128 (m <= 2), 127 (m = 3 .. 5), 126 (m = 6), 125 (m = 7, 8)"""
-    # ``small_cases.lds_bytes`` restates two expressions of smallgp.hpp; knowingly textual (white space aside): whoever edits them there
-    # is sent here.  The behaviour itself -- accepted, refused, the handle usable afterwards -- is tested through the library on the GPU.
-    src = re.sub(r"\s+", "", open(os.path.join(ROOT, "seaiceextentforecasting_amd", "csrc", "smallgp.hpp")).read())
-    assert "((long)(n+1+m)*ldk+(long)(n+m)*(ch+1)+ch+4*SM_MMAX+16+n)*(long)sizeof(double)" in src and "constlongldk=n|1;" in src
-    assert "SM_CV_EXTRA_BYTES=(2L*SM_CVW*SM_CVP+SM_CVW)*(long)sizeof(double)" in src and "SM_CVW=32;" in src and "SM_MMAX=8;" in src
+    # ``small_cases.lds_bytes`` / ``upload_chunk`` / ``cv_chunk`` restate csrc/smallgp_layout.hpp, which a stand-alone host program sweeps:
+    # n = 1 .. 128, m = 0 .. 8, ch in {8, 16, 32}, all five flavours.  The behaviour itself -- accepted, refused, the handle usable
+    # afterwards -- is tested through the library on the GPU.
+    src = tmp_path / "small_layout.cpp"
+    src.write_text(LAYOUT_PROGRAM)
+    exe = tmp_path / "small_layout"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "seaiceextentforecasting_amd", "csrc"), "-o", str(exe), str(src)])
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    rows = {k: [] for k in "KFLC"}
+    for line in p.stdout.split("\n"):
+        if line:
+            rows[line[0]].append([int(x) for x in line.split()[1:]])
+    assert rows["K"] == [[128, 8, SC.CV_W, SC.CV_W + 1, SC.LDS_MAX]]
+    assert rows["F"] == [[0, 4, 0], [1, 8, 0], [2, 6, 1], [3, 6, 1], [4, 6, 1]]       # plain, gradient, leave-one-out, leave-block-out, hindcast
+    assert len(rows["L"]) == 128 * 9 * 3 * 5 and len(rows["C"]) == 128 * 9
+    CV = 3
+    for n, m, ch, f, size, ldk, lda, Kp, Ac, wk, kss, red, at, Pw, Ww, tv in rows["L"]:
+        assert size == SC.lds_bytes(n, m, ch) + (SC.CV_EXTRA if f == CV else 0), (n, m, ch, f)
+        assert (ldk, lda) == (n | 1, ch + 1)
+        # the offsets the kernel had as literals: red = kss + SM_MMAX, at = red + 16, Pw = at + n + 24 (24 doubles of slack)
+        assert (Kp, Ac, wk, kss, red, at, Pw) == (0, (n + 1 + m) * ldk, (n + 1 + m) * ldk + (n + m) * lda, wk + ch, kss + 8, red + 16, at + n + 24), (n, m, ch, f)
+        assert (Ww, tv) == (Pw + 32 * 33, Pw + 2 * 32 * 33) and Pw * 8 == SC.lds_bytes(n, m, ch)
+        pieces = [(Kp, (n + 1 + m) * ldk), (Ac, (n + m) * lda), (wk, ch), (kss, 8), (red, 16), (at, n)]
+        if f == CV:
+            pieces += [(Pw, 32 * 33), (Ww, 32 * 33), (tv, 32)]
+        pieces.sort()
+        assert pieces[0][0] >= 0 and 8 * (pieces[-1][0] + pieces[-1][1]) <= size, (n, m, ch, f)                 # inside bytes() ...
+        assert all(a[0] + a[1] <= b[0] for a, b in zip(pieces, pieces[1:])), (n, m, ch, f)                        # ... and disjoint
+    for n, m, up, cvc in rows["C"]:
+        assert (up or None, cvc or None) == (SC.upload_chunk(n, m), SC.cv_chunk(n, m)), (n, m)
     assert [SC.cv_order_limit(m, before_fix=True) for m in (0, 1, 2, 8)] == [118, 117, 117, 113]
     assert [SC.cv_order_limit(m) for m in range(9)] == [128, 128, 128, 127, 127, 127, 126, 125, 125]
     for n, m in ((128, 0), (128, 2), (127, 3), (125, 8)):
