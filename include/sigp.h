@@ -521,7 +521,8 @@ int sigp_cv_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int ker
  * sigp_predict / sigp_get_alpha / sigp_loo / sigp_cv afterwards return the bits they returned before.  SIGP_BAD_ARG: an fp32 handle, a
  * sharded fit, not fitted, lead < 1, lead > SIGP_HINDCAST_MAX_LEAD, min_train < 1, no scored row (min_train + lead - 1 > n - 1), a bad
  * sigma_mode.  Device work is accounted under SIGP_KC_MLII (the scan and the row pass: one entry each).
- * Out of scope: gradients for lockstep groups, gradients in sigp_small_*, the reference kernel's gradient, the fp32 engine, sharded fits. */
+ * Gradients for lockstep groups: sigp_hindcast_grad_ard_batch (below).  Out of scope: gradients in sigp_small_*, the reference kernel's
+ * gradient, the fp32 engine, sharded fits. */
 enum { SIGP_HINDCAST_MAX_LEAD = 128, SIGP_HINDCAST_SMALL_MAX_LEAD = 32 };
 int sigp_hindcast(sigp_handle* h, int64_t lead, int64_t min_train, int sigma_mode, double* mean, double* var, double* score);
 /* ... for lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2; the retro loop's refits per grid point,
@@ -558,6 +559,32 @@ int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_in
  * +inf, mean / var NaN.  Afterwards the handle is fitted at exp(theta) with the scales set, as after sigp_loo_grad_ard. */
 int sigp_hindcast_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int64_t lead, int64_t min_train, int sigma_mode,
                            int criterion, double* mean, double* var, double* score, double* grad);
+/* ... for lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2, fp64): what sigp_hindcast_batch does, with
+ * scales per FIT and every other convention as in sigp_cv_grad_ard_batch, lead / min_train in place of block / gap -- fit i uses data set
+ * (first + i) % batch and theta_i = theta[i ldtheta .. + ntheta) = (log l_1 .. log l_d, log sn~), ntheta = d + 1; two members of one group
+ * may share a data set and differ in scales.  score [count][2] = nlpd, sse; mean / var [count][nstride >= n] (both or neither; NaN where a
+ * row is not scored); grad [count][ldgrad >= d + 1], the derivatives of the score `criterion` names, or NULL: scores and predictions only,
+ * no L~^-T and no cubic work.  Groups of `group` members (sigp_set_option) run one after another.  Per group: sigp_batch_run_ard's staging
+ * launch, the isotropic entries' fit at ell = 1 on the staged features and sigp_hindcast_batch's launches on it -- the scores and
+ * predictions carry the bits sigp_hindcast_batch returns on data sets X / l uploaded as they are, at ell = 1 --, then for every member at
+ * once sigp_hindcast_grad_ard's steps with the member on a grid axis: the coefficients, zbar, the banded part of C, U = L~^-T, W = U C,
+ * ONE cubic product G = U W^T per member and sigp_loo_grad_ard's tile pass and fixed-order sums.  W = U C runs on a kernel of its own here
+ * (hindcast_w_lds_kernel): it keeps the row piece of U and the row of W in LDS (16.5 n_pad bytes) and touches global memory only in runs
+ * of 256 consecutive doubles, where the single fit's kernel reads and writes at a stride of up to 32 doubles; both form every entry by the
+ * same chain of operations, so W has the same bits.  It serves n_pad <= 8192 (132 KB of the 160 KB of LDS a workgroup may have); larger
+ * groups take the single fit's kernel.  No atomics:
+ * the same bits on every run, whatever the group size, and a member executes a single fit's floating-point operations and carries the bits
+ * sigp_hindcast_grad_ard returns for it wherever the lockstep factorisation has the single fit's bits.  One copy brings a group's gradients
+ * back.  A member whose exp(theta) overflows, one of whose scales underflows to 0 or whose K~ is not SPD gets +inf in both scores and all
+ * d + 1 gradient entries and NaN rows in mean / var; its group mates are unaffected and the call returns SIGP_OK.
+ * Memory beside the slot: the staging area and the vectors; a gradient adds three matrices of 8 group n_pad^2 bytes (L~^-T, W, Cb / G).
+ * SIGP_BAD_ARG: everything sigp_loo_grad_ard_batch refuses, and sigp_hindcast's checks on the batch's n (lead <= SIGP_HINDCAST_MAX_LEAD).
+ * Device work is accounted under SIGP_KC_MLII (sigp_hindcast_grad_ard's entries, their figures times the members), the staging under
+ * SIGP_KC_KBUILD.  The handle is left unfitted, as after the other batch entries.
+ * Not covered: sigp_small_*, the reference kernel's gradient, the fp32 engine, sharded fits. */
+int sigp_hindcast_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta, int64_t ldtheta,
+                                 int64_t lead, int64_t min_train, int sigma_mode, int criterion, double* mean, double* var, int64_t nstride,
+                                 double* score, double* grad, int64_t ldgrad);
 
 /* One large fit sharded over the GPUs of a node (BASELINE configs[3] fp64, configs[4] fp32 + fp64 refinement): 1-D block-cyclic
  * ownership of outer panels (W column blocks of 128; panel q belongs to rank q % nranks), OWNER-ONLY storage -- a rank allocates,

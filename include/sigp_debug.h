@@ -93,6 +93,14 @@ int sigp_debug_f32_get_inverse(sigp_handle* h, int which, float* out);
  * diagonal tiles whole: their two halves agree to rounding, not bit for bit), zeros in the tiles above.  criterion SIGP_LOO_NLPD /
  * SIGP_LOO_SSE; lead, min_train, sigma_mode as sigp_hindcast. */
 int sigp_debug_run_hindcast_adjoint(sigp_handle* h, int64_t lead, int64_t min_train, int sigma_mode, int criterion, double* out, int64_t ldo);
+/* ONE launch of W = U C (hindcast.hpp) on host operands, every buffer back whole: which = 0 hindcast_w_kernel, 1 hindcast_w_lds_kernel
+ * (n_pad <= 8192).  U, Cb, W hold c_elems doubles each: member m's n_pad x n_pad matrix at m sC, rows ld >= n_pad apart (of U only the
+ * entries i <= j < n are read, of Cb rows and columns below n; W comes in with the caller's sentinels and goes back whole: rows and columns
+ * 0 .. n_pad of every member are written).  z, zbar hold z_elems doubles each, member m's [n] at m sZ.  1 <= n <= n_pad, n_pad a multiple
+ * of 128, 1 <= lead <= 128, 1 <= members <= 8.  SIGP_BAD_ARG, nothing launched: a descriptor that leaves the buffers, members whose
+ * matrices overlap, which = 1 beyond the LDS limit. */
+int sigp_debug_run_hindcast_w(sigp_handle* h, int which, const double* U, const double* Cb, const double* z, const double* zbar, double* W, int n, int n_pad,
+                              int64_t ld, int lead, int members, int64_t sC, int64_t sZ, int64_t c_elems, int64_t z_elems);
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,7 @@ CV_MAX_WINDOW, CV_SMALL_MAX_WINDOW = 128, 32   # SIGP_CV_MAX_WINDOW / SIGP_CV_SM
 LOO_CRITERIA = {"loo_nlpd": "nlpd", "loo_sse": "sse"}   # optimiser criteria -> keys of GPR.loo's result
 LOO_CRITERION_IDS = {"loo_nlpd": 0, "loo_sse": 1}       # SIGP_LOO_NLPD / SIGP_LOO_SSE (sigp_loo_grad_ard)
 CV_CRITERION_IDS = {"cv_nlpd": 0, "cv_sse": 1}          # the same ids for the leave-block-out scores (sigp_cv_grad_ard)
-HINDCAST_CRITERION_IDS = {"hindcast_nlpd": 0, "hindcast_sse": 1}   # ... and for the expanding-window hindcast scores (sigp_hindcast_grad_ard)
+HINDCAST_CRITERION_IDS = {"hindcast_nlpd": 0, "hindcast_sse": 1}   # ... and for the expanding-window hindcast scores (sigp_hindcast_grad_ard, sigp_hindcast_grad_ard_batch)
 HINDCAST_MAX_LEAD, HINDCAST_SMALL_MAX_LEAD = 128, 32   # SIGP_HINDCAST_MAX_LEAD / SIGP_HINDCAST_SMALL_MAX_LEAD: rows withheld before a target, plus one
 
 _dp = C.POINTER(C.c_double)
@@ -84,6 +84,7 @@ SIGNATURES = {
     "sigp_hindcast_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64, _dp]),
     "sigp_small_run_hindcast": (C.c_int, [_h, _i64, _ip64, _dp, _dp, _i64, _i64, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_hindcast_grad_ard": (C.c_int, [_h, C.c_int, _dp, _i64, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "sigp_hindcast_grad_ard_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_dist_unique_id": (C.c_int, [C.c_void_p]),
     "sigp_dist_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),
     "sigp_dist_init_transport": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p]),

@@ -1,5 +1,6 @@
-// Expanding-window (rolling-origin) hindcast validation from ONE fit (sigp_hindcast, sigp_hindcast_batch, sigp_hindcast_grad_ard; drivers:
-// sigp_hindcast.inc).  Rows are in time order, 0-based.  Row t is scored when s = t - lead + 1 >= min_train; its training set is rows [0, s).
+// Expanding-window (rolling-origin) hindcast validation from ONE fit (sigp_hindcast, sigp_hindcast_batch, sigp_hindcast_grad_ard and, for
+// lockstep groups, sigp_hindcast_grad_ard_batch; drivers: sigp_hindcast.inc, sigp_hindcastbatch.inc).  Rows are in time order, 0-based.
+// Row t is scored when s = t - lead + 1 >= min_train; its training set is rows [0, s).
 // The Cholesky factor of the first s rows is the leading s x s block of L = L~, and z = L^-1 y restricted to its first s entries is that
 // prefix's solved vector, so with the hyper-parameters held every origin's forecast is read out of the factor and the solved ride row:
 //     r_t = y_t - mean_t = sum_{j=s..t} L_tj z_j        w_t = sum_{j=s..t} L_tj^2        var_t = sigma_t w_t  (with the noise, like fvar)
@@ -13,8 +14,8 @@
 //     d score / d log l_k = sum_ij G_ij h_ij (u_ik - u_jk)^2  (ard_grad_partial_kernel<., ARD_W_LOO> with M = G, v = 0, eps = 0),  d / d log sn~ = sn~ tr G
 // The lower triangle of L^T B is banded: (L^T B)_ij = sum_{k=i..j+lead-1} L_ki B_kj for 0 <= i - j < lead, and B is never stored: an entry of
 // C forms the terms of B it needs from rho, kappa sigma, z and L.  W = U C needs no cubic product: the banded part of C is a banded product
-// and its rank-one part two scans along each row of U (hindcast_w_kernel).  The one cubic step beyond U is G = U W^T on syrk128_kernel's
-// SET form (sigp_hindcast.inc).  Rows and columns n .. n_pad of Cb and W are zero.  No atomics anywhere: the same bits on every run.
+// and its rank-one part two scans along each row of U (hindcast_w_kernel; lockstep groups: hindcast_w_lds_kernel).  The one cubic step
+// beyond U is G = U W^T on syrk128_kernel's SET form (sigp_hindcast.inc).  Rows and columns n .. n_pad of Cb and W are zero.  No atomics anywhere: the same bits on every run.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -184,6 +185,36 @@ __global__ __launch_bounds__(256) void hindcast_band_kernel(const double* __rest
 // The two sums of the rank-one part are one prefix scan and one suffix scan along the row (hc_block_scan: a fixed order); the banded part is
 // at most 2 lead - 1 terms per entry, Cb read along its rows (Cb is symmetric): coalesced across the threads.  Rows and columns n .. n_pad
 // of W are zero.  blockIdx.y = lockstep member.
+//
+// The row of W both kernels below form, written once so that every entry is one chain of floating-point operations whichever kernel forms
+// it: urow[j] and wrow[j] (j = i .. n - 1: the row piece of U and the rank-one part on its way) live where the caller says -- global memory
+// (hindcast_w_kernel: wrow is the row of W itself) or LDS (hindcast_w_lds_kernel) -- and `out` is the row of W.
+template <typename UR, typename WR>
+__device__ __forceinline__ void hc_w_row(int i, int n, int n_pad, int lead, UR urow, WR wrow, const double* __restrict__ z, const double* __restrict__ zbar,
+                                         const double* __restrict__ Cb, long ld, double* out, double* tot /* [256] LDS */, double* whole /* LDS */) {
+  const int len = n - i;
+  // prefix: wrow[j] = -zbar_j / 2 sum_{i <= j' < j} U_ij' z_j'
+  hc_block_scan(len, tot, [&](int p) { return urow[i + p] * z[i + p]; }, [&](int p, double before, double) { wrow[i + p] = -0.5 * zbar[i + p] * before; });
+  __syncthreads();
+  // suffix, from the last column down: wrow[j] -= z_j / 2 sum_{j' >= j} U_ij' zbar_j'; the whole sum serves the columns left of the diagonal
+  hc_block_scan(len, tot, [&](int p) { return urow[n - 1 - p] * zbar[n - 1 - p]; },
+                [&](int p, double before, double v) {
+                  const int j = n - 1 - p;
+                  const double sfx = before + v;
+                  wrow[j] = fma(-0.5 * z[j], sfx, wrow[j]);
+                  if (j == i) *whole = sfx;
+                });
+  __syncthreads();
+  const double wh = *whole;
+  for (int k = threadIdx.x; k < n_pad; k += 256) {
+    if (k >= n) { out[k] = 0.0; continue; }
+    double a = k < i ? -0.5 * z[k] * wh : wrow[k];
+    const int j0 = max(i, k - lead + 1), j1 = min(n - 1, k + lead - 1);
+    for (int j = j0; j <= j1; ++j) a = fma(urow[j], Cb[(long)j * ld + k], a);
+    out[k] = a;
+  }
+}
+
 __global__ __launch_bounds__(256) void hindcast_w_kernel(const double* __restrict__ U, const double* __restrict__ Cb, long ld, int n, int n_pad,
                                                          const double* __restrict__ z, int lead, HindcastVecs hv, double* __restrict__ W, HindcastStrides ms) {
   __shared__ double tot[256];
@@ -198,29 +229,43 @@ __global__ __launch_bounds__(256) void hindcast_w_kernel(const double* __restric
     for (int k = threadIdx.x; k < n_pad; k += 256) wrow[k] = 0.0;
     return;
   }
-  const double* urow = U + (long)i * ld;
-  const double* zbar = hv.zbar();
-  const int len = n - i;
-  // prefix: wrow[j] = -zbar_j / 2 sum_{i <= j' < j} U_ij' z_j'
-  hc_block_scan(len, tot, [&](int p) { return urow[i + p] * z[i + p]; }, [&](int p, double before, double) { wrow[i + p] = -0.5 * zbar[i + p] * before; });
-  __syncthreads();
-  // suffix, from the last column down: wrow[j] -= z_j / 2 sum_{j' >= j} U_ij' zbar_j'; the whole sum serves the columns left of the diagonal
-  hc_block_scan(len, tot, [&](int p) { return urow[n - 1 - p] * zbar[n - 1 - p]; },
-                [&](int p, double before, double v) {
-                  const int j = n - 1 - p;
-                  const double sfx = before + v;
-                  wrow[j] = fma(-0.5 * z[j], sfx, wrow[j]);
-                  if (j == i) whole = sfx;
-                });
-  __syncthreads();
-  const double wh = whole;
-  for (int k = threadIdx.x; k < n_pad; k += 256) {
-    if (k >= n) { wrow[k] = 0.0; continue; }
-    double a = k < i ? -0.5 * z[k] * wh : wrow[k];
-    const int j0 = max(i, k - lead + 1), j1 = min(n - 1, k + lead - 1);
-    for (int j = j0; j <= j1; ++j) a = fma(urow[j], Cb[(long)j * ld + k], a);
-    wrow[k] = a;
+  hc_w_row(i, n, n_pad, lead, U + (long)i * ld, wrow, z, hv.zbar(), Cb, ld, wrow, tot, &whole);
+}
+
+// The same row with the row piece U[i, i..n) and the rank-one part kept in dynamic LDS (hindcast_w_lds_bytes(n_pad), score_layout.hpp), for
+// lockstep groups: hindcast_w_kernel's chunked scans make the lanes of a wave read the row of U -- and read and write the row of W -- at a
+// stride of the chunk length c = ceil(len / 256), one cache line per lane from c = 16 on.  Here global memory is touched three times, each
+// 256 consecutive doubles wide: the row piece of U comes in once, Cb is read along its rows, the row of W goes out once.  hc_w_row forms
+// every entry, so a row carries hindcast_w_kernel's bits.  Column j of the row sits at LDS index q + (q >> 5), q = j - i: the scans' lanes
+// are c doubles apart, which at c = 8, 16, 32 (n = 2048 .. 8192) would put 8, 16, 32 lanes of a 32-lane ds_read_b64 group on one pair of
+// banks; with the skew of one double per 32 the group's 32 addresses fall on 32 bank pairs at all three.  z and zbar stay in global
+// memory: 16 n bytes shared by every row, they live in the caches.
+// grid (n_pad, members), n_pad <= HINDCAST_W_LDS_MAX_NPAD.
+struct HcLdsRow {
+  double* p; int i;
+  __device__ __forceinline__ double& operator[](int j) const { const int q = j - i; return p[q + (q >> 5)]; }
+};
+
+__global__ __launch_bounds__(256) void hindcast_w_lds_kernel(const double* __restrict__ U, const double* __restrict__ Cb, long ld, int n, int n_pad,
+                                                             const double* __restrict__ z, int lead, HindcastVecs hv, double* __restrict__ W, HindcastStrides ms) {
+  extern __shared__ double hc_w_lds[];   // the row piece of U, then the rank-one part: hindcast_w_lds_row(n_pad) doubles each
+  __shared__ double tot[256];
+  __shared__ double whole;
+  {
+    const long mb = blockIdx.y;
+    U += mb * ms.C; Cb += mb * ms.C; W += mb * ms.C; z += mb * ms.L; hv.base += mb * ms.v;
   }
+  const int i = blockIdx.x;
+  double* out = W + (long)i * ld;
+  if (i >= n) {
+    for (int k = threadIdx.x; k < n_pad; k += 256) out[k] = 0.0;
+    return;
+  }
+  const HcLdsRow urow{hc_w_lds, i}, wrow{hc_w_lds + hindcast_w_lds_row(n_pad), i};
+  const double* ug = U + (long)i * ld;
+  for (int j = i + (int)threadIdx.x; j < n; j += 256) urow[j] = ug[j];
+  __syncthreads();
+  hc_w_row(i, n, n_pad, lead, urow, wrow, z, hv.zbar(), Cb, ld, out, tot, &whole);
 }
 
 }  // namespace sigp

@@ -10,16 +10,19 @@
 //                       MliiParts            sigp_nlml_grad
 //                       MliiGroupParts       sigp_nlml_grad_batch
 //                       ArdParts             sigp_nlml_grad_ard, sigp_nlml_grad_ard_batch
-//                       LooArdGroupParts     sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch: ScoreParts of G members, then ArdParts of G members
+//                       LooArdGroupParts     sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch, sigp_hindcast_grad_ard_batch: ScoreParts of G members, then
+//                                            ArdParts of G members
 //   gV                  LooGradVecs          sigp_loo_grad(_batch)
 //                       LooArdVecs           sigp_loo_grad_ard, sigp_cv_grad_ard
 //                       LooArdGroupVecs      sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch: G LooArdVecs at an even member stride
 //                       HindcastVecs         sigp_hindcast, sigp_hindcast_batch (G of them, size() apart)
 //                       HindcastArdVecs      sigp_hindcast_grad_ard: HindcastVecs, then LooArdVecs
+//                       HindcastArdGroupVecs sigp_hindcast_grad_ard_batch: G HindcastArdVecs at an even member stride
 //   cvPart cvBlk cvVec  CvWork               cv_launch
 //   cvAdj               CvAdjStore           sigp_cv_grad_ard; it fills the CvAdjoint that cv_launch and the kernels take
 //                       CvAdjGroupStore      sigp_cv_grad_ard_batch: the same pieces for the nb members of a lockstep group
-//   bStage              ArdStage             sigp_batch_run_ard, sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch
+//   bStage              ArdStage             sigp_batch_run_ard, sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch, sigp_cv_grad_ard_batch,
+//                                            sigp_hindcast_grad_ard_batch
 // gU, gK, gD [G][n_pad][n_pad], scratchZ and ardXc are used whole: they have no layout beyond their size.
 // Everything is in doubles.  n_pad is a multiple of 128, dp of 64, wp of 16.
 #pragma once
@@ -158,6 +161,24 @@ struct HindcastArdVecs {
   __host__ __device__ HindcastVecs hc() const { return HindcastVecs{base, n_pad}; }
   __host__ __device__ LooArdVecs ard() const { return LooArdVecs{base + HindcastVecs::size(n_pad), n_pad}; }
 };
+
+// sigp_hindcast_grad_ard_batch: G members of HindcastArdVecs -- HindcastVecs, then the LooArdVecs the ARD pass takes -- mstride() = 11 n_pad + 2
+// apart: HindcastArdVecs::size is odd and the LooArdVecs are read in 16-byte pairs, so one double is spare behind every member's eps, as in
+// LooArdGroupVecs.  hc(0) and ard(0) are member 0's views; the launches reach member b at b mstride() behind them.
+struct HindcastArdGroupVecs {
+  double* base; long n_pad, G;
+  __host__ __device__ static long size(long G, long n_pad) { return G * (HindcastArdVecs::size(n_pad) + 1); }
+  __host__ __device__ long mstride() const { return HindcastArdVecs::size(n_pad) + 1; }
+  __host__ __device__ HindcastArdVecs member(long b) const { return HindcastArdVecs{base + b * mstride(), n_pad}; }
+};
+
+// The dynamic LDS of hindcast_w_lds_kernel (hindcast.hpp): the row piece of U and the rank-one part of the row of W, n_pad doubles each and
+// one double of skew per 32; the kernel's scan totals (2 KB, static) come on top.  A group takes that kernel while n_pad is at most
+// HINDCAST_W_LDS_MAX_NPAD -- 132 KB of the 160 KB a workgroup may have -- and hindcast_w_kernel beyond it.
+constexpr long HINDCAST_W_LDS_MAX_NPAD = 8192;
+__host__ __device__ constexpr long hindcast_w_lds_row(long n_pad) { return n_pad + n_pad / 32; }
+__host__ __device__ constexpr long hindcast_w_lds_bytes(long n_pad) { return 2 * hindcast_w_lds_row(n_pad) * 8; }
+__host__ __device__ constexpr bool hindcast_w_use_lds(long n_pad) { return n_pad <= HINDCAST_W_LDS_MAX_NPAD; }
 
 // ---- cvPart, cvBlk, cvVec ----------------------------------------------------------------------------------------------------------------------
 // The work buffers of one pass of cv_launch over `blocks` (member, fold) pairs with S K-slices and windows of at most wp rows:

@@ -264,6 +264,7 @@ struct sigp_handle {
   int opt_update_wgs = 0;    // > 0: trailing updates with more tiles than this run as a persistent grid of this many workgroups (slots left free
                              // for the panel stream's latency chain); 0: one workgroup per tile
   int opt_group = 8;         // fits factorised in lockstep per launch in the batch path
+  int opt_hindcast_w_lds = -1;   // debug library only: sigp_hindcast_grad_ard_batch forms W = U C by hindcast_w_kernel even where hindcast_w_lds_kernel's LDS fits (0; -1 = by n_pad, what the product library always does): same bits, A/B timing
   int opt_host_timing = 0;   // print host enqueue time per batch_run (debug)
   int opt_reserve_cus = 0;   // CUs masked out of the update streams (0: none -- the 84 KB diagonal kernel fits beside an update workgroup, and a CU-masked stream measured 6 % slower)
   // profiling
@@ -793,7 +794,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 610; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard
+int sigp_version(void) { return 620; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard; 6.2: sigp_hindcast_grad_ard_batch
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -937,6 +938,11 @@ int sigp_set_option(sigp_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "update_late")) { if (value < 0 || value > 4096) return SIGP_BAD_ARG; h->opt_update_late = (int)value; return SIGP_OK; }
   if (!strcmp(name, "update_wgs")) { if (value < 0 || value > 4096) return SIGP_BAD_ARG; h->opt_update_wgs = (int)value; return SIGP_OK; }
   if (!strcmp(name, "group")) { if (value < 1 || value > 256) return SIGP_BAD_ARG; h->opt_group = (int)value; return SIGP_OK; }
+  if (!strcmp(name, "hindcast_w_lds")) {
+    if (!DBG_MASK) return fail(h, SIGP_BAD_ARG, "hindcast_w_lds is a measurement switch of libsigp_debug.so");
+    if (value < -1 || value > 0) return SIGP_BAD_ARG;
+    h->opt_hindcast_w_lds = (int)value; return SIGP_OK;
+  }
   if (!strcmp(name, "host_timing")) { h->opt_host_timing = (int)value; return SIGP_OK; }
   if (!strcmp(name, "reserve_cus")) {
     if (value < 0 || value > 64) return SIGP_BAD_ARG;
@@ -1819,6 +1825,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_cvard.inc"     // sigp_cv_grad_ard: exact per-feature gradients of the leave-block-out scores
 #include "sigp_cvardbatch.inc"    // sigp_cv_grad_ard_batch: ... for lockstep groups; the driver it shares with sigp_loo_grad_ard_batch
 #include "sigp_hindcast.inc"   // sigp_hindcast, sigp_hindcast_batch, sigp_hindcast_grad_ard: expanding-window hindcast validation and its exact ARD gradient
+#include "sigp_hindcastbatch.inc"   // sigp_hindcast_grad_ard_batch: ... that gradient for lockstep groups
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"

@@ -24,6 +24,23 @@
 // Profile classes: the staging SIGP_KC_KBUILD, the rest SIGP_KC_MLII (sigp_loo_grad_ard's / sigp_cv_grad_ard's entries, their figures times nb).
 // Out of scope: sigp_small_*, the reference kernel, the fp32 engine, sharded fits.
 
+// A member's parameters from its theta = (log l_1 .. log l_d, log sn~): ell [d] and sn~.  false: an exp(theta) is not finite and positive; the
+// member then rides along at harmless parameters (ell = 1, sn~ = 1) and the driver drops its results.
+static bool ard_member_params(const double* th, long d, double* ell, double* snt) {
+  bool good = true;
+  for (long k = 0; k < d; ++k) {
+    ell[k] = std::exp(th[k]);
+    if (!std::isfinite(ell[k]) || !(ell[k] > 0)) good = false;
+  }
+  *snt = std::exp(th[d]);
+  if (!std::isfinite(*snt)) good = false;
+  if (!good) {
+    std::fill(ell, ell + d, 1.0);
+    *snt = 1.0;
+  }
+  return good;
+}
+
 static int ard_score_batch(sigp_handle* h, const char* what, const CvFolds* cv, int64_t first, int64_t count, int kernel_id, const double* theta, int64_t ntheta,
                            int64_t ldtheta, int sigma_mode, int criterion, double* mean, double* var, int64_t nstride, double* score, double* grad, int64_t ldgrad) {
   if (!h || !theta || !score) return fail(h, SIGP_BAD_ARG, "%s: bad argument (theta [count][ldtheta], score [count][2] required)", what);
@@ -80,22 +97,7 @@ static int ard_score_batch(sigp_handle* h, const char* what, const CvFolds* cv, 
   for (int b = 0; b < G; ++b) ds[(size_t)b] = b;             // member b is "data set b" of the staging area
   for (long g0 = 0; g0 < count; g0 += G) {
     const int nb = (int)std::min<long>(G, count - g0);
-    for (int b = 0; b < nb; ++b) {
-      const double* th = theta + (g0 + b) * ldtheta;
-      bool good = true;
-      for (long k = 0; k < d; ++k) {
-        const double l = std::exp(th[k]);
-        ell[(size_t)(b * d + k)] = l;
-        if (!std::isfinite(l) || !(l > 0)) good = false;
-      }
-      snt[(size_t)b] = std::exp(th[d]);
-      if (!std::isfinite(snt[(size_t)b])) good = false;
-      if (!good) {                                           // the member rides along at harmless parameters; its results are dropped
-        std::fill(ell.begin() + b * d, ell.begin() + (b + 1) * d, 1.0);
-        snt[(size_t)b] = 1.0;
-      }
-      ok[(size_t)b] = good;
-    }
+    for (int b = 0; b < nb; ++b) ok[(size_t)b] = ard_member_params(theta + (g0 + b) * ldtheta, d, &ell[(size_t)(b * d)], &snt[(size_t)b]);
     if ((rc = ard_stage_group(h, st, a, nb, ell.data(), d, snt.data(), first + g0, hdiv))) return rc;
     if ((rc = batch_group_fit_on(h, s, nb, kernel_id, one.data(), snt.data(), ds.data(), a.X, a.y, a.Xs, 0))) return rc;
     CvAdjoint adj{};
@@ -129,7 +131,7 @@ static int ard_score_batch(sigp_handle* h, const char* what, const CvFolds* cv, 
           if ((rc = syrk_set(h, st, nb, h->gD, h->gK, h->gU, n_pad, 1, 0))) return rc;
         }
       }
-      if ((rc = loo_ard_pass_members(h, st, nb, kernel_id, a.X, n_pad * dp, n, d, dp, n_pad, w, ls, ap.partial(), ap.grad(), 0.0, a.sn, gh.data()))) return rc;
+      if ((rc = loo_ard_pass_members(h, st, nb, kernel_id, a.X, n_pad * dp, n, d, dp, n_pad, w, ls, h->gU, ap.partial(), ap.grad(), 0.0, a.sn, gh.data()))) return rc;
     }
     if ((rc = batch_scores_fetch(h, st, nb, sp, mean ? mv.data() : nullptr, sc.data()))) return rc;
     if ((rc = sync_slot(h, s))) return rc;

@@ -642,10 +642,52 @@ int sigp_debug_run_hindcast_adjoint(sigp_handle* h, int64_t lead, int64_t min_tr
   const HindcastVecs hv{h->gV, n_pad};
   if ((rc = scores_stage_q(h, st, sp))) return rc;
   if ((rc = hindcast_launch(h, st, 1, n, n_pad, s.mat, 0, h->y, 0, nullptr, sp.q(), 0, lead, min_train, sigma_mode, sp, hv, 0, 1))) return rc;
-  if ((rc = hindcast_adjoint(h, st, lead, min_train, sigma_mode, criterion, sp.q(), hv))) return rc;
+  if ((rc = hindcast_adjoint(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, lead, min_train, sigma_mode, criterion, sp.q(), 0, hv, 0, false))) return rc;
   HIPCHK(h, hipMemcpy2DAsync(out, (size_t)ldo * sizeof(double), h->gD, (size_t)n_pad * sizeof(double), (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, st));
   if ((rc = sync_slot(h, s))) return rc;
   for (long i = 0; i < n; ++i)
     for (long j = (i / NB + 1) * NB; j < n; ++j) out[i * ldo + j] = 0.0;
+  return SIGP_OK;
+}
+
+// ONE launch of hindcast_w_kernel (which = 0) or hindcast_w_lds_kernel (1) on host operands (include/sigp_debug.h).  zbar travels inside a
+// HindcastVecs arena whose other six vectors are NaN: the kernels read zbar alone.
+int sigp_debug_run_hindcast_w(sigp_handle* h, int which, const double* U, const double* Cb, const double* z, const double* zbar, double* W, int n, int n_pad,
+                              int64_t ld, int lead, int members, int64_t sC, int64_t sZ, int64_t c_elems, int64_t z_elems) {
+  constexpr long LIM = 1L << 28;
+  if (!h || !U || !Cb || !z || !zbar || !W || which < 0 || which > 1) return SIGP_BAD_ARG;
+  if (n < 1 || n_pad < n || n_pad % 128 || n_pad > 16384 || ld < n_pad || ld > LIM || lead < 1 || lead > SIGP_HINDCAST_MAX_LEAD || members < 1 || members > 8)
+    return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_w: n / n_pad / ld / lead / members");
+  if (sC < 0 || sZ < 0 || sC > LIM || sZ > LIM || c_elems < 1 || c_elems > LIM || z_elems < 1 || z_elems > LIM) return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_w: strides");
+  const long mat_hi = (long)(n_pad - 1) * ld + n_pad - 1;
+  if ((long)(members - 1) * sC + mat_hi >= c_elems || (long)(members - 1) * sZ + n - 1 >= z_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_w: the descriptor reaches outside the operand buffers");
+  if (members > 1 && sC <= mat_hi) return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_w: members would write the same entries");
+  if (which == 1 && !hindcast_w_use_lds(n_pad)) return fail(h, SIGP_BAD_ARG, "debug_run_hindcast_w: n_pad = %d is beyond hindcast_w_lds_kernel's LDS limit", n_pad);
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cb = (size_t)c_elems * sizeof(double), zb = (size_t)z_elems * sizeof(double), head = (size_t)6 * n_pad * sizeof(double);
+  DebugDeviceBuf dU, dC, dW, dZ, dV;
+  HIPCHK(h, hipMalloc(&dU.p, cb)); HIPCHK(h, hipMemcpy(dU.p, U, cb, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dC.p, cb)); HIPCHK(h, hipMemcpy(dC.p, Cb, cb, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dW.p, cb)); HIPCHK(h, hipMemcpy(dW.p, W, cb, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dZ.p, zb)); HIPCHK(h, hipMemcpy(dZ.p, z, zb, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMalloc(&dV.p, head + zb));
+  HIPCHK(h, hipMemset(dV.p, 0xFF, head));                    // cum .. suf: NaN
+  HIPCHK(h, hipMemcpy((char*)dV.p + head, zbar, zb, hipMemcpyHostToDevice));
+  const HindcastVecs hv{(double*)dV.p, n_pad};               // hv.zbar() = the copy of zbar; member m's sZ behind it
+  const HindcastStrides ms{sZ, 0, sZ, sC};
+  hipStream_t st = h->slots[0].s_upd;
+  if (which == 1) {
+    static AttrOnce attr;
+    HIPCHK(h, attr.set(h->device, (const void*)hindcast_w_lds_kernel, (int)hindcast_w_lds_bytes(HINDCAST_W_LDS_MAX_NPAD)));
+    hipLaunchKernelGGL(hindcast_w_lds_kernel, dim3((unsigned)n_pad, (unsigned)members), dim3(256), (size_t)hindcast_w_lds_bytes(n_pad), st, (const double*)dU.p,
+                       (const double*)dC.p, (long)ld, n, n_pad, (const double*)dZ.p, lead, hv, (double*)dW.p, ms);
+  } else {
+    hipLaunchKernelGGL(hindcast_w_kernel, dim3((unsigned)n_pad, (unsigned)members), dim3(256), 0, st, (const double*)dU.p, (const double*)dC.p, (long)ld, n, n_pad,
+                       (const double*)dZ.p, lead, hv, (double*)dW.p, ms);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(W, dW.p, cb, hipMemcpyDeviceToHost));
   return SIGP_OK;
 }

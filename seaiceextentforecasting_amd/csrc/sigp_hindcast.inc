@@ -1,5 +1,5 @@
 // sigp_hindcast, sigp_hindcast_batch, sigp_hindcast_grad_ard: expanding-window hindcast validation from one fit, and the exact per-feature
-// gradient of its scores (hindcast.hpp has the formulae and the kernels).  Included inside extern "C" of sigp.hip, after sigp_scores.inc
+// gradient of its scores (hindcast.hpp has the formulae and the kernels; sigp_hindcastbatch.inc the gradient for lockstep groups).  Included inside extern "C" of sigp.hip, after sigp_scores.inc
 // and sigp_looard.inc.
 //
 // The values read the factor, the solved ride row z and q = z.z alone: a scan of z^2, the row pass, loo_sum_kernel.  No L~^-T.
@@ -14,7 +14,8 @@
 //                             (U is upper triangular; G is symmetric, so U W^T stands for W U^T): n^3/3 -- the one cubic step beyond U
 //   the ARD pass              the tile pass with ARD_W_LOO over M = G with a = v = 0, eps = 0, then loo_ard_finish_kernel
 // Memory: sigp_loo_grad's single-fit buffers (gU, gK, gD, gV, gPart) plus ardXc.  Profile class: SIGP_KC_MLII, one entry per step.
-// Out of scope: gradients for lockstep groups, sigp_small_*, the reference kernel's gradient, the fp32 engine, sharded fits.
+// Lockstep groups: sigp_hindcast_grad_ard_batch (sigp_hindcastbatch.inc), which runs these launches with a member axis and W = U C on
+// hindcast_w_lds_kernel.  Out of scope: sigp_small_*, the reference kernel's gradient, the fp32 engine, sharded fits.
 
 // the value pass for nb lockstep members: cum, the rows, the sums.  rw = 1: r and w stay in hv for the gradient.
 static int hindcast_launch(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* y, long sY, const KParams* kps,
@@ -102,44 +103,54 @@ int sigp_hindcast_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
   return SIGP_OK;
 }
 
-// The adjoint of the score `criterion` on the single fit, after hindcast_launch with rw = 1 on the same stream: G = d score / d K~, lower
-// 128-tiles (whole diagonal tiles), into gD.  gU holds U = L~^-T afterwards, gK W = U C.
+// The adjoint of the score `criterion` for nb lockstep members, after hindcast_launch with rw = 1 on the same stream: G = d score / d K~,
+// lower 128-tiles (whole diagonal tiles), into gD.  gU holds U = L~^-T afterwards, gK W = U C, all three n_pad^2 apart.  Member b's factor
+// (and its ride row z) at Lm + b sL, its inverse diagonal blocks at dinvp + b sD, q at q + b sQ, its vectors at b sV behind hv; the single
+// fit is one member with zero strides.  w_lds: W = U C by hindcast_w_lds_kernel (lockstep groups with n_pad <= HINDCAST_W_LDS_MAX_NPAD;
+// the same bits, hindcast.hpp) instead of hindcast_w_kernel.
 // Precondition on inv_factor, shared with kinv_lower: the product G = U W^T starts K at the row block and reads the WHOLE diagonal 128-block
 // of U, so trtri_levels must leave zeros left of the diagonal inside the diagonal blocks (blocks below the block diagonal are never read).
 // Inside a diagonal tile G_ij = sum_k U_ik W_jk and G_ji = sum_k U_jk W_ik are different sums: the two halves agree to rounding, not bit for
 // bit.  The ARD pass reads the strictly lower half and the diagonal only.
-static int hindcast_adjoint(sigp_handle* h, hipStream_t st, long lead, long min_train, int mode, int criterion, const double* q, HindcastVecs hv) {
-  Slot& s = h->slots[0];
-  const long n = h->n, n_pad = h->n_pad, ld = n_pad;
-  const HindcastStrides ms{0, 0, 0, 0};
-  const double* z = s.mat + n_pad * ld;
+static int hindcast_adjoint(sigp_handle* h, hipStream_t st, int nb, long n, long n_pad, const double* Lm, long sL, const double* dinvp, long sD, long lead, long min_train,
+                            int mode, int criterion, const double* q, long sQ, HindcastVecs hv, long sV, bool w_lds) {
+  const long ld = n_pad;
+  const HindcastStrides ms{sL, sQ, sV, n_pad * n_pad};
+  const double* z = Lm + n_pad * ld;
   int rc;
-  {   // rho, kappa sigma and the suffix sums: one block, a fixed-order scan
-    ProfScope ps(h, st, SIGP_KC_MLII, 12.0 * n, 48.0 * n);
-    hipLaunchKernelGGL(hindcast_coef_kernel, dim3(1), dim3(256), 0, st, (int)n, q, (int)lead, (int)min_train, mode, criterion, hv, ms);
+  {   // rho, kappa sigma and the suffix sums: one block per member, a fixed-order scan
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * 12.0 * n, nb * 48.0 * n);
+    hipLaunchKernelGGL(hindcast_coef_kernel, dim3((unsigned)nb), dim3(256), 0, st, (int)n, q, (int)lead, (int)min_train, mode, criterion, hv, ms);
     HIPCHK(h, hipGetLastError());
   }
   {   // zbar
-    ProfScope ps(h, st, SIGP_KC_MLII, 2.0 * n * lead, 8.0 * n * lead);
-    hipLaunchKernelGGL(hindcast_zbar_kernel, dim3((unsigned)(n_pad / 256 + 1), 1), dim3(256), 0, st, (const double*)s.mat, ld, (int)n, (int)n_pad, z, (int)lead, mode, hv, ms);
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * 2.0 * n * lead, nb * 8.0 * n * lead);
+    hipLaunchKernelGGL(hindcast_zbar_kernel, dim3((unsigned)(n_pad / 256 + 1), (unsigned)nb), dim3(256), 0, st, Lm, ld, (int)n, (int)n_pad, z, (int)lead, mode, hv, ms);
     HIPCHK(h, hipGetLastError());
   }
   {   // the banded part of C
-    ProfScope ps(h, st, SIGP_KC_MLII, 4.0 * n * lead * lead, 8.0 * n_pad * n_pad + 16.0 * n * lead * lead);
-    hipLaunchKernelGGL(hindcast_band_kernel, dim3((unsigned)((n_pad + 255) / 256), (unsigned)n_pad, 1), dim3(256), 0, st, (const double*)s.mat, ld, (int)n, (int)n_pad, z, (int)lead,
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * 4.0 * n * lead * lead, nb * (8.0 * n_pad * n_pad + 16.0 * n * lead * lead));
+    hipLaunchKernelGGL(hindcast_band_kernel, dim3((unsigned)((n_pad + 255) / 256), (unsigned)n_pad, (unsigned)nb), dim3(256), 0, st, Lm, ld, (int)n, (int)n_pad, z, (int)lead,
                        hv, h->gD, ms);
     HIPCHK(h, hipGetLastError());
   }
-  if ((rc = inv_factor(h, st, 1, s.mat, 0, s.dinv, 0, n_pad))) return rc;
+  if ((rc = inv_factor(h, st, nb, Lm, sL, dinvp, sD, n_pad))) return rc;
   {   // W = U C: the two scans and the banded product
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n * n * (2.0 * lead + 3.0), 8.0 * n * n * (lead + 2.0));
-    hipLaunchKernelGGL(hindcast_w_kernel, dim3((unsigned)n_pad, 1), dim3(256), 0, st, (const double*)h->gU, (const double*)h->gD, ld, (int)n, (int)n_pad, z, (int)lead, hv,
-                       h->gK, ms);
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n * n * (2.0 * lead + 3.0)), nb * (8.0 * n * n * (lead + 2.0)));
+    if (w_lds) {
+      static AttrOnce attr;
+      HIPCHK(h, attr.set(h->device, (const void*)hindcast_w_lds_kernel, (int)hindcast_w_lds_bytes(HINDCAST_W_LDS_MAX_NPAD)));
+      hipLaunchKernelGGL(hindcast_w_lds_kernel, dim3((unsigned)n_pad, (unsigned)nb), dim3(256), (size_t)hindcast_w_lds_bytes(n_pad), st, (const double*)h->gU,
+                         (const double*)h->gD, ld, (int)n, (int)n_pad, z, (int)lead, hv, h->gK, ms);
+    } else {
+      hipLaunchKernelGGL(hindcast_w_kernel, dim3((unsigned)n_pad, (unsigned)nb), dim3(256), 0, st, (const double*)h->gU, (const double*)h->gD, ld, (int)n, (int)n_pad, z,
+                         (int)lead, hv, h->gK, ms);
+    }
     HIPCHK(h, hipGetLastError());
   }
   {   // G = U W^T
-    ProfScope ps(h, st, SIGP_KC_MLII, (double)n_pad * n_pad * n_pad / 3, 0.0);
-    if ((rc = syrk_set(h, st, 1, h->gU, h->gK, h->gD, n_pad, 1, 1))) return rc;
+    ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n_pad * n_pad * n_pad / 3), 0.0);
+    if ((rc = syrk_set(h, st, nb, h->gU, h->gK, h->gD, n_pad, 1, 1))) return rc;
   }
   return SIGP_OK;
 }
@@ -175,7 +186,7 @@ int sigp_hindcast_grad_ard(sigp_handle* h, int kernel_id, const double* theta, i
   if ((rc = scores_to_host(h, st, n, sp, mean, var, score))) return rc;
   if (!grad) return sync_slot(h, s);
 
-  if ((rc = hindcast_adjoint(h, st, lead, min_train, sigma_mode, criterion, sp.q(), hv))) return rc;
+  if ((rc = hindcast_adjoint(h, st, 1, n, n_pad, s.mat, 0, s.dinv, 0, lead, min_train, sigma_mode, criterion, sp.q(), 0, hv, 0, false))) return rc;
   const LooArdVecs w = av.ard();
   HIPCHK(h, hipMemsetAsync(w.base, 0, (size_t)LooArdVecs::size(n_pad) * sizeof(double), st));   // a = v = 0, eps = 0: the adjoint is G alone
   {

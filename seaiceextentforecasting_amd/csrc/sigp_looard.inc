@@ -17,19 +17,20 @@
 
 // The ARD pass of a leave-one-out / leave-block-out score (sigp_cv_grad_ard shares it) over M in gU with the vectors w: every tile's share of
 // all d components, then the fixed-order sums; the gradient [d + 1] on its way to the caller.  The partials and the gradient lie in ap.
-// The member form (sigp_loo_grad_ard_batch): nb lockstep members on scaled features U [nb][n_pad][dp] (member stride sU), member b's M in gU,
-// vectors, partials and gradient at b times the strides of ls behind w, partial and gdev (ls.grad = d + 1: the group's gradients go to the
+// The member form (sigp_loo_grad_ard_batch): nb lockstep members on scaled features U [nb][n_pad][dp] (member stride sU), member b's M at
+// M + b ls.P (gU here and for the leave-block-out scores, gD for the hindcast scores), vectors, partials and gradient at b times the
+// strides of ls behind w, partial and gdev (ls.grad = d + 1: the group's gradients go to the
 // host in one copy), its sn~ in sn_m[b] (NULL: snt).  One member with zero strides is the single fit.
 static int loo_ard_pass_members(sigp_handle* h, hipStream_t st, int nb, int kernel_id, const double* U, long sU, long n, long d, long dp, long n_pad, LooArdVecs w,
-                                LooArdStrides ls, double* partial, double* gdev, double snt, const double* sn_m, double* grad) {
+                                LooArdStrides ls, const double* M, double* partial, double* gdev, double snt, const double* sn_m, double* grad) {
   const long ntiles = kbuild_tiles(n_pad);
   const ArdMemberStrides ms{sU, ls.P, ls.w, 0, ls.partial, ls.w, ls.w};
   int rc;
   {
     ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n * n * (3.0 * d + 4.0 * ((d + 15) / 16 * 16) + 36)), nb * (4.0 * n * n + 8.0 * ntiles * (192.0 * d + dp)));
-    if ((rc = ard_tile_pass_members<ARD_W_LOO>(h, st, nb, U, n, d, dp, n_pad, ms, kernel_id, h->gU, n_pad, w.a(), nullptr, w.v(), w.eps(), partial))) return rc;
+    if ((rc = ard_tile_pass_members<ARD_W_LOO>(h, st, nb, U, n, d, dp, n_pad, ms, kernel_id, M, n_pad, w.a(), nullptr, w.v(), w.eps(), partial))) return rc;
     hipLaunchKernelGGL(loo_ard_finish_kernel, dim3((unsigned)(d + 1), (unsigned)nb), dim3(256), 0, st, (const double*)partial, ntiles, (int)dp, (int)d, (int)n,
-                       (const double*)h->gU, n_pad, w, snt, gdev, ls, sn_m);
+                       M, n_pad, w, snt, gdev, ls, sn_m);
     HIPCHK(h, hipGetLastError());
   }
   HIPCHK(h, hipMemcpyAsync(grad, gdev, (size_t)nb * (d + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -37,7 +38,7 @@ static int loo_ard_pass_members(sigp_handle* h, hipStream_t st, int nb, int kern
 }
 
 static int loo_ard_pass(sigp_handle* h, hipStream_t st, int kernel_id, LooArdVecs w, ScoreArdParts ap, double snt, double* grad) {
-  return loo_ard_pass_members(h, st, 1, kernel_id, h->X, 0, h->n, h->d, h->dp, h->n_pad, w, LooArdStrides{0, 0, 0, 0, 0}, ap.partial(), ap.grad(), snt, nullptr, grad);
+  return loo_ard_pass_members(h, st, 1, kernel_id, h->X, 0, h->n, h->d, h->dp, h->n_pad, w, LooArdStrides{0, 0, 0, 0, 0}, h->gU, ap.partial(), ap.grad(), snt, nullptr, grad);
 }
 
 int sigp_loo_grad_ard(sigp_handle* h, int kernel_id, const double* theta, int64_t ntheta, int sigma_mode, int criterion, double* mean, double* var, double* score,

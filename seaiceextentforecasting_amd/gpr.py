@@ -1205,7 +1205,7 @@ class GPR:
             self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
 
     def _ard_score_batch(self, what, theta, grad, group, predictions, cid, call):
-        """What ``loo_ard_batch`` and ``cv_ard_batch`` share after their own checks: the kernel / engine, the staged data, theta's width -- all
+        """What ``loo_ard_batch``, ``cv_ard_batch`` and ``hindcast_ard_batch`` share after their own checks: the kernel / engine, the staged data, theta's width -- all
         before any device call -- then the buffers, ``call(theta, F, d, n, mean, var, score, grad)`` and the result."""
         if self.kernel == "netdiffusion" or self.dtype != "f64":
             raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
@@ -1354,6 +1354,88 @@ class GPR:
             return bfgs_lockstep(lambda t: self.cv_ard_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter,
                                  gtol=gtol, ftol=ftol, max_step=max_step)
         return bfgs_lockstep(lambda t: self.cv_objective_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, group=group), th0, maxiter=maxiter, gtol=gtol,
+                             ftol=ftol, max_step=max_step)
+
+    def hindcast_ard_batch(self, theta, lead=1, min_train=None, first=0, criterion="hindcast_nlpd", sigma_f="refit", grad="exact", group=8, predictions=False):
+        """``hindcast_ard`` for many fits in one device call on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern, fp64):
+        theta [F, d + 1] = (log l_1 .. log l_d, log sn~) per FIT, fit i uses data set (first + i) % B -- two fits may share a data set and
+        differ in scales.  Lockstep groups of ``group`` fits (``sigp_hindcast_grad_ard_batch``): per group one staging launch, the fit and
+        ``hindcast_batch``'s launches at ell = 1 on the staged features, then ``hindcast_ard``'s gradient for all members at once (the
+        inverse factor, W = U C on a kernel that keeps the row in LDS, one cubic product per member, one tile pass).  Returns (value [F],
+        grad [F, d + 1] or None) with value = the hindcast negative log predictive density (``criterion='hindcast_nlpd'``) or sum of squared
+        errors (``'hindcast_sse'``) of ``hindcast(lead, min_train, sigma_f)``; ``grad=None``: values only, no inverse and no cubic work.
+        ``predictions=True`` returns dict(value, grad, mean [F, n], var [F, n], nlpd [F], sse [F]) instead (NaN where a row is not scored).
+        A fit whose K~ is not SPD or whose exp(theta) overflows gets +inf in its value, both scores and all its gradient entries and NaN
+        predictions; its group mates are unaffected.  The gradient pass forms every number by ``hindcast_ard``'s own chain of operations:
+        where the lockstep factorisation has the single fit's bits (small orders), every fit carries the bits ``hindcast_ard`` returns for
+        it.  ``min_train=None`` means max(2, d + 1) with d of the staged data sets, as in ``hindcast_batch``."""
+        if criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse' (the leave-one-out scores: loo_ard_batch, the leave-block-out scores: cv_ard_batch)")
+        if grad not in (None, "exact"):
+            raise ValueError("grad must be None or 'exact'")
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, getattr(self, "_batch_n", None), getattr(self, "_batch_d", None))
+        cid = L.HINDCAST_CRITERION_IDS[criterion]
+        return self._ard_score_batch("hindcast_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: self._lib.sigp_hindcast_grad_ard_batch(
+            self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, lead, min_train, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+
+    def hindcast_objective_batch(self, theta, lead=1, min_train=None, first=0, criterion="hindcast_nlpd", sigma_f="refit", group=8):
+        """A hindcast score over ONE common length scale for many fits in one device call: theta [F, 2] = (log l, log sn~) per fit ->
+        (value [F], grad [F, 2]).  It is ``hindcast_ard_batch`` at equal scales with d/dlog l = sum_k d/dlog l_k: per fit the bits
+        ``hindcast_objective`` returns for it where ``hindcast_ard_batch`` carries ``hindcast_ard``'s.  A fit whose exp(theta) is not finite
+        (it rides along at harmless parameters) or whose K~ is not SPD gets inf in its value and both gradient entries."""
+        if criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse'")
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, getattr(self, "_batch_n", None), getattr(self, "_batch_d", None))
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        d = getattr(self, "_batch_d", None)
+        if d is None:
+            raise RuntimeError("hindcast_objective_batch: stage the data sets with upload_batch() first")
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        if theta.ndim != 2 or theta.shape[1] != 2:
+            raise ValueError("theta must be [F, 2] = (log l, log sn~) per fit, got %s" % (theta.shape,))
+        with np.errstate(over="ignore"):
+            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
+        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
+        th = np.where(ok[:, None], np.concatenate([np.repeat(theta[:, :1], d, axis=1), theta[:, 1:]], axis=1), 0.0)
+        f, g = self.hindcast_ard_batch(th, lead=lead, min_train=min_train, first=first, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group)
+        f, g = np.array(f, dtype=np.float64), np.array([[np.sum(gi[:-1]), gi[-1]] for gi in g])       # row by row, as hindcast_objective adds them
+        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
+        f[~ok] = np.inf
+        g[~ok] = np.inf
+        return f, g
+
+    def optimize_hindcast_batch(self, X, y, theta0, lead=1, min_train=None, criterion="hindcast_nlpd", sigma_f="refit", ard=True, group=8, maxiter=50, gtol=1e-5,
+                                ftol=1e-10, max_step=2.0):
+        """``optimize_ard(criterion='hindcast_*')`` for EVERY data set of a retrospective run at once: X [B, n, d], y [B, n] -> dict(x [F, d + 1],
+        fun [F], nit [F], converged [F], nfev = device calls), the lockstep BFGS of ``optimize_batch`` (``optim.bfgs_lockstep``) on the
+        expanding-window hindcast score ``criterion`` ('hindcast_nlpd' | 'hindcast_sse') of ``hindcast(lead, min_train, sigma_f)`` -- the
+        score the retrospective loop reports.  Each round is ONE device call for all unfinished starts (``hindcast_ard_batch``).
+        ``ard=True``: one length scale per feature and the noise; ``theta0`` is [F, d + 1], [d + 1], [F, 2] or [2] (the common log l is
+        repeated for all d features), as ``optimize_cv_batch`` takes it; F = S B rows are S starts per data set, start i on data set
+        i % B, and all F results come back.  ``ard=False``: one common length scale (``hindcast_objective_batch``), ``theta0`` [2] or
+        [F, 2], x [F, 2].  ``min_train=None`` means max(2, d + 1).  RBF / Matern, fp64; lead <= 128 and at least one scored row."""
+        from .optim import bfgs_lockstep
+        if criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse' (the leave-block-out scores: optimize_cv_batch; the leave-one-out scores and "
+                             "'nlml': optimize_ard_batch)")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        X = L.f64(X, 3)
+        B, n, d = X.shape
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, n, d)
+        if ard:
+            th0 = self._ard_starts(theta0, B, d)
+        else:
+            th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
+            if th0.ndim != 2 or th0.shape[1] != 2:
+                raise ValueError("theta0 must hold 2 entries per start (log l, log sn~) with ard=False")
+            th0 = np.array(th0) if th0.shape[0] != B and th0.shape[0] % B == 0 else np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, 2))
+        self.upload_batch(X, y, None, group=group, concurrency=1)
+        objective = self.hindcast_ard_batch if ard else self.hindcast_objective_batch
+        return bfgs_lockstep(lambda t: objective(t, lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f, group=group), th0, maxiter=maxiter, gtol=gtol,
                              ftol=ftol, max_step=max_step)
 
     def _loo_objective_batch(self, theta, criterion, sigma_f, group):
