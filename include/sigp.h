@@ -356,7 +356,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
  * and the fit must have come from sigp_fit_predict, which is told ell: d/dlog ell = ell d/dell), else NULL.  Errors as sigp_loo (fp32 handle,
  * sharded fit, n < 2, not fitted: SIGP_BAD_ARG).  The fit is only read: sigp_predict / sigp_get_alpha / sigp_loo afterwards return the bits
  * they returned before.
- * Not covered: gradients in sigp_small_run_loo (the one-workgroup kernel), sharded fits, the fp32 engine.  With per-feature length scales
+ * The one-workgroup kernel has its own: sigp_small_run_loo_grad.  Not covered: sharded fits, the fp32 engine.  With per-feature length scales
  * set (sigp_set_length_scales) the derivative is that of the common multiplier ell; the per-feature derivatives are sigp_loo_grad_ard's. */
 int sigp_loo_grad(sigp_handle* h, int sigma_mode, const double* MSigma, int64_t ldsigma, double* mean, double* var, double* score, double* grad);
 /* Lockstep groups on the resident batch data, arguments as sigp_loo_batch (RBF / Matern only); grad [count][4].  A non-SPD member gets +inf
@@ -521,8 +521,8 @@ int sigp_cv_grad_ard_batch(sigp_handle* h, int64_t first, int64_t count, int ker
  * sigp_predict / sigp_get_alpha / sigp_loo / sigp_cv afterwards return the bits they returned before.  SIGP_BAD_ARG: an fp32 handle, a
  * sharded fit, not fitted, lead < 1, lead > SIGP_HINDCAST_MAX_LEAD, min_train < 1, no scored row (min_train + lead - 1 > n - 1), a bad
  * sigma_mode.  Device work is accounted under SIGP_KC_MLII (the scan and the row pass: one entry each).
- * Gradients for lockstep groups: sigp_hindcast_grad_ard_batch (below).  Out of scope: gradients in sigp_small_*, the reference kernel's
- * gradient, the fp32 engine, sharded fits. */
+ * Gradients for lockstep groups: sigp_hindcast_grad_ard_batch (below); the reference kernel's, in the one-workgroup kernel:
+ * sigp_small_run_hindcast_grad.  Out of scope: the fp32 engine, sharded fits. */
 enum { SIGP_HINDCAST_MAX_LEAD = 128, SIGP_HINDCAST_SMALL_MAX_LEAD = 32 };
 int sigp_hindcast(sigp_handle* h, int64_t lead, int64_t min_train, int sigma_mode, double* mean, double* var, double* score);
 /* ... for lockstep groups on the data sets resident after sigp_batch_upload (RBF / Matern-5/2; the retro loop's refits per grid point,
@@ -541,6 +541,27 @@ int sigp_hindcast_batch(sigp_handle* h, int64_t first, int64_t count, int kernel
 int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead,
                             int64_t min_train, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* hc_mean,
                             double* hc_var, int64_t nstride);
+/* Gradients of the leave-one-out and hindcast scores in the one-workgroup kernel (the reference's own kernel): sigp_small_run_loo /
+ * sigp_small_run_hindcast with `criterion` (SIGP_LOO_NLPD / SIGP_LOO_SSE) added, in the same single launch, one workgroup per fit.
+ * out8 [nprob][8] = the six outputs of the score entry, then d S / d log l and d S / d log sn~ of the score S the criterion names, with
+ * (l, sn~) held and sigma_f re-profiled as sigma_mode says.  out8[0..5], mean / var and the row predictions carry the bytes the score entry
+ * returns for the same arguments.  A score is a function of K~ = A diag(w) A^T + sn~ I and y alone; with its symmetric adjoint G = dS/dK~
+ * (sigp_loo_grad_ard's for leave-one-out, sigp_hindcast_grad_ard's for the hindcast)
+ *     dS/dlog l = l <G, A diag(dw) A^T>,  dw_k = lam_k exp(l lam_k)  (lam_mode 1 sets: sigp_small_set_dweights' pool; without it NaN),     dS/dlog sn~ = sn~ tr G.
+ * G is never stored: with X = L~^-1 formed in LDS over L~, G = X^T C X and both contractions are sums of b^T C b over b = X a_c and over the
+ * columns of X; the hindcast flavour saves the band L~(t, s_t..t) before the inverse overwrites it.  No atomics, every sum in a fixed order:
+ * the same bits on every run, whatever a fit's place in the queue.  A non-SPD K~: +inf in out8[4..7], rows as the caller left them.
+ * Limits (SmallLayout, smallgp_layout.hpp): every n <= 96 with every m <= 8 and every lead <= SIGP_HINDCAST_SMALL_MAX_LEAD; beyond that what
+ * fits in LDS at feature chunk 8 -- leave-one-out: n <= 128 up to m = 6, n <= 127 at m = 7, 8; hindcast at lead = 1: n <= 128 up to m = 5,
+ * n <= 127 above, and at n = 128, m = 0 up to lead = 6 -- for the LARGEST n and m uploaded.  SIGP_BAD_ARG: what the score entry refuses, a
+ * bad criterion, and a launch beyond these limits.  To fit, the launch may build K~ from shorter feature chunks than the score entry does
+ * (as sigp_small_run_cv); the bytes then agree where no set has more features than the chunk.  Not covered: leave-block-out gradients. */
+int sigp_small_run_loo_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode,
+                            int criterion, double* out8, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var,
+                            int64_t nstride);
+int sigp_small_run_hindcast_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead,
+                                 int64_t min_train, int sigma_mode, int criterion, double* out8, double* mean, double* var, int64_t mstride,
+                                 double* hc_mean, double* hc_var, int64_t nstride);
 /* The hindcast scores AND the exact derivatives of one of them with respect to theta = (log l_1 .. log l_d, log sn~) (RBF / Matern-5/2,
  * fp64), so that the length scales can be chosen by the score the retro loop reports (September1st_retro.py:176-248) instead of a grid.
  * theta, ntheta = d + 1, criterion (SIGP_LOO_NLPD / SIGP_LOO_SSE) and mean / var [n] (both or neither) as sigp_loo_grad_ard.  Sets the

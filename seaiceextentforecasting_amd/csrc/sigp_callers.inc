@@ -60,7 +60,8 @@ struct SmallRequest {
   SmallFlavour flavour = SmallFlavour::Plain;
   int sigma_mode = 0;                                  // Loo, Cv, Hindcast: SIGP_LOO_REFIT / SIGP_LOO_FIXED
   int64_t block = 0, gap = 0;                          // Cv
-  int64_t lead = 0, min_train = 0;                     // Hindcast
+  int64_t lead = 0, min_train = 0;                     // Hindcast, HindcastGrad
+  int criterion = 0;                                   // LooGrad, HindcastGrad: SIGP_LOO_NLPD / SIGP_LOO_SSE
   double *row_mean = nullptr, *row_var = nullptr;      // Loo, Cv, Hindcast: the caller's [nprob][pitch]
   int64_t pitch = 0;
 };
@@ -88,6 +89,9 @@ static void small_count_flops(double& fl, const SmallSet& s, const SmallRequest&
     case SmallFlavour::Loo: fl += inverse + 2.0 * n * n; break;                       // X's column norms and X^T z
     case SmallFlavour::Cv: fl += inverse + 2.0 * n * n; fl += n * n * (rq.block + 2.0 * rq.gap); break;   // ... and the folds' P_SS from X's columns
     case SmallFlavour::Hindcast: fl += 4.0 * n * rq.lead + 2.0 * n * n; break;        // the row segments and the prefix sums of z^2
+    // ... then X, b_c = X a_c and x_c^T C x_c: Loo X^T b_c and the lower triangle of P; Hindcast the band and the scan against every column
+    case SmallFlavour::LooGrad: fl += 2.0 * inverse + 2.0 * n * n + 2.0 * n * n * s.N + 4.0 * n * (s.N + n); break;
+    case SmallFlavour::HindcastGrad: fl += 4.0 * n * rq.lead + 2.0 * n * n + inverse + n * n * s.N + (8.0 * rq.lead + 5.0) * n * (s.N + n); break;
   }
 }
 
@@ -95,7 +99,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
                           double* mean, double* var, int64_t mstride, const SmallRequest& rq) {
   if (!h || h->sm_sets.empty()) return fail(h, SIGP_BAD_ARG, "small_run: call sigp_small_upload first");
   const SmallFlavour F = rq.flavour;
-  const bool cv = F == SmallFlavour::Cv, hc = F == SmallFlavour::Hindcast, rows = small_has_rows(F);
+  const bool cv = F == SmallFlavour::Cv, hc = F == SmallFlavour::Hindcast || F == SmallFlavour::HindcastGrad, rows = small_has_rows(F);
   const char* cvloo = cv ? "cv" : "loo";
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
   if (rows && (!rq.row_mean || !rq.row_var || rq.pitch < h->sm_nmax)) {
@@ -110,6 +114,15 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
     if (!ch)
       return fail(h, SIGP_BAD_ARG, "small_run_cv: n = %d with m = %d leaves no LDS for the folds' %ld bytes (feature chunk 8: %ld of %ld bytes)", h->sm_nmax, h->sm_mmax,
                   lds - SmallLayout{h->sm_nmax, h->sm_mmax, 8, SmallFlavour::Plain}.bytes(), lds, SM_LDS_MAX);
+  }
+  // so do the score gradients, whose image adds Bc, gv and (hindcast) the saved band
+  if (small_is_score_grad(F)) {
+    const int lead = hc ? (int)rq.lead : 0;
+    ch = small_pick_chunk(h->sm_nmax, h->sm_mmax, F, h->sm_ch, lead);
+    lds = SmallLayout{h->sm_nmax, h->sm_mmax, ch ? ch : 8, F, lead}.bytes();
+    if (!ch)
+      return fail(h, SIGP_BAD_ARG, "small_run_%s_grad: n = %d with m = %d and lead = %d needs %ld bytes of LDS at feature chunk 8; the limit is %ld (every n <= 96 with m <= %d and lead <= %d fits)",
+                  hc ? "hindcast" : "loo", h->sm_nmax, h->sm_mmax, lead, lds, SM_LDS_MAX, SM_MMAX, (int)SIGP_HINDCAST_SMALL_MAX_LEAD);
   }
   std::vector<char> cv_checked(cv ? h->sm_sets.size() : 0, 0);
   if (h->sm_mmax > 0 && (!mean || !var || mstride < h->sm_mmax)) return fail(h, SIGP_BAD_ARG, "small_run: mean / var [nprob][mstride >= %d] required", h->sm_mmax);
@@ -155,7 +168,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
     double fl = 0;
     for (const auto& pb : probs) small_count_flops(fl, h->sm_sets[(size_t)pb.set], rq);
     ProfScope ps(h, st, SIGP_KC_SMALL, fl, 0.0);
-    const SmallExtras x{d_lmean, d_lvar, (int)ns, rq.sigma_mode, (int)rq.block, (int)rq.gap, (int)rq.lead, (int)rq.min_train};
+    const SmallExtras x{d_lmean, d_lvar, (int)ns, rq.sigma_mode, (int)rq.block, (int)rq.gap, (int)rq.lead, (int)rq.min_train, rq.criterion};
     decltype(&small_launch<256, SmallFlavour::Plain>) launch = nullptr;
     switch (F) {
       // four wavefronts per fit at every order; one per fit (orders up to 64) is a measurement switch: on the reference-size grid
@@ -165,6 +178,8 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
       case SmallFlavour::Loo: launch = small_launch<256, SmallFlavour::Loo>; break;
       case SmallFlavour::Cv: launch = small_launch<256, SmallFlavour::Cv>; break;
       case SmallFlavour::Hindcast: launch = small_launch<256, SmallFlavour::Hindcast>; break;
+      case SmallFlavour::LooGrad: launch = small_launch<256, SmallFlavour::LooGrad>; break;
+      case SmallFlavour::HindcastGrad: launch = small_launch<256, SmallFlavour::HindcastGrad>; break;
     }
     HIPCHK(h, launch(h, st, nprob, lds, ch, d_out, d_mean, d_var, (int)ms, x));
   }
@@ -238,6 +253,31 @@ int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_in
   rq.flavour = SmallFlavour::Hindcast; rq.sigma_mode = sigma_mode; rq.lead = lead; rq.min_train = min_train;
   rq.row_mean = hc_mean; rq.row_var = hc_var; rq.pitch = nstride;
   return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
+}
+
+// sigp_small_run_loo, then the derivatives of one of its two scores w.r.t. (log l, log sn~) in the same single launch (SmallFlavour::LooGrad)
+int sigp_small_run_loo_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode, int criterion,
+                            double* out8, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_loo_grad: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (criterion != SIGP_LOO_NLPD && criterion != SIGP_LOO_SSE) return fail(h, SIGP_BAD_ARG, "small_run_loo_grad: criterion must be SIGP_LOO_NLPD or SIGP_LOO_SSE");
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::LooGrad; rq.sigma_mode = sigma_mode; rq.criterion = criterion;
+  rq.row_mean = loo_mean; rq.row_var = loo_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, rq);
+}
+
+// sigp_small_run_hindcast, then the derivatives of one of its two scores in the same single launch (SmallFlavour::HindcastGrad: the band of L~ the
+// adjoint reads is saved in LDS, then L~^-1 is formed over L~)
+int sigp_small_run_hindcast_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead, int64_t min_train,
+                                 int sigma_mode, int criterion, double* out8, double* mean, double* var, int64_t mstride, double* hc_mean, double* hc_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_hindcast_grad: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (criterion != SIGP_LOO_NLPD && criterion != SIGP_LOO_SSE) return fail(h, SIGP_BAD_ARG, "small_run_hindcast_grad: criterion must be SIGP_LOO_NLPD or SIGP_LOO_SSE");
+  if (lead < 1 || lead > SIGP_HINDCAST_SMALL_MAX_LEAD) return fail(h, SIGP_BAD_ARG, "small_run_hindcast_grad: 1 <= lead <= %d required (got %lld)", (int)SIGP_HINDCAST_SMALL_MAX_LEAD, (long long)lead);
+  if (min_train < 1) return fail(h, SIGP_BAD_ARG, "small_run_hindcast_grad: min_train >= 1 required (got %lld)", (long long)min_train);
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::HindcastGrad; rq.sigma_mode = sigma_mode; rq.criterion = criterion; rq.lead = lead; rq.min_train = min_train;
+  rq.row_mean = hc_mean; rq.row_var = hc_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, rq);
 }
 
 // ---- ComplexNetworks tau(): cell-to-cell correlation matrix + thresholded mean (ComplexNetworks.py:31-47) ------------

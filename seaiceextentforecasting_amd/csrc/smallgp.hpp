@@ -52,6 +52,17 @@
 // (sum_{j<s} z_j^2) / s (sigma_fixed = 0: sigma_f profiled on the training rows alone) or sigma_f (sigma_fixed = 1); one thread per row, every
 // sum in ascending j.  Outputs as Loo's; rows that are not scored get NaN.  A non-SPD K~ gives +inf in both scores.
 //
+// LooGrad, HindcastGrad (8 outputs): Loo's / Hindcast's six -- the same statements in the same order, so the same bits --, then the
+// derivative of the score x.crit (nlpd or sse) w.r.t. (log l, log sn~) with theta held and sigma_f re-profiled as x.sigma_fixed says.  The score
+// is a function of K~ and y alone; with its symmetric adjoint G = dS/dK~ = X^T C X (X = L~^-1)
+//     dS/dlog l = l <G, D1> = l sum_c dw_c b_c^T C b_c,  b_c = X a_c  (the chunk's b_c kept in Bc),     dS/dlog sn~ = sn~ tr G = sn~ sum_c x_c^T C x_c,
+// x_c = column c of X (the upper triangle of Kp is zero from the build on).  G and C are never formed; b^T C b is
+//   Loo (looard.hpp)        (u.b)(z.b) + sum_j gamma_j (X^T b)_j^2 + eps (z.b)^2,   u = X beta       [C = (u z^T + z u^T)/2 + X Gamma X^T + eps z z^T]
+//   Hindcast (hindcast.hpp) sum_t sum_{i=s_t..t} L_ti b_i (sum_{j=s_t..i-1} B_tj b_j + B_ti b_i / 2) - sum_i zbar_i b_i (sum_{j<i} z_j b_j + z_i b_i / 2)
+//                           with B_tj = rho_t z_j + 2 kappa_t sigma_t L_tj: the lower triangle of L^T B - zbar z^T, its diagonal halved.
+// The band L~(t, s_t..t) is saved in hb before the inverse overwrites L~.  Every thread adds its terms in a fixed order and smallgp_allsum adds
+// the threads: the same bits on every run.  lam_mode 1 sets without dweights: NaN in dS/dlog l alone.
+//
 // NT = threads per workgroup: 256 (four wavefronts per fit) is the default at every order; NT = 64 (one wavefront per fit, every
 // barrier of the column loop a wave-local no-op) is kept as a measurement switch ("small_nt64") -- on the reference-size grid it
 // is SLOWER (1.71 vs 1.02 ms for 48 000 fits of n = 6 .. 45): the rank-1 updates have ~n^2/2 elements, enough for four waves,
@@ -85,6 +96,7 @@ struct SmallExtras {
   int sigma_fixed;         // Loo, Cv, Hindcast: 0 = sigma_f re-profiled without the rows left out, 1 = the full fit's sigma_f
   int block, gap;          // Cv
   int lead, min_train;     // Hindcast
+  int crit;                // LooGrad, HindcastGrad: the score that is differentiated, 0 = nlpd, 1 = sse (SIGP_LOO_NLPD / SIGP_LOO_SSE)
 };
 
 // one workgroup's fit: its sizes, its pieces in LDS and this thread's place in the 16-wide element mapping
@@ -278,9 +290,10 @@ __device__ __forceinline__ bool smallgp_write_scores(const SmallFit& w, double t
 }
 
 // ---- the tails: y, o, rmean, rvar = this fit's y, its row of `out` and its rows of the flavour's predictions -------------------------------
-template <int NT>
+// KEEP: r_t, w_t and sigma_t of every row (w_t = 0: not scored) into gv[0], gv[1], gv[2] for the gradient
+template <int NT, bool KEEP = false>
 __device__ __forceinline__ void smallgp_tail_hindcast(const SmallFit& w, const SmallExtras& x, const double* __restrict__ y, double sf, double* o,
-                                                      double* __restrict__ rmean, double* __restrict__ rvar) {
+                                                      double* __restrict__ rmean, double* __restrict__ rvar, double* gv = nullptr) {
   const double qnan = __builtin_nan("");
   const double* z = w.z;
   double tn = 0.0, ts = 0.0;
@@ -301,6 +314,9 @@ __device__ __forceinline__ void smallgp_tail_hindcast(const SmallFit& w, const S
       mu = y[t] - r;
       tn += 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
       ts = fma(r, r, ts);
+      if constexpr (KEEP) { gv[t] = r; gv[w.n + t] = wt; gv[2 * w.n + t] = sig; }
+    } else if constexpr (KEEP) {
+      gv[t] = 0.0; gv[w.n + t] = 0.0; gv[2 * w.n + t] = 0.0;
     }
     rmean[t] = mu;
     rvar[t] = v;
@@ -308,9 +324,10 @@ __device__ __forceinline__ void smallgp_tail_hindcast(const SmallFit& w, const S
   smallgp_write_scores<NT>(w, tn, ts, o);
 }
 
-template <int NT>
+// KEEP: a~_i into at and g_i into gv[0] for the gradient
+template <int NT, bool KEEP = false>
 __device__ __forceinline__ void smallgp_tail_loo(const SmallFit& w, const SmallExtras& x, const double* __restrict__ y, double zz, double sf, double* o,
-                                                 double* __restrict__ rmean, double* __restrict__ rvar) {
+                                                 double* __restrict__ rmean, double* __restrict__ rvar, double* gv = nullptr) {
   const int n = w.n;
   // column i of X: a~_i and g_i in one walk (odd pitch: the lanes' columns fall in different banks)
   double tn = 0.0, ts = 0.0;
@@ -323,6 +340,7 @@ __device__ __forceinline__ void smallgp_tail_loo(const SmallFit& w, const SmallE
     rvar[i] = v;
     tn += 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
     ts = fma(r, r, ts);
+    if constexpr (KEEP) { w.at[i] = a; gv[i] = g; }
   }
   smallgp_write_scores<NT>(w, tn, ts, o);
 }
@@ -440,6 +458,181 @@ __device__ __forceinline__ void smallgp_tail_grad(const SmallFit& w, const Small
   }
 }
 
+// ---- the score gradients (LooGrad, HindcastGrad) -----------------------------------------------------------------------------------------------
+// kappa = d nlpd / d var, rho = d nlpd / d r of a scored row with residual r and variance v; for the sse 0 and 2 r
+__device__ __forceinline__ void small_kappa_rho(int crit, double r, double v, double& kappa, double& rho) {
+  if (crit == 0) { kappa = 1.0 / (2.0 * v) - r * r / (2.0 * v * v); rho = r / v; }
+  else { kappa = 0.0; rho = 2.0 * r; }
+}
+
+// dw of the chunk's features into wk and the chunk's raw columns into Ac (as the Grad tail stages them), then Bc(i, c) = sum_{k <= i} X(i, k) Ac(k, c);
+// a barrier ahead of the staging and one behind Bc
+template <int NT>
+__device__ __forceinline__ void smallgp_stage_b(const SmallFit& w, const SmallSet& st, const SmallProb& pb, const double* __restrict__ A, const double* __restrict__ lam,
+                                                const double* __restrict__ dlam, int k0, int kc, double* Bc) {
+  const int n = w.n, N = w.N, ldk = w.ldk, lda = w.lda, tid = w.tid;
+  const double qnan = __builtin_nan("");
+  __syncthreads();
+  if (tid < kc) {
+    const double l = lam[k0 + tid];
+    w.wk[tid] = st.lam_mode ? (dlam ? dlam[k0 + tid] : qnan) : l * exp(pb.ell * l);
+  }
+  for (int e = tid; e < n * kc; e += NT) {
+    const int r = e / kc, k = e - r * kc;
+    w.Ac[r * lda + k] = A[(long)r * N + k0 + k];
+  }
+  __syncthreads();
+  for (int e = tid; e < n * kc; e += NT) {
+    const int i = e / kc, c = e - i * kc;
+    const double* xi = w.Kp + i * ldk;
+    double v = 0.0;
+    for (int k = 0; k <= i; ++k) v = fma(xi[k], w.Ac[k * lda + c], v);
+    Bc[i * lda + c] = v;
+  }
+  __syncthreads();
+}
+
+// this thread's share of sum_c wc_c b_c^T C b_c over the ncol columns of b [n][ldb] for the leave-one-out C (wc = nullptr: weights 1):
+// gam, u, eps as in the header; `tri`: b is X itself, whose column c is zero above row c
+template <int NT>
+__device__ __forceinline__ double smallgp_quad_loo(const SmallFit& w, const double* b, int ldb, int ncol, const double* wc, bool tri, const double* gam, const double* u,
+                                                   double eps) {
+  const int n = w.n, ldk = w.ldk, tid = w.tid;
+  const double* z = w.z;
+  double acc = 0.0;
+  for (int e = tid; e < n * ncol; e += NT) {              // gamma_j (X^T b_c)_j^2; with b = X the pair (j, c), j < c, stands for (c, j) as well
+    const int j = e / ncol, c = e - j * ncol;
+    if (tri && j > c) continue;
+    double p = 0.0;
+    for (int k = tri ? c : j; k < n; ++k) p = fma(w.Kp[k * ldk + j], b[k * ldb + c], p);
+    const double g = tri && j < c ? gam[j] + gam[c] : gam[j];
+    acc = fma((wc ? wc[c] : 1.0) * g * p, p, acc);
+  }
+  for (int c = tid; c < ncol; c += NT) {
+    double ub = 0.0, zb = 0.0;
+    for (int i = tri ? c : 0; i < n; ++i) { const double bi = b[i * ldb + c]; ub = fma(u[i], bi, ub); zb = fma(z[i], bi, zb); }
+    acc = fma(wc ? wc[c] : 1.0, ub * zb + eps * zb * zb, acc);
+  }
+  return acc;
+}
+
+// the same for the hindcast C: rho, ks = 2 kappa sigma (both zero in rows that are not scored), zbar and the band hb [n][lead]
+template <int NT>
+__device__ __forceinline__ double smallgp_quad_hindcast(const SmallFit& w, const double* b, int ldb, int ncol, const double* wc, const double* rho, const double* ks,
+                                                        const double* zbar, const double* hb, int lead, int min_train) {
+  const int n = w.n, tid = w.tid;
+  const double* z = w.z;
+  double acc = 0.0;
+  for (int e = tid; e < n * ncol; e += NT) {              // row t of B against column c
+    const int t = e / ncol, c = e - t * ncol;
+    const int s = t - lead + 1;
+    if (s < min_train) continue;
+    const double* lt = hb + t * lead - s;
+    const double rt = rho[t], kt = ks[t];
+    double pre = 0.0, q = 0.0;
+    for (int j = s; j <= t; ++j) {
+      const double bj = b[j * ldb + c], lj = lt[j];
+      const double Bb = (rt * z[j] + kt * lj) * bj;
+      q = fma(lj * bj, pre + 0.5 * Bb, q);
+      pre += Bb;
+    }
+    acc = fma(wc ? wc[c] : 1.0, q, acc);
+  }
+  for (int c = tid; c < ncol; c += NT) {                  // the rank-one part: a scan of z_j b_j down the column
+    double pre = 0.0, q = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double bi = b[i * ldb + c], zb = z[i] * bi;
+      q = fma(zbar[i] * bi, pre + 0.5 * zb, q);
+      pre += zb;
+    }
+    acc = fma(wc ? -wc[c] : -1.0, q, acc);
+  }
+  return acc;
+}
+
+// after smallgp_invert and smallgp_tail_loo<NT, true>: o[6], o[7]
+template <int NT>
+__device__ __forceinline__ void smallgp_tail_loo_grad(const SmallFit& w, const SmallSet& st, const SmallProb& pb, const SmallExtras& x, const double* __restrict__ A,
+                                                      const double* __restrict__ lam, const double* __restrict__ dlam, double* Bc, double* gv, double zz, double sf,
+                                                      double* o) {
+  const int n = w.n, N = w.N, ldk = w.ldk, ch = w.ch, tid = w.tid;
+  double *gg = gv, *beta = gv + n, *gam = gv + 2 * n, *u = gv + 3 * n;
+  const double n1 = (double)(n - 1);
+  double ke = 0.0;
+  for (int i = tid; i < n; i += NT) {                     // the thread that wrote at[i] and g_i
+    const double a = w.at[i], g = gg[i], r = a / g;
+    const double s = x.sigma_fixed ? sf : (zz - a * r) / n1;
+    const double v = s / g;
+    double kappa, rho;
+    small_kappa_rho(x.crit, r, v, kappa, rho);
+    double be = -rho / g, ga = kappa * s / (g * g) + rho * a / (g * g);
+    if (!x.sigma_fixed) { be += 2.0 * kappa * a / (g * g * n1); ga -= kappa * a * a / (g * g * g * n1); }
+    beta[i] = be; gam[i] = ga;
+    ke += kappa / g;
+  }
+  const double eps = -smallgp_allsum<NT>(ke, w.red) / (x.sigma_fixed ? (double)n : n1);     // its barriers publish beta
+  for (int i = tid; i < n; i += NT) {
+    double a = 0.0;
+    for (int k = 0; k <= i; ++k) a = fma(w.Kp[i * ldk + k], beta[k], a);
+    u[i] = a;
+  }
+  double g1 = 0.0;
+  for (int k0 = 0; k0 < N; k0 += ch) {
+    const int kc = min(ch, N - k0);
+    smallgp_stage_b<NT>(w, st, pb, A, lam, dlam, k0, kc, Bc);
+    g1 += smallgp_quad_loo<NT>(w, Bc, w.lda, kc, w.wk, false, gam, u, eps);
+  }
+  __syncthreads();                                        // u, where there was no chunk
+  const double g0 = smallgp_quad_loo<NT>(w, w.Kp, ldk, n, nullptr, true, gam, u, eps);
+  const double G1 = smallgp_allsum<NT>(g1, w.red);
+  const double G0 = smallgp_allsum<NT>(g0, w.red);
+  if (tid == 0) { o[6] = pb.ell * G1; o[7] = pb.sn * G0; }
+}
+
+// after smallgp_tail_hindcast<NT, true>, L~ still in place: saves the band, inverts, o[6], o[7]
+template <int NT>
+__device__ __forceinline__ void smallgp_tail_hindcast_grad(const SmallFit& w, const SmallSet& st, const SmallProb& pb, const SmallExtras& x, const double* __restrict__ A,
+                                                           const double* __restrict__ lam, const double* __restrict__ dlam, double* Bc, double* gv, double* hb,
+                                                           double* o) {
+  const int n = w.n, N = w.N, ldk = w.ldk, ch = w.ch, tid = w.tid, lead = x.lead;
+  double *rho = gv, *ks = gv + n, *kw = gv + 2 * n, *zbar = gv + 3 * n;
+  const double* z = w.z;
+  for (int t = tid; t < n; t += NT) {                     // the thread that wrote r_t, w_t, sigma_t there
+    const int s = t - lead + 1;
+    const double r = rho[t], wt = ks[t], sig = kw[t];
+    double rh = 0.0, k2 = 0.0, kq = 0.0;
+    if (s >= x.min_train) {
+      double kappa;
+      small_kappa_rho(x.crit, r, sig * wt, kappa, rh);
+      k2 = 2.0 * kappa * sig;
+      kq = kappa * wt / (double)(x.sigma_fixed ? n : s);
+      for (int j = s; j <= t; ++j) hb[t * lead + j - s] = w.Kp[t * ldk + j];
+    }
+    rho[t] = rh; ks[t] = k2; kw[t] = kq;
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += NT) {
+    // zbar_j = sum_{t scored, s_t <= j <= t} rho_t L_tj + 2 z_j sum_{t scored, s_t > j} kappa_t w_t / s_t   (fixed: every scored t, / n)
+    double a = 0.0, c = 0.0;
+    const int t1 = min(n - 1, j + lead - 1);
+    for (int t = j; t <= t1; ++t)
+      if (t - lead + 1 >= x.min_train) a = fma(rho[t], hb[t * lead + j - (t - lead + 1)], a);
+    for (int t = x.sigma_fixed ? 0 : t1 + 1; t < n; ++t) c += kw[t];
+    zbar[j] = fma(2.0 * z[j], c, a);
+  }
+  smallgp_invert<NT>(w);                                  // its first barrier comes before its first write: the band is out
+  double g1 = 0.0;
+  for (int k0 = 0; k0 < N; k0 += ch) {
+    const int kc = min(ch, N - k0);
+    smallgp_stage_b<NT>(w, st, pb, A, lam, dlam, k0, kc, Bc);
+    g1 += smallgp_quad_hindcast<NT>(w, Bc, w.lda, kc, w.wk, rho, ks, zbar, hb, lead, x.min_train);
+  }
+  const double g0 = smallgp_quad_hindcast<NT>(w, w.Kp, ldk, n, nullptr, rho, ks, zbar, hb, lead, x.min_train);
+  const double G1 = smallgp_allsum<NT>(g1, w.red);
+  const double G0 = smallgp_allsum<NT>(g0, w.red);
+  if (tid == 0) { o[6] = pb.ell * G1; o[7] = pb.sn * G0; }
+}
+
 template <int NT, SmallFlavour F>
 __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict__ sets, const SmallProb* __restrict__ probs,
                                                       const double* __restrict__ Apool, const double* __restrict__ ypool,
@@ -450,7 +643,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
   __shared__ int s_info;
   const SmallProb pb = probs[blockIdx.x];
   const SmallSet st = sets[pb.set];
-  const SmallLayout lay{st.n, st.m, ch, F};
+  const SmallLayout lay{st.n, st.m, ch, F, F == SmallFlavour::HindcastGrad ? x.lead : 0};
   double* lds = (double*)smem_raw;
   SmallFit w;
   w.n = st.n; w.N = st.N; w.m = st.m; w.R = lay.rows();
@@ -472,13 +665,21 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
     if (info != 0) return;           // uniform
     double* rmean = x.row_mean + (long)blockIdx.x * x.pitch;
     double* rvar = x.row_var + (long)blockIdx.x * x.pitch;
+    const double* dlam = dlampool ? dlampool + st.lam_off : nullptr;
     if constexpr (F == SmallFlavour::Hindcast) {
       smallgp_tail_hindcast<NT>(w, x, y, sf, o, rmean, rvar);
+    } else if constexpr (F == SmallFlavour::HindcastGrad) {
+      smallgp_tail_hindcast<NT, true>(w, x, y, sf, o, rmean, rvar, lds + lay.gv());
+      smallgp_tail_hindcast_grad<NT>(w, st, pb, x, A, lam, dlam, lds + lay.Bc(), lds + lay.gv(), lds + lay.hb(), o);
+    } else if constexpr (F == SmallFlavour::LooGrad) {
+      smallgp_invert<NT>(w);
+      smallgp_tail_loo<NT, true>(w, x, y, zz, sf, o, rmean, rvar, lds + lay.gv());
+      smallgp_tail_loo_grad<NT>(w, st, pb, x, A, lam, dlam, lds + lay.Bc(), lds + lay.gv(), zz, sf, o);
     } else {
       smallgp_invert<NT>(w);
       if constexpr (F == SmallFlavour::Cv) smallgp_tail_cv<NT>(w, x, lds + lay.Pw(), lds + lay.Ww(), lds + lay.tv(), y, zz, sf, o, rmean, rvar);
       if constexpr (F == SmallFlavour::Loo) smallgp_tail_loo<NT>(w, x, y, zz, sf, o, rmean, rvar);
-      if constexpr (F == SmallFlavour::Grad) smallgp_tail_grad<NT>(w, st, pb, A, lam, dlampool ? dlampool + st.lam_off : nullptr, sf, o);
+      if constexpr (F == SmallFlavour::Grad) smallgp_tail_grad<NT>(w, st, pb, A, lam, dlam, sf, o);
     }
   }
 }

@@ -15,6 +15,7 @@ constexpr int SM_NMAX = 128;                   // largest order one workgroup ha
 constexpr int SM_MMAX = 8;                     // test points per fit
 constexpr int SM_CVW = 32;                     // widest window (block + 2 gap) of the leave-block-out flavour
 constexpr int SM_CVP = SM_CVW + 1;             // odd pitch of its w x w scratch matrices
+constexpr int SM_GV = 4;                       // vectors of order n the score gradients keep (gv)
 constexpr int SM_RED = 16;                     // doubles of reduction scratch (one per wavefront is used)
 constexpr int SM_SLACK = 24;                   // unused doubles behind a~: part of every launch's size since the first
 constexpr long SM_LDS_MAX = 160 * 1024 - 64;   // bytes of dynamic LDS one workgroup may ask for
@@ -25,12 +26,17 @@ constexpr long SM_LDS_MAX = 160 * 1024 - 64;   // bytes of dynamic LDS one workg
 //   Loo       the leave-one-out predictions and scores
 //   Cv        the leave-block-out predictions and scores
 //   Hindcast  the expanding-window hindcast predictions and scores
-enum class SmallFlavour { Plain, Grad, Loo, Cv, Hindcast };
+//   LooGrad / HindcastGrad   what Loo / Hindcast form, then the derivatives of one of the two scores w.r.t. (log l, log sn~)
+enum class SmallFlavour { Plain, Grad, Loo, Cv, Hindcast, LooGrad, HindcastGrad };
 
+// does the flavour differentiate a row score?
+__host__ __device__ constexpr bool small_is_score_grad(SmallFlavour f) { return f == SmallFlavour::LooGrad || f == SmallFlavour::HindcastGrad; }
 // doubles per fit of `out`
-__host__ __device__ constexpr int small_out_width(SmallFlavour f) { return f == SmallFlavour::Plain ? 4 : f == SmallFlavour::Grad ? 8 : 6; }
+__host__ __device__ constexpr int small_out_width(SmallFlavour f) { return f == SmallFlavour::Plain ? 4 : f == SmallFlavour::Grad || small_is_score_grad(f) ? 8 : 6; }
 // does the flavour write a prediction per training row (mean / var [nprob][pitch]) and the scores out[4], out[5]?
-__host__ __device__ constexpr bool small_has_rows(SmallFlavour f) { return f == SmallFlavour::Loo || f == SmallFlavour::Cv || f == SmallFlavour::Hindcast; }
+__host__ __device__ constexpr bool small_has_rows(SmallFlavour f) {
+  return f == SmallFlavour::Loo || f == SmallFlavour::Cv || f == SmallFlavour::Hindcast || small_is_score_grad(f);
+}
 
 // The LDS image of a fit of n training rows and m test points built ch features at a time; every offset in doubles from the start of the
 // dynamic LDS.  A launch is sized for its largest n and m; each workgroup lays out its own fit.
@@ -44,9 +50,18 @@ __host__ __device__ constexpr bool small_has_rows(SmallFlavour f) { return f == 
 //   Pw  [SM_CVW][SM_CVP]     a fold's P_SS, then its factor M (lower)
 //   Ww  [SM_CVW][SM_CVP]     W = M^-1 (lower)
 //   tv  [SM_CVW]             t = W a~_S
+//   LooGrad and HindcastGrad alone, behind at and its slack:
+//   Bc  [n][lda]             b_c = X a_c for the chunk's columns (X = L~^-1): what the Grad tail forms and does not keep
+//   gv  [SM_GV][n]           the adjoint's vectors: Loo g, beta, gamma, u = X beta;  Hindcast rho, 2 kappa sigma, kappa w / s, zbar
+//   hb  [n][lead]            HindcastGrad alone: the band L~(t, s_t .. t), saved before the inverse overwrites L~
+// Limits of the two (every order the upload takes is laid out; what does not fit in SM_LDS_MAX at feature chunk 8 is refused):
+//   every order n <= 96 with every m <= SM_MMAX fits, HindcastGrad at every lead <= SIGP_HINDCAST_SMALL_MAX_LEAD = 32 (chunk 32 throughout);
+//   beyond that whatever bytes() <= SM_LDS_MAX admits: LooGrad n <= 128 up to m = 6 and n <= 127 at m = 7, 8;  HindcastGrad at lead = 1
+//   n <= 128 up to m = 5 and n <= 127 at m = 6 .. 8, and at n = 128, m = 0 up to lead = 6.
 struct SmallLayout {
   int n, m, ch;
   SmallFlavour flavour;
+  int lead = 0;                                // HindcastGrad: the pitch of hb
   __host__ __device__ constexpr int rows() const { return n + 1 + m; }
   __host__ __device__ constexpr int ldk() const { return n | 1; }
   __host__ __device__ constexpr int lda() const { return ch + 1; }
@@ -59,14 +74,20 @@ struct SmallLayout {
   __host__ __device__ constexpr long Pw() const { return at() + n + SM_SLACK; }
   __host__ __device__ constexpr long Ww() const { return Pw() + SM_CVW * SM_CVP; }
   __host__ __device__ constexpr long tv() const { return Ww() + SM_CVW * SM_CVP; }
-  __host__ __device__ constexpr long bytes() const { return (flavour == SmallFlavour::Cv ? tv() + SM_CVW : Pw()) * (long)sizeof(double); }
+  __host__ __device__ constexpr long Bc() const { return Pw(); }
+  __host__ __device__ constexpr long gv() const { return Bc() + (long)n * lda(); }
+  __host__ __device__ constexpr long hb() const { return gv() + (long)SM_GV * n; }
+  __host__ __device__ constexpr long end() const {
+    return flavour == SmallFlavour::Cv ? tv() + SM_CVW : flavour == SmallFlavour::LooGrad ? hb() : flavour == SmallFlavour::HindcastGrad ? hb() + (long)n * lead : Pw();
+  }
+  __host__ __device__ constexpr long bytes() const { return end() * (long)sizeof(double); }
 };
 
 // The feature chunk of a launch whose largest fit has nmax rows and mmax test points: the largest of start, start / 2, ... down to 8
-// whose image fits (sigp_small_upload: start = 32, the Plain image; the Cv launch: start = the upload's chunk); 0 if none does.
-__host__ __device__ constexpr int small_pick_chunk(int nmax, int mmax, SmallFlavour f, int start) {
+// whose image fits (sigp_small_upload: start = 32, the Plain image; the Cv, LooGrad and HindcastGrad launches: start = the upload's chunk); 0 if none does.
+__host__ __device__ constexpr int small_pick_chunk(int nmax, int mmax, SmallFlavour f, int start, int lead = 0) {
   for (int ch = start; ch >= 8; ch /= 2)
-    if (SmallLayout{nmax, mmax, ch, f}.bytes() <= SM_LDS_MAX) return ch;
+    if (SmallLayout{nmax, mmax, ch, f, lead}.bytes() <= SM_LDS_MAX) return ch;
   return 0;
 }
 

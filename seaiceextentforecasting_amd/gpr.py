@@ -1482,7 +1482,7 @@ class GPR:
             raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse'")
         if criterion != "nlml" and self.kernel == "netdiffusion":
             raise ValueError("optimize_batch: the leave-one-out criteria cover the RBF / Matern kernels; the reference kernel's batch runs one workgroup per "
-                             "fit (sigp_small_run_loo), which has no gradients -- optimise its data sets one at a time with optimize(criterion=...)")
+                             "fit and minimises the leave-one-out and hindcast scores through optimize_small_batch(criterion=...)")
         if self.kernel == "netdiffusion":
             self.upload_batch(X, y, None, M=M)
             B = len(self._small_ids)
@@ -1517,6 +1517,65 @@ class GPR:
         if criterion != "nlml":   # the same lockstep BFGS on a leave-one-out score: one sigp_loo_grad_batch call per round
             return bfgs_lockstep(lambda t: self._loo_objective_batch(t, criterion, sigma_f, group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
         return bfgs_lockstep(lambda t: self.nlml_batch(t, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
+
+    def small_score_batch(self, theta, criterion="hindcast_nlpd", lead=1, min_train=2, sigma_f="refit", first=0, expm="eigh", sets=None):
+        """A leave-one-out or hindcast score of the reference kernel and its exact gradient for many (data set, theta) pairs in ONE launch, one
+        workgroup per pair, on the data sets staged by ``upload_batch`` (``SmallBatch.run(loo= / hindcast=, score_grad=)``): theta [F, 2] =
+        (log l, log sn~), pair i uses data set (first + i) % B or ``sets[i]``.  ``criterion`` 'loo_nlpd' | 'loo_sse' | 'hindcast_nlpd' |
+        'hindcast_sse'; ``lead`` / ``min_train`` as ``SmallBatch.run(hindcast=)``; ``expm`` as ``nlml_batch``.  Returns (score [F], grad [F, 2]),
+        +inf where K~ is not SPD or exp(theta) overflows."""
+        if self.kernel != "netdiffusion":
+            raise ValueError("small_score_batch runs the reference kernel (RBF / Matern: loo_ard_batch, hindcast_ard_batch)")
+        if criterion not in L.LOO_CRITERION_IDS and criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'loo_nlpd', 'loo_sse', 'hindcast_nlpd' or 'hindcast_sse' (block-CV gradients are not built for the reference kernel)")
+        if sigma_f not in L.LOO_MODES:
+            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        sb = getattr(self, "_small", None)
+        if sb is None:
+            raise RuntimeError("small_score_batch: stage the data sets with upload_batch(X_list, y_list, Xs_list, M=M_list) first")
+        theta = L.f64(np.atleast_2d(theta), 2)
+        if theta.shape[1] != 2:
+            raise ValueError("theta must be [F, 2]")
+        F, B = theta.shape[0], len(self._small_ids)
+        with np.errstate(over="ignore"):
+            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
+        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
+        val = np.full(F, np.inf)
+        g = np.full((F, 2), np.inf)
+        sb.clear_fits()
+        run = []
+        for i in np.flatnonzero(ok):
+            try:
+                sb.add_fit(self._small_ids[(first + i) % B if sets is None else int(sets[i])], ell[i], sn[i], expm=expm)
+                run.append(i)
+            except (FloatingPointError, OverflowError, ValueError):
+                pass
+        if run:
+            kind, key = criterion.split("_")
+            if kind == "loo":
+                r = sb.run(loo=sigma_f, score_grad=key)
+            else:
+                r = sb.run(hindcast=dict(lead=lead, min_train=min_train, sigma_f=sigma_f), score_grad=key)
+            val[run] = r[criterion]
+            g[run] = r[kind + "_grad"]
+            g[~np.isfinite(val)] = np.inf
+        return val, g
+
+    def optimize_small_batch(self, X, y, theta0, criterion="hindcast_nlpd", lead=1, min_train=2, sigma_f="refit", M=None, expm="eigh", maxiter=50,
+                             gtol=1e-5, ftol=1e-10, max_step=2.0):
+        """``optimize_batch`` for the reference kernel by a leave-one-out or hindcast score instead of nlML (``optimize_batch`` keeps refusing
+        those criteria for this kernel): X / y (/ M) are sequences of ragged data sets (n <= 128 rows each), theta0 [B, 2] or [2] ->
+        dict(x [B, 2], fun [B], jac [B, 2], nit [B], converged [B], nfev = launches).  Lockstep BFGS (``optim.bfgs_lockstep``) over
+        ``small_score_batch``: each round is ONE launch, one workgroup per data set, score and exact gradient formed in LDS."""
+        from .optim import bfgs_lockstep
+        if self.kernel != "netdiffusion":
+            raise ValueError("optimize_small_batch runs the reference kernel (RBF / Matern: optimize_batch, optimize_ard_batch, optimize_hindcast_batch)")
+        if criterion not in L.LOO_CRITERION_IDS and criterion not in L.HINDCAST_CRITERION_IDS:
+            raise ValueError("criterion must be 'loo_nlpd', 'loo_sse', 'hindcast_nlpd' or 'hindcast_sse' (block-CV gradients are not built for the reference kernel)")
+        self.upload_batch(X, y, None, M=M)
+        th0 = np.broadcast_to(np.asarray(theta0, dtype=np.float64), (len(self._small_ids), 2))
+        return bfgs_lockstep(lambda t: self.small_score_batch(t, criterion=criterion, lead=lead, min_train=min_train, sigma_f=sigma_f, expm=expm), th0,
+                             maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
 
     def nlml_grid(self, X, y, ells, sns, concurrency=2, group=8, M=None):
         """nlML on the (l, sn~) grid for one data set -- the offline 20x20 search implied by

@@ -144,7 +144,7 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
             gp.close()
 
 
-def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, gp=None, theta0=None, expm="eigh", **kw):
+def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, gp=None, theta0=None, expm="eigh", criterion="nlml", lead=1, min_train=2, **kw):
     """The optimiser call the reference left commented out (north/June1st.py:259-262, `minimize(MLII, x0, method='CG', jac=True)`
     with x0 = log of the script's table entries), re-enabled for EVERY (region, year) of the retro loop
     (September1st_retro.py:176-180) at once: each optimiser round is one device launch, one workgroup per (region, year), with
@@ -152,7 +152,15 @@ def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, 
     are not a derivative -- SURVEY App. C-7 -- and are available through ``nlml_batch(grad='ref')``).
     Returns {region: dict(x [n_years, 2] = (log l, log sn~), fun, nit, converged)} and ``nfev`` (device launches); with
     ``SIEs_trend`` also the forecast at each optimum in the reference's GPR-dict layout (``_fmean``, ``_fvar``, ``_fmean_rt``,
-    rounded as :241-244)."""
+    rounded as :241-244).
+
+    ``criterion`` = "loo_nlpd", "loo_sse", "hindcast_nlpd" or "hindcast_sse" minimises that score instead of nlML (``GPR.optimize_small_batch``:
+    lockstep BFGS, each round still one launch with the score and its exact gradient formed in LDS; ``lead`` / ``min_train`` as
+    ``retro_grid_search``, sigma_f re-profiled; ``sigma_f="fixed"`` and the optimiser's tolerances go through ``**kw``); each region's dict then
+    also carries ``jac``, the gradient at ``x``.  What is held fixed is what ``retro_grid_search`` holds fixed.  The leave-block-out scores
+    have no gradient in this kernel."""
+    if criterion != "nlml" and criterion not in ("loo_nlpd", "loo_sse", "hindcast_nlpd", "hindcast_sse"):
+        raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'hindcast_nlpd' or 'hindcast_sse' (block-CV gradients are not built for the reference kernel)")
     tab = SCRIPT_TABLE[script]
     own = gp is None
     gp = gp or GPR(kernel="netdiffusion")
@@ -166,11 +174,16 @@ def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, 
                 Xl.append(X); yl.append(y); Xsl.append(Xs); Ml.append(M)
                 x0.append([np.log(tab["ell"][k]), np.log(tab["sn"][k])])
         x0 = np.asarray(x0) if theta0 is None else np.broadcast_to(np.asarray(theta0, dtype=np.float64), (len(Xl), 2))
-        res = gp.optimize_batch(Xl, yl, x0, M=Ml, expm=expm, **kw)
+        if criterion == "nlml":
+            res = gp.optimize_batch(Xl, yl, x0, M=Ml, expm=expm, **kw)
+        else:
+            res = gp.optimize_small_batch(Xl, yl, x0, criterion=criterion, lead=lead, min_train=min_train, M=Ml, expm=expm, **kw)
         out = {"nfev": res["nfev"]}
         for k, region in enumerate(tab["regions"]):
             sl = slice(k * ny, (k + 1) * ny)
             out[region] = dict(x=res["x"][sl], fun=res["fun"][sl], nit=res["nit"][sl], converged=res["converged"][sl])
+            if criterion != "nlml":
+                out[region]["jac"] = res["jac"][sl]
         if SIEs_trend is not None:
             th = res["x"]
             r = gp.fit_batch(Xl, yl, Xsl, np.exp(th[:, 0]), np.exp(th[:, 1]), M=Ml)

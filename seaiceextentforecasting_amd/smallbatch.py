@@ -95,8 +95,9 @@ class SmallBatch:
         return len(self._fits) - 1
 
     # ---- device ---------------------------------------------------------------------------------------------------
-    def upload(self):
-        """Stage every data set queued so far in HBM (flat pools + offsets)."""
+    def upload(self, dweights=True):
+        """Stage every data set queued so far in HBM (flat pools + offsets).  ``dweights=False`` leaves out the M Sigma~ weights of the "pade"
+        sets (``sigp_small_set_dweights``): their d/d log l entries are then NaN."""
         sets = self._sets
         if not sets:
             raise RuntimeError("no fits queued")
@@ -113,7 +114,7 @@ class SmallBatch:
         gp = self.gp
         gp._check(gp._lib.sigp_small_upload(gp._h, len(sets), L.iptr(n), L.iptr(N), L.iptr(m), L.iptr(mode), L.ptr(A), L.iptr(a_off),
                                             L.ptr(y), L.iptr(y_off), L.ptr(lam), L.iptr(l_off)), "small_upload")
-        if mode.any():
+        if mode.any() and dweights:
             dlam = np.concatenate([s[4] for s in sets])
             gp._check(gp._lib.sigp_small_set_dweights(gp._h, L.ptr(dlam), len(dlam)), "small_set_dweights")
         self._uploaded = len(sets)
@@ -124,7 +125,7 @@ class SmallBatch:
         self._fits = []
         self._packed = None
 
-    def run(self, grad=False, loo=None, cv=None, hindcast=None):
+    def run(self, grad=False, loo=None, cv=None, hindcast=None, score_grad=None):
         """All queued fits in one launch -> dict(sigma_f, nlml, info, sigma_n, mean [F, mmax], var [F, mmax]); with ``grad=True``
         also grad_ref [F, 2] (the reference's MLII formulae, north/June1st.py:248-252) and grad_exact [F, 2] (the derivative of the
         profiled nlML w.r.t. (log l, log sn~)); +inf where K~ is not positive definite (:254-256).
@@ -148,7 +149,25 @@ class SmallBatch:
         instead (``sigp_small_run_hindcast``; rows and modes as ``GPR.hindcast``, lead <= 32, every data set must have a scored row:
         min_train + lead - 1 <= n - 1): hindcast_mean, hindcast_var [F, nmax] (NaN where a row is not scored and beyond a data set's n),
         hindcast_nlpd, hindcast_sse [F] (+inf / NaN rows where K~ is not positive definite).  L~ and z are read where the factorisation left
-        them; no inverse is formed.  Mutually exclusive with ``grad``, ``loo`` and ``cv``."""
+        them; no inverse is formed.  Mutually exclusive with ``grad``, ``loo`` and ``cv``.
+
+        ``score_grad="nlpd"`` / ``"sse"`` with ``loo=`` or ``hindcast=``: the same single launch also differentiates that score of every fit
+        with respect to (log l, log sn~), (l, sn~) held and sigma_f re-profiled as the mode says (``sigp_small_run_loo_grad`` /
+        ``sigp_small_run_hindcast_grad``): loo_grad / hindcast_grad [F, 2]; every other key carries the bytes of the launch without it (where no
+        data set has more features than the launch's feature chunk, as for ``cv``).  "pade" fits take d/d log l through the staged M Sigma~
+        weights, as ``grad=True`` does.  +inf where K~ is not positive definite.  The launch keeps more in LDS: every batch whose largest order
+        is <= 96 runs (any m <= 8, any lead <= 32); beyond that leave-one-out takes n <= 128 up to m = 6 and n <= 127 at m = 7, 8, the hindcast
+        at lead = 1 n <= 128 up to m = 5 and n <= 127 above, and at n = 128, m = 0 lead <= 6; what does not fit raises ValueError (the
+        library's SIGP_BAD_ARG, whose message names the bytes needed and the limit) and the batch still runs every other launch.  From order 97
+        on the launch may build K~ from shorter feature chunks than the score launch does: sets with more features than the chunk then agree
+        with it to rounding, not byte for byte.  Leave-block-out gradients are not built: ``cv=`` with ``score_grad`` raises."""
+        if score_grad is not None:
+            if cv is not None:
+                raise ValueError("score_grad: block-CV gradients are not built in the one-workgroup kernel (loo= and hindcast= have them)")
+            if score_grad not in ("nlpd", "sse"):
+                raise ValueError("score_grad must be None, 'nlpd' or 'sse'")
+            if loo is None and hindcast is None:
+                raise ValueError("score_grad differentiates a row score: pass loo= or hindcast= with it (grad=True is the nlML's gradient)")
         if hindcast is not None:
             if loo is not None or grad or cv is not None:
                 raise ValueError("one launch forms the gradients, the leave-one-out, the leave-block-out or the hindcast predictions: run them separately")
@@ -188,10 +207,14 @@ class SmallBatch:
         si, ell, sn = self._packed
         if hindcast is not None:
             flavour, extra = "hindcast", (hc_lead, hc_mt, L.LOO_MODES[hc_mode])
+            if score_grad is not None:
+                flavour, extra = "hindcast_grad", extra + (self._SCORE_IDS[score_grad],)
         elif cv is not None:
             flavour, extra = "cv", (cv_block, cv_gap, L.LOO_MODES[cv_mode])
         elif loo is not None:
             flavour, extra = "loo", (L.LOO_MODES[loo],)
+            if score_grad is not None:
+                flavour, extra = "loo_grad", extra + (self._SCORE_IDS[score_grad],)
         else:
             flavour, extra = ("grad" if grad else "plain"), ()
         prefix, fn, what, width = self._FLAVOURS[flavour]
@@ -211,7 +234,11 @@ class SmallBatch:
             res.update({prefix + "_mean": rmean, prefix + "_var": rvar, prefix + "_nlpd": out[:, 4].copy(), prefix + "_sse": out[:, 5].copy()})
         if grad:
             res["grad_ref"], res["grad_exact"] = out[:, 4:6].copy(), out[:, 6:8].copy()
+        if score_grad is not None:
+            res[prefix + "_grad"] = out[:, 6:8].copy()
         return res
+
+    _SCORE_IDS = {"nlpd": 0, "sse": 1}       # SIGP_LOO_NLPD / SIGP_LOO_SSE
 
     # flavour -> (prefix of its result keys, entry point (its arguments beyond the common ones go ahead of ``out``), the name errors carry,
     # doubles per fit of ``out``)
@@ -219,4 +246,6 @@ class SmallBatch:
                  "grad": (None, "sigp_small_run_grad", "small_run", 8),
                  "loo": ("loo", "sigp_small_run_loo", "small_run_loo", 6),
                  "cv": ("cv", "sigp_small_run_cv", "small_run_cv", 6),
-                 "hindcast": ("hindcast", "sigp_small_run_hindcast", "small_run_hindcast", 6)}
+                 "hindcast": ("hindcast", "sigp_small_run_hindcast", "small_run_hindcast", 6),
+                 "loo_grad": ("loo", "sigp_small_run_loo_grad", "small_run_loo_grad", 8),
+                 "hindcast_grad": ("hindcast", "sigp_small_run_hindcast_grad", "small_run_hindcast_grad", 8)}
