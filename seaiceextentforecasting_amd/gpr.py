@@ -28,6 +28,52 @@ class LinAlgError(np.linalg.LinAlgError):
         self.info = info
 
 
+# The validation-score families, one row each: the criteria and their ids, the normaliser of the family's own arguments (called as
+# ``args(gp, values, sigma_f, n, d)`` with n, d of the staged data or None; it refuses a bad ``sigma_f``, fold or window and returns the
+# values as the library takes them), the keywords those arguments go by, the library entries of the per-feature (ARD) call of one fit and
+# of a lockstep group, and the wording of the refusals: ``criteria`` for a criterion of another family, ``elsewhere`` what the group entry
+# adds to it, ``objective`` why ``<family>_objective`` refuses the reference kernel, ``optimize`` what ``optimize`` calls the family and
+# the reference kernel's way to its scores.  A fourth family is a row here, its ``<family>_ard`` / ``_ard_batch`` / ``_objective`` /
+# ``_objective_batch`` / ``optimize_<family>_batch`` methods (signature and docstring; the body is one call of ``_family_ard`` /
+# ``_common_scale`` / ``_family_objective_batch`` / ``_optimize_family_batch``) and its own arguments in ``optimize`` / ``optimize_ard``.
+_FAMILIES = {
+    "loo": dict(ids=L.LOO_CRITERION_IDS, args=None, params=(), ard="sigp_loo_grad_ard", ard_batch="sigp_loo_grad_ard_batch",
+                criteria="criterion must be 'loo_nlpd' or 'loo_sse'", elsewhere=" (the leave-block-out scores 'cv_nlpd' / 'cv_sse': cv_ard_batch)"),
+    "cv": dict(ids=L.CV_CRITERION_IDS, args=lambda gp, a, sigma_f, n, d: gp._cv_args(*a, sigma_f, n=n), params=("block", "gap"),
+               ard="sigp_cv_grad_ard", ard_batch="sigp_cv_grad_ard_batch",
+               criteria="criterion must be 'cv_nlpd' or 'cv_sse'", elsewhere=" (the leave-one-out scores: loo_ard_batch)",
+               objective="the reference kernel's leave-block-out scores have no gradient: cv_grid", optimize=("leave-block-out", "cv_grid")),
+    "hindcast": dict(ids=L.HINDCAST_CRITERION_IDS, args=lambda gp, a, sigma_f, n, d: gp._hindcast_args(*a, sigma_f, n, d), params=("lead", "min_train"),
+                     ard="sigp_hindcast_grad_ard", ard_batch="sigp_hindcast_grad_ard_batch",
+                     criteria="criterion must be 'hindcast_nlpd' or 'hindcast_sse'",
+                     elsewhere=" (the leave-one-out scores: loo_ard_batch, the leave-block-out scores: cv_ard_batch)",
+                     objective="the reference kernel's hindcast scores have no gradient", optimize=("hindcast", "hindcast after fit")),
+}
+_ALL_CRITERIA = "criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd', 'cv_sse', 'hindcast_nlpd' or 'hindcast_sse'"
+
+
+def _family_of(criterion):
+    """the name of the family ``criterion`` belongs to, None for 'nlml' and anything else"""
+    return next((name for name, fam in _FAMILIES.items() if criterion in fam["ids"]), None)
+
+
+def _check_sigma_f(sigma_f):
+    if sigma_f not in L.LOO_MODES:
+        raise ValueError("sigma_f must be 'refit' or 'fixed'")
+
+
+def _check_grad(grad, allowed=(None, "exact"), message=None):
+    if grad not in allowed:
+        raise ValueError(message or "grad must be None%s or 'exact'" % (", 'ref'" if "ref" in allowed else ""))
+
+
+def _finite_exp(theta):
+    """theta [F, 2] = (log l, log sn~) -> (l [F], sn~ [F], which rows can be evaluated: both finite and l > 0)"""
+    with np.errstate(over="ignore"):
+        ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
+    return ell, sn, np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
+
+
 class GPR:
     def __init__(self, kernel="netdiffusion", dtype="f64", device=0, outer_blocks=None, lookahead=None, schedule=None,
                  panel_mode=None, expm="pade", accurate=None):
@@ -78,6 +124,27 @@ class GPR:
         if rc == L.BAD_ARG:
             raise ValueError("%s: %s" % (what, msg))
         raise L.SigpError("%s: %s" % (what, msg))
+
+    def _require_data(self, what):
+        if not self._has_data:
+            raise RuntimeError("%s: no data staged; call fit() or set_data() first" % what)
+
+    def _require_ard_engine(self):
+        if self.kernel == "netdiffusion" or self.dtype != "f64":
+            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+
+    def _require_staged(self, what):
+        """d of the data sets of the lockstep batch"""
+        d = getattr(self, "_batch_d", None)
+        if d is None:
+            raise RuntimeError("%s: stage the data sets with upload_batch() first" % what)
+        return d
+
+    def _shape(self, batch=False):
+        """(n, d) of the staged data set (``batch``: of the lockstep batch's data sets), (None, None) before any is staged"""
+        if batch:
+            return getattr(self, "_batch_n", None), getattr(self, "_batch_d", None)
+        return (self.n, self.d) if getattr(self, "_has_data", False) else (None, None)
 
     def set_option(self, name, value):
         self._check(self._lib.sigp_set_option(self._h, name.encode(), int(value)), "set_option")
@@ -151,8 +218,7 @@ class GPR:
                 self._check(self._lib.sigp_set_length_scales(self._h, None, 0), "set_length_scales")
                 self._ard = False
             return None
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        self._require_ard_engine()
         vec = L.f64(np.asarray(ell, dtype=np.float64), 1).copy()
         if vec.shape[0] != self.d:
             raise ValueError("ell must be a scalar or hold one length scale per feature (%d), got %d" % (self.d, vec.shape[0]))
@@ -175,8 +241,7 @@ class GPR:
 
     def refit(self, ell, sn_tilde):
         """Fit again on the staged data with new hyper-parameters (grid search / optimiser loop)."""
-        if not self._has_data:
-            raise RuntimeError("refit: no data staged; call fit() or set_data() first")
+        self._require_data("refit")
         out = np.zeros(4)
         m = 0 if self._ride is None else self._ride.shape[0]
         mean = np.zeros(max(m, 1))
@@ -278,8 +343,7 @@ class GPR:
 
         ``grad=True`` (``sigp_loo_grad``) adds nlpd_grad [2] and sse_grad [2], the exact derivatives of the two scores with respect to
         (log l, log sn~); every other entry carries the same bits as without."""
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        _check_sigma_f(sigma_f)
         if not self._fitted:
             raise RuntimeError("loo: call fit() first")
         mean, var, score = np.zeros(self.n), np.zeros(self.n), np.zeros(2)
@@ -304,8 +368,7 @@ class GPR:
         lockstep groups of ``group`` fits (``sigp_loo_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F])
         and, with ``predictions``, mean [F, n], var [F, n]; a non-SPD member gets +inf / NaN (north/June1st.py:254-256).
         ``grad=True`` (``sigp_loo_grad_batch``) adds nlpd_grad [F, 2] and sse_grad [F, 2] with respect to (log l, log sn~)."""
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        _check_sigma_f(sigma_f)
         ell, sn, F, n, score, mean, var = self._batch_score_args("loo_batch", ell, sn_tilde, group, predictions)
         g4 = np.zeros((F, 4)) if grad else None
         if grad:
@@ -326,9 +389,8 @@ class GPR:
         F = len(ell)
         if len(sn) != F:
             raise ValueError("ell and sn_tilde must have the same length")
-        n = getattr(self, "_batch_n", None)
-        if n is None:
-            raise RuntimeError("%s: stage the data sets with upload_batch() first" % what)
+        self._require_staged(what)
+        n = self._batch_n
         self.set_option("group", group)
         return ell, sn, F, n, np.zeros((F, 2)), (np.zeros((F, n)) if predictions else None), (np.zeros((F, n)) if predictions else None)
 
@@ -345,8 +407,7 @@ class GPR:
     def loo_grid(self, X, y, ells, sns, sigma_f="refit", group=8, M=None):
         """The leave-one-out scores on the (l, sn~) grid for one data set, shaped like ``nlml_grid``: dict(nlpd, sse), each
         [len(ells), len(sns)], +inf where K~ is not SPD.  Reference kernel (n <= 128): one launch, one workgroup per grid point."""
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        _check_sigma_f(sigma_f)
         return self._score_grid(X, y, ells, sns, group, M, "loo", sigma_f, lambda E, S: self.loo_batch(E, S, sigma_f=sigma_f, group=group, predictions=False))
 
     def _score_grid(self, X, y, ells, sns, group, M, prefix, small_arg, batch):
@@ -370,13 +431,12 @@ class GPR:
         return dict(nlpd=nlpd.reshape(len(ells), len(sns)), sse=sse.reshape(len(ells), len(sns)))
 
     # ---- expanding-window hindcast validation ----------------------------------------------------
-    def _hindcast_args(self, lead, min_train, sigma_f, n=None, d=None):
+    def _hindcast_args(self, lead, min_train, sigma_f, n=None, d=None, max_lead=L.HINDCAST_MAX_LEAD):
         """the checks ``hindcast`` and its relatives share; ``min_train=None`` means max(2, d + 1).  Returns (lead, min_train)."""
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        _check_sigma_f(sigma_f)
         lead = int(lead)
-        if lead < 1 or lead > L.HINDCAST_MAX_LEAD:
-            raise ValueError("hindcast: 1 <= lead <= %d required" % L.HINDCAST_MAX_LEAD)
+        if lead < 1 or lead > max_lead:
+            raise ValueError("hindcast: 1 <= lead <= %d required" % max_lead)
         if min_train is None:
             min_train = 2 if d is None else max(2, d + 1)
         min_train = int(min_train)
@@ -400,8 +460,7 @@ class GPR:
         rows, scored = slice(min_train + lead - 1, n)) with skill = 1 - sse / sum((y - mean(y))^2) over the scored rows.  The fit stays as
         it is: ``predict`` / ``loo`` / ``cv`` afterwards work unchanged."""
         if not self._fitted:
-            if sigma_f not in L.LOO_MODES:
-                raise ValueError("sigma_f must be 'refit' or 'fixed'")
+            _check_sigma_f(sigma_f)
             raise RuntimeError("hindcast: call fit() first")
         lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n, self.d)
         mean, var, score = np.zeros(self.n), np.zeros(self.n), np.zeros(2)
@@ -422,7 +481,7 @@ class GPR:
         means max(2, d + 1) with d of the staged data sets, as in ``hindcast``."""
         if self.kernel == "netdiffusion":
             raise ValueError("hindcast_batch covers the RBF / Matern kernels; the reference kernel's batch is SmallBatch.run(hindcast=...)")
-        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, getattr(self, "_batch_n", None), getattr(self, "_batch_d", None))
+        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, *self._shape(batch=True))
         ell, sn, F, n, score, mean, var = self._batch_score_args("hindcast_batch", ell, sn_tilde, group, predictions)
         self._check(self._lib.sigp_hindcast_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), lead, min_train, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
                                                   L.ptr(score)), "hindcast_batch")
@@ -448,8 +507,7 @@ class GPR:
 
     @staticmethod
     def _cv_args(block, gap, sigma_f, max_window=L.CV_MAX_WINDOW, n=None):
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
+        _check_sigma_f(sigma_f)
         if int(block) != block or int(gap) != gap or block < 1 or gap < 0:
             raise ValueError("block >= 1 and gap >= 0 (integers) required")
         if block + 2 * gap > max_window:
@@ -490,7 +548,7 @@ class GPR:
         """``cv`` for many (data set, l, sn~) on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern), in lockstep groups
         of ``group`` fits (``sigp_cv_batch``): fit i uses data set (first + i) % B.  Returns dict(nlpd [F], sse [F]) and, with
         ``predictions``, mean [F, n], var [F, n]; a member whose K~ (or one of whose blocks of K~^-1) is not SPD gets +inf / NaN."""
-        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "_batch_n", None))
+        block, gap = self._cv_args(block, gap, sigma_f, n=self._shape(batch=True)[0])
         ell, sn, F, n, score, mean, var = self._batch_score_args("cv_batch", ell, sn_tilde, group, predictions)
         self._check(self._lib.sigp_cv_batch(self._h, int(first), F, self._kid, L.ptr(ell), L.ptr(sn), block, gap, L.LOO_MODES[sigma_f], L.ptr(mean), L.ptr(var), n,
                                             L.ptr(score)), "cv_batch")
@@ -516,10 +574,8 @@ class GPR:
         A non-SPD K~ or an overflowing exp(theta) gives ``(inf, [inf, inf])`` like the reference's except
         branch (:254-256).  Everything O(n^3) runs on the device (K13/K14: tr(K~^-1 dK~) from a lockstep
         forward block solve of the identity + one SYRK)."""
-        if not self._has_data:
-            raise RuntimeError("nlml: no data staged; call fit() or set_data() first")
-        if grad not in (None, "ref", "exact"):
-            raise ValueError("grad must be None, 'ref' or 'exact'")
+        self._require_data("nlml")
+        _check_grad(grad, (None, "ref", "exact"))
         if grad == "ref" and self.kernel != "netdiffusion":
             raise ValueError("grad='ref' is defined for the reference kernel only")
         theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(2), 1)
@@ -570,12 +626,9 @@ class GPR:
         library call -- ``call(theta, mean, var, score, g)`` returns its code and leaves the two scores (``nlml_ard``: the nlML) in ``score``,
         of which ``which`` is the value (None: ``nlml_ard``) --, the non-SPD branch and the handle's state afterwards.  Returns dict(value, grad,
         mean, var, nlpd, sse, spd)."""
-        if not self._has_data:
-            raise RuntimeError("%s: no data staged; call fit() or set_data() first" % what)
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        self._require_data(what)
+        _check_grad(grad)
+        self._require_ard_engine()
         theta = L.f64(np.asarray(theta, dtype=np.float64).reshape(-1), 1)
         if theta.shape[0] != self.d + 1:
             raise ValueError("theta must hold d + 1 = %d entries (log l_1 .. log l_d, log sn~), got %d" % (self.d + 1, theta.shape[0]))
@@ -618,14 +671,26 @@ class GPR:
         exp(theta) gives ``(inf, [inf] * (d + 1))``, like ``nlml_ard``.  ``predictions=True`` returns dict(value, grad, mean [n], var [n], nlpd,
         sse) instead: the bits ``loo(sigma_f)`` returns on that fit.  Afterwards the handle is fitted at exp(theta) with the scales set, as
         after ``nlml_ard``.  RBF / Matern, fp64."""
-        if criterion not in L.LOO_CRITERION_IDS:
-            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if grad not in (None, "exact"):                    # (here, not only in _ard_call: a wrong ``grad`` is refused before missing data)
-            raise ValueError("grad must be None or 'exact'")
-        r = self._ard_call("loo_ard", theta, grad, L.LOO_CRITERION_IDS[criterion], predictions, lambda th, mean, var, score, g: self._lib.sigp_loo_grad_ard(
-            self._h, self._kid, L.ptr(th), th.shape[0], L.LOO_MODES[sigma_f], L.LOO_CRITERION_IDS[criterion], L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
+        return self._family_ard("loo", theta, (), criterion, sigma_f, grad, predictions, sigma_f_first=True)
+
+    def _family_ard(self, family, theta, args, criterion, sigma_f, grad, predictions, sigma_f_first=False, first=None, group=None):
+        """``<family>_ard`` and, with ``first`` and ``group``, ``<family>_ard_batch`` behind their signatures: the refusals in the order each
+        entry has them -- the criterion, ``sigma_f`` (ahead of ``grad`` only with ``sigma_f_first``; otherwise with the family's arguments),
+        ``grad`` (here, not only in ``_ard_call``: a wrong ``grad`` is refused before missing data), the family's arguments ``args`` on the
+        staged data -- and then the family's library entry through ``_ard_call`` / ``_ard_score_batch``."""
+        fam, batch = _FAMILIES[family], first is not None
+        if criterion not in fam["ids"]:
+            raise ValueError(fam["criteria"] + (fam["elsewhere"] if batch else ""))
+        if sigma_f_first:
+            _check_sigma_f(sigma_f)
+        _check_grad(grad)
+        args = self._family_kw(family, args, sigma_f, *self._shape(batch)).values()
+        cid, mode = fam["ids"][criterion], L.LOO_MODES[sigma_f]
+        if batch:
+            return self._ard_score_batch(family + "_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: getattr(self._lib, fam["ard_batch"])(
+                self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, *args, mode, cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+        r = self._ard_call(family + "_ard", theta, grad, cid, predictions, lambda th, mean, var, score, g: getattr(self._lib, fam["ard"])(
+            self._h, self._kid, L.ptr(th), th.shape[0], *args, mode, cid, L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
         del r["spd"]
         return r if predictions else (r["value"], r["grad"])
 
@@ -638,15 +703,7 @@ class GPR:
         of K~^-1 is not SPD gives ``(inf, [inf] * (d + 1))``.  ``predictions=True`` returns dict(value, grad, mean [n], var [n], nlpd, sse)
         instead: the bits ``cv(block, gap, sigma_f)`` returns on that fit.  Afterwards the handle is fitted at exp(theta) with the scales set,
         as after ``loo_ard``.  RBF / Matern, fp64; block + 2 gap <= 128 and every fold must leave a training row."""
-        if criterion not in L.CV_CRITERION_IDS:
-            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse'")
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
-        r = self._ard_call("cv_ard", theta, grad, L.CV_CRITERION_IDS[criterion], predictions, lambda th, mean, var, score, g: self._lib.sigp_cv_grad_ard(
-            self._h, self._kid, L.ptr(th), th.shape[0], block, gap, L.LOO_MODES[sigma_f], L.CV_CRITERION_IDS[criterion], L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
-        del r["spd"]
-        return r if predictions else (r["value"], r["grad"])
+        return self._family_ard("cv", theta, (block, gap), criterion, sigma_f, grad, predictions)
 
     def hindcast_ard(self, theta, lead=1, min_train=None, criterion="hindcast_nlpd", sigma_f="refit", grad="exact", predictions=False):
         """An expanding-window hindcast score with per-feature (ARD) length scales as an optimiser's objective: theta = (log l_1 .. log l_d,
@@ -657,40 +714,38 @@ class GPR:
         ``(inf, [inf] * (d + 1))``.  ``predictions=True`` returns dict(value, grad, mean [n], var [n], nlpd, sse) instead: the bits
         ``hindcast`` returns on that fit.  ``min_train=None`` means max(2, d + 1).  Afterwards the handle is fitted at exp(theta) with the
         scales set, as after ``loo_ard``.  RBF / Matern, fp64."""
-        if criterion not in L.HINDCAST_CRITERION_IDS:
-            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse'")
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        has = getattr(self, "_has_data", False)
-        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n if has else None, self.d if has else None)
-        cid = L.HINDCAST_CRITERION_IDS[criterion]
-        r = self._ard_call("hindcast_ard", theta, grad, cid, predictions, lambda th, mean, var, score, g: self._lib.sigp_hindcast_grad_ard(
-            self._h, self._kid, L.ptr(th), th.shape[0], lead, min_train, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), L.ptr(score), L.ptr(g)))
-        del r["spd"]
-        return r if predictions else (r["value"], r["grad"])
+        return self._family_ard("hindcast", theta, (lead, min_train), criterion, sigma_f, grad, predictions)
+
+    def _family_kw(self, family, args, sigma_f, n, d):
+        """the family's own arguments as the keywords its methods take them by, refused or normalised for data of shape (n, d) (None, None:
+        nothing staged yet) by the family's normaliser -- which refuses a wrong ``sigma_f`` first"""
+        fam = _FAMILIES[family]
+        return dict(zip(fam["params"], fam["args"](self, args, sigma_f, n, d))) if fam["args"] else {}
+
+    def _common_scale(self, family, theta, args, criterion, sigma_f, grad="exact"):
+        """``<family>_ard`` over ONE common length scale: theta = (log l, log sn~) goes in as (log l x d, log sn~) and the gradient comes
+        back as d/dlog l = sum_k d/dlog l_k (None with ``grad=None``).  Before any data is staged theta goes in as it is, for
+        ``<family>_ard`` to refuse the call.  The reference kernel is refused first, in the words of ``<family>_objective``."""
+        fam = _FAMILIES[family]
+        if self.kernel == "netdiffusion":
+            raise ValueError("%s_objective covers the RBF / Matern kernels (%s)" % (family, fam["objective"]))
+        theta = np.asarray(theta, dtype=np.float64).reshape(2)
+        if getattr(self, "_has_data", False):
+            theta = np.concatenate([np.full(self.d, theta[0]), theta[1:]])
+        v, g = getattr(self, family + "_ard")(theta, criterion=criterion, sigma_f=sigma_f, grad=grad, **dict(zip(fam["params"], args)))
+        return v, (None if g is None else np.array([np.sum(g[:-1]), g[-1]]))
 
     def hindcast_objective(self, theta, lead=1, min_train=None, criterion="hindcast_nlpd", sigma_f="refit"):
         """A hindcast score as an optimiser's objective over ONE common length scale: theta = (log l, log sn~) -> (value, grad [2]).  It is
         ``hindcast_ard`` at equal scales with d/dlog l = sum_k d/dlog l_k, as ``cv_objective``.  RBF / Matern, fp64."""
-        if self.kernel == "netdiffusion":
-            raise ValueError("hindcast_objective covers the RBF / Matern kernels (the reference kernel's hindcast scores have no gradient)")
-        theta = np.asarray(theta, dtype=np.float64).reshape(2)
-        d = getattr(self, "d", None) if getattr(self, "_has_data", False) else None
-        v, g = self.hindcast_ard(theta if d is None else np.concatenate([np.full(d, theta[0]), theta[1:]]), lead=lead, min_train=min_train, criterion=criterion,
-                                 sigma_f=sigma_f)
-        return v, np.array([np.sum(g[:-1]), g[-1]])
+        return self._common_scale("hindcast", theta, (lead, min_train), criterion, sigma_f)
 
     def cv_objective(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit"):
         """A leave-block-out score as an optimiser's objective over ONE common length scale: theta = (log l, log sn~) -> (value, grad [2])
         with value = the ``criterion`` ('cv_nlpd' | 'cv_sse') of ``cv(block, gap, sigma_f)`` on the fit at exp(theta).  It is ``cv_ard`` at equal
         scales with d/dlog l = sum_k d/dlog l_k.  A non-SPD K~ or an overflowing exp(theta) gives ``(inf, [inf, inf])``.  Afterwards the
         handle is fitted at exp(theta), the scales set to the common l.  RBF / Matern, fp64."""
-        if self.kernel == "netdiffusion":
-            raise ValueError("cv_objective covers the RBF / Matern kernels (the reference kernel's leave-block-out scores have no gradient: cv_grid)")
-        theta = np.asarray(theta, dtype=np.float64).reshape(2)
-        d = getattr(self, "d", None) if getattr(self, "_has_data", False) else None
-        v, g = self.cv_ard(theta if d is None else np.concatenate([np.full(d, theta[0]), theta[1:]]), block, gap=gap, criterion=criterion, sigma_f=sigma_f)
-        return v, np.array([np.sum(g[:-1]), g[-1]])
+        return self._common_scale("cv", theta, (block, gap), criterion, sigma_f)
 
     def optimize_ard(self, theta0, criterion="nlml", sigma_f="refit", method="L-BFGS-B", grad="exact", block=5, gap=0, lead=1, min_train=None, **kw):
         """Minimise ``criterion`` over one length scale per feature and the noise: 'nlml' (``nlml_ard``; what ``optimize(ard=True)`` does),
@@ -702,49 +757,49 @@ class GPR:
         training set.  ``theta0`` = (log l_1 .. log l_d, log sn~), or (log l, log sn~)
         with log l broadcast to every feature; ``grad`` 'exact' or None (SciPy then differences the value).  ``bounds`` and the other keywords
         go to SciPy as they are.  Returns the scipy ``OptimizeResult``; afterwards the handle is fitted at ``exp(result.x)``."""
-        from scipy.optimize import minimize
+        family = _family_of(criterion)
+        if criterion != "nlml" and family is None:
+            raise ValueError(_ALL_CRITERIA)
+        _check_sigma_f(sigma_f)
+        _check_grad(grad, message="optimize_ard takes grad='exact' or None")
+        if family is None:
+            return self._minimize_ard("optimize_ard", lambda th: self.nlml_ard(th, grad=grad), theta0, method, grad, kw)
+        own = self._family_kw(family, dict(loo=(), cv=(block, gap), hindcast=(lead, min_train))[family], sigma_f, *self._shape())
+        if own:                        # (the leave-one-out scores leave the engine to ``loo_ard``, behind the staged data)
+            self._require_ard_engine()
+        return self._minimize_ard("optimize_ard", lambda th: getattr(self, family + "_ard")(th, criterion=criterion, sigma_f=sigma_f, grad=grad, **own), theta0, method, grad, kw)
 
-        if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS and criterion not in L.CV_CRITERION_IDS and criterion not in L.HINDCAST_CRITERION_IDS:
-            raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd', 'cv_sse', 'hindcast_nlpd' or 'hindcast_sse'")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if grad not in (None, "exact"):
-            raise ValueError("optimize_ard takes grad='exact' or None")
-        if criterion in L.HINDCAST_CRITERION_IDS:
-            has = getattr(self, "_has_data", False)
-            lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n if has else None, self.d if has else None)
-            if self.kernel == "netdiffusion" or self.dtype != "f64":
-                raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        if criterion in L.CV_CRITERION_IDS:
-            block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
-            if self.kernel == "netdiffusion" or self.dtype != "f64":
-                raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        if not self._has_data:
-            raise RuntimeError("optimize_ard: no data staged; call fit() or set_data() first")
+    def _minimize_ard(self, what, objective, theta0, method, grad, kw):
+        """``optimize_ard`` and ``optimize(ard=True)`` behind their own refusals: the staged data, ``theta0`` as d + 1 entries, the minimiser"""
+        self._require_data(what)
         th0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
         if th0.shape[0] == 2 and self.d != 1:
             th0 = np.concatenate([np.full(self.d, th0[0]), th0[1:]])
         if th0.shape[0] != self.d + 1:
             raise ValueError("theta0 must hold d + 1 = %d entries, or 2 (log l is broadcast)" % (self.d + 1))
-        if criterion == "nlml":
-            objective = lambda th: self.nlml_ard(th, grad=grad)
-        elif criterion in L.CV_CRITERION_IDS:
-            objective = lambda th: self.cv_ard(th, block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad=grad)
-        elif criterion in L.HINDCAST_CRITERION_IDS:
-            objective = lambda th: self.hindcast_ard(th, lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f, grad=grad)
-        else:
-            objective = lambda th: self.loo_ard(th, criterion=criterion, sigma_f=sigma_f, grad=grad)
+        return self._minimize(objective, th0, method, grad, kw, ard=True)
+
+    def _minimize(self, objective, th0, method, grad, kw, ard=False):
+        """The tail of ``optimize`` and ``optimize_ard``: SciPy's ``minimize`` on ``objective(theta) -> (value, grad)`` (``grad=None``: on the
+        value alone, SciPy differences it) and the refit at exp(result.x) -- by ``_exp`` for per-feature results, whose fits the library
+        made at the C library's exp, by NumPy's for (log l, log sn~), as ``nlml`` and ``loo_objective`` form it: the two can differ in the
+        last bit."""
+        from scipy.optimize import minimize
+
         if grad is None:
             res = minimize(lambda th: float(objective(th)[0]), th0, method=method, jac=False, **kw)
         else:
-            def fun_ard(th):
+            def fun(th):
                 v, g = objective(th)
                 return float(v), np.asarray(g, dtype=np.float64)
 
-            res = minimize(fun_ard, th0, method=method, jac=True, **kw)
+            res = minimize(fun, th0, method=method, jac=True, **kw)
         if np.all(np.isfinite(res.x)):
             try:
-                self.refit(self._exp(res.x[:-1]), float(self._exp(res.x[-1:])[0]))
+                if ard:
+                    self.refit(self._exp(res.x[:-1]), float(self._exp(res.x[-1:])[0]))
+                else:
+                    self.refit(float(np.exp(res.x[0])), float(np.exp(res.x[1])))
             except LinAlgError:
                 pass
         return res
@@ -755,11 +810,9 @@ class GPR:
         exp(theta), and its exact gradient (``loo(grad=True)``).  A non-SPD K~ or an overflowing exp(theta) gives ``(inf, [inf, inf])``,
         like ``nlml``.  Afterwards the handle is fitted at exp(theta)."""
         if criterion not in L.LOO_CRITERIA:
-            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse'")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if not self._has_data:
-            raise RuntimeError("loo_objective: no data staged; call fit() or set_data() first")
+            raise ValueError(_FAMILIES["loo"]["criteria"])
+        _check_sigma_f(sigma_f)
+        self._require_data("loo_objective")
         theta = np.asarray(theta, dtype=np.float64).reshape(2)
         inf2 = (np.inf, np.asarray([np.inf, np.inf]))
         with np.errstate(over="ignore"):
@@ -789,100 +842,36 @@ class GPR:
         ``ard=True``: one length scale per feature, by ``nlml_ard``'s exact gradient -- ``theta0`` = (log l_1 .. log l_d, log sn~), or
         (log l, log sn~) with log l broadcast to every feature; ``criterion`` must be 'nlml' here (``optimize_ard`` takes the others); the relevance of feature k is read from
         ``result.x[k]`` (a large log l_k: the feature does not matter).  ``bounds`` and the other keywords go to SciPy as they are."""
-        from scipy.optimize import minimize
-
         if ard:
             if criterion != "nlml":
                 raise ValueError("ard=True: criterion must be 'nlml' (optimize_ard minimises the leave-one-out, leave-block-out and hindcast scores -- loo_ard, cv_ard, hindcast_ard -- over per-feature scales)")
-            if grad not in (None, "exact"):
-                raise ValueError("ard=True takes grad='exact' or None")
-            if not self._has_data:
-                raise RuntimeError("optimize: no data staged; call fit() or set_data() first")
-            th0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
-            if th0.shape[0] == 2 and self.d != 1:
-                th0 = np.concatenate([np.full(self.d, th0[0]), th0[1:]])
-            if th0.shape[0] != self.d + 1:
-                raise ValueError("theta0 must hold d + 1 = %d entries, or 2 (log l is broadcast)" % (self.d + 1))
+            _check_grad(grad, message="ard=True takes grad='exact' or None")
+            return self._minimize_ard("optimize", lambda th: self.nlml_ard(th, grad=grad), theta0, method, grad, kw)
+        family = _family_of(criterion)
+        if family in ("cv", "hindcast"):
+            fam, names = _FAMILIES[family], "criterion '%s_nlpd' / '%s_sse'" % (family, family)
+            _check_grad(grad, message="a %s criterion takes grad='exact' or None" % fam["optimize"][0])
+            if self.kernel == "netdiffusion":
+                raise ValueError("%s covers the RBF / Matern kernels (the reference kernel: %s)" % (names, fam["optimize"][1]))
+            if self.dtype != "f64":
+                raise ValueError("%s: fp64 engine only" % names)
+            own = self._family_kw(family, dict(cv=(block, gap), hindcast=(lead, min_train))[family], sigma_f, *self._shape())
+            self._require_data("optimize")
+            th0 = np.asarray(theta0, dtype=np.float64).reshape(2)
             if grad is None:
-                res = minimize(lambda th: float(self.nlml_ard(th, grad=None)[0]), th0, method=method, jac=False, **kw)
+                objective = lambda th: self._common_scale(family, th, own.values(), criterion, sigma_f, grad=None)
             else:
-                def fun_ard(th):
-                    v, g = self.nlml_ard(th, grad="exact")
-                    return float(v), np.asarray(g, dtype=np.float64)
-
-                res = minimize(fun_ard, th0, method=method, jac=True, **kw)
-            if np.all(np.isfinite(res.x)):
-                try:
-                    self.refit(self._exp(res.x[:-1]), float(self._exp(res.x[-1:])[0]))
-                except LinAlgError:
-                    pass
-            return res
-
-        if criterion in L.CV_CRITERION_IDS:
-            if grad not in (None, "exact"):
-                raise ValueError("a leave-block-out criterion takes grad='exact' or None")
-            if self.kernel == "netdiffusion":
-                raise ValueError("criterion 'cv_nlpd' / 'cv_sse' covers the RBF / Matern kernels (the reference kernel: cv_grid)")
-            if self.dtype != "f64":
-                raise ValueError("criterion 'cv_nlpd' / 'cv_sse': fp64 engine only")
-            block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "n", None) if getattr(self, "_has_data", False) else None)
-            if not self._has_data:
-                raise RuntimeError("optimize: no data staged; call fit() or set_data() first")
-            th0 = np.asarray(theta0, dtype=np.float64).reshape(2)
-
-            def fun(th):
-                if grad is None:
-                    return float(self.cv_ard(np.concatenate([np.full(self.d, th[0]), th[1:]]), block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad=None)[0])
-                v, g = self.cv_objective(th, block, gap=gap, criterion=criterion, sigma_f=sigma_f)
-                return float(v), np.asarray(g, dtype=np.float64)
-
-            res = minimize(fun, th0, method=method, jac=grad is not None, **kw)
-        elif criterion in L.HINDCAST_CRITERION_IDS:
-            if grad not in (None, "exact"):
-                raise ValueError("a hindcast criterion takes grad='exact' or None")
-            if self.kernel == "netdiffusion":
-                raise ValueError("criterion 'hindcast_nlpd' / 'hindcast_sse' covers the RBF / Matern kernels (the reference kernel: hindcast after fit)")
-            if self.dtype != "f64":
-                raise ValueError("criterion 'hindcast_nlpd' / 'hindcast_sse': fp64 engine only")
-            has = getattr(self, "_has_data", False)
-            lead, min_train = self._hindcast_args(lead, min_train, sigma_f, self.n if has else None, self.d if has else None)
-            if not self._has_data:
-                raise RuntimeError("optimize: no data staged; call fit() or set_data() first")
-            th0 = np.asarray(theta0, dtype=np.float64).reshape(2)
-
-            def fun(th):
-                if grad is None:
-                    return float(self.hindcast_ard(np.concatenate([np.full(self.d, th[0]), th[1:]]), lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f,
-                                                   grad=None)[0])
-                v, g = self.hindcast_objective(th, lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f)
-                return float(v), np.asarray(g, dtype=np.float64)
-
-            res = minimize(fun, th0, method=method, jac=grad is not None, **kw)
+                objective = lambda th: getattr(self, family + "_objective")(th, criterion=criterion, sigma_f=sigma_f, **own)
         elif criterion != "nlml":
-            if criterion not in L.LOO_CRITERIA:
-                raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'cv_nlpd', 'cv_sse', 'hindcast_nlpd' or 'hindcast_sse'")
-            if grad not in (None, "exact"):
-                raise ValueError("a leave-one-out criterion takes grad='exact' or None")
-
-            def fun(th):
-                v, g = self.loo_objective(th, criterion, sigma_f)
-                return (float(v), np.asarray(g, dtype=np.float64)) if grad is not None else float(v)
-
-            res = minimize(fun, np.asarray(theta0, dtype=np.float64), method=method, jac=grad is not None, **kw)
-        elif grad is None:                  # value only: scipy differences it numerically
-            res = minimize(lambda th: float(self.nlml(th, grad=None)[0]), np.asarray(theta0, dtype=np.float64), method=method, jac=False, **kw)
+            if family is None:
+                raise ValueError(_ALL_CRITERIA)
+            _check_grad(grad, message="a leave-one-out criterion takes grad='exact' or None")
+            th0 = np.asarray(theta0, dtype=np.float64)
+            objective = lambda th: self.loo_objective(th, criterion, sigma_f)
         else:
-            def fun(th):
-                v, g = self.nlml(th, grad=grad)
-                return float(v), np.asarray(g, dtype=np.float64)
-
-            res = minimize(fun, np.asarray(theta0, dtype=np.float64), method=method, jac=True, **kw)
-        if np.all(np.isfinite(res.x)):
-            try:
-                self.refit(float(np.exp(res.x[0])), float(np.exp(res.x[1])))
-            except LinAlgError:
-                pass
-        return res
+            th0 = np.asarray(theta0, dtype=np.float64)
+            objective = lambda th: self.nlml(th, grad=grad)             # grad=None: value only, SciPy differences it numerically
+        return self._minimize(objective, th0, method, grad, kw)
 
     # ---- state accessors -----------------------------------------------------------------------
     def _stat(self, name):
@@ -1119,33 +1108,11 @@ class GPR:
             raise ValueError("theta must be [F, 2]")
         F = theta.shape[0]
         if self.kernel == "netdiffusion":
-            if grad not in (None, "ref", "exact"):
-                raise ValueError("grad must be None, 'ref' or 'exact'")
-            sb = getattr(self, "_small", None)
-            if sb is None:
-                raise RuntimeError("nlml_batch: stage the data sets with upload_batch(X_list, y_list, Xs_list, M=M_list) first")
-            B = len(self._small_ids)
-            with np.errstate(over="ignore"):
-                ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
-            ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
-            val = np.full(F, np.inf)
-            g = np.full((F, 2), np.inf)
-            sb.clear_fits()
-            run = []
-            for i in np.flatnonzero(ok):
-                try:
-                    sb.add_fit(self._small_ids[(first + i) % B if sets is None else int(sets[i])], ell[i], sn[i], expm=expm)
-                    run.append(i)
-                except (FloatingPointError, OverflowError, ValueError):       # scipy's expm overflowed: the except branch of :254-256
-                    pass
-            if run:
-                r = sb.run(grad=grad is not None)
-                val[run] = r["nlml"]
-                if grad is not None:
-                    g[run] = r["grad_ref" if grad == "ref" else "grad_exact"]
+            _check_grad(grad, (None, "ref", "exact"))
+            val, g = self._small_run(self._small_staged("nlml_batch"), theta, first, sets, expm, "nlml", {None: None, "ref": "grad_ref", "exact": "grad_exact"}[grad],
+                                     grad=grad is not None)
             return val, (g if grad is not None else None)
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
+        _check_grad(grad)
         if sets is not None:
             raise ValueError("sets= is for the reference kernel's ragged data sets; the lockstep groups pair theta i with data set (first + i) % B")
         self.set_option("group", group)
@@ -1164,13 +1131,9 @@ class GPR:
         members at once.  Returns (nlml [F], grad [F, d + 1] or None); a fit whose K~ is not SPD or whose exp(theta) overflows gets +inf in
         its value and all its gradient entries, its group mates are unaffected.  The gradient pass is ``nlml_ard``'s own code: where the lockstep factorisation has the single fit's bits
         (small orders), every fit carries the bits ``nlml_ard`` returns for it."""
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        d = getattr(self, "_batch_d", None)
-        if d is None:
-            raise RuntimeError("nlml_ard_batch: stage the data sets with upload_batch() first")
+        _check_grad(grad)
+        self._require_ard_engine()
+        d = self._require_staged("nlml_ard_batch")
         theta = L.f64(np.atleast_2d(theta), 2)
         if theta.shape[1] != d + 1:
             raise ValueError("theta must be [F, d + 1] = [F, %d] (log l_1 .. log l_d, log sn~), got %s" % (d + 1, theta.shape))
@@ -1194,24 +1157,13 @@ class GPR:
         is not SPD or whose exp(theta) overflows gets +inf in its value, both scores and all its gradient entries and NaN predictions; its
         group mates are unaffected.  The gradient pass is ``loo_ard``'s own code: where the lockstep factorisation has the single fit's
         bits (small orders), every fit carries the bits ``loo_ard`` returns for it."""
-        if criterion not in L.LOO_CRITERION_IDS:
-            raise ValueError("criterion must be 'loo_nlpd' or 'loo_sse' (the leave-block-out scores 'cv_nlpd' / 'cv_sse': cv_ard_batch)")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        cid = L.LOO_CRITERION_IDS[criterion]
-        return self._ard_score_batch("loo_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: self._lib.sigp_loo_grad_ard_batch(
-            self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+        return self._family_ard("loo", theta, (), criterion, sigma_f, grad, predictions, sigma_f_first=True, first=first, group=group)
 
     def _ard_score_batch(self, what, theta, grad, group, predictions, cid, call):
         """What ``loo_ard_batch``, ``cv_ard_batch`` and ``hindcast_ard_batch`` share after their own checks: the kernel / engine, the staged data, theta's width -- all
         before any device call -- then the buffers, ``call(theta, F, d, n, mean, var, score, grad)`` and the result."""
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        d, n = getattr(self, "_batch_d", None), getattr(self, "_batch_n", None)
-        if d is None:
-            raise RuntimeError("%s: stage the data sets with upload_batch() first" % what)
+        self._require_ard_engine()
+        d, n = self._require_staged(what), self._batch_n
         theta = L.f64(np.atleast_2d(theta), 2)
         if theta.shape[1] != d + 1:
             raise ValueError("theta must be [F, d + 1] = [F, %d] (log l_1 .. log l_d, log sn~), got %s" % (d + 1, theta.shape))
@@ -1242,43 +1194,45 @@ class GPR:
         ascending fold order however a group splits them into passes, and the gradient pass is ``cv_ard``'s own code: where the lockstep
         factorisation has the single fit's bits (small orders), every fit carries the bits ``cv_ard`` returns for it.
         block + 2 gap <= 128 and every fold must leave a training row."""
-        if criterion not in L.CV_CRITERION_IDS:
-            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse' (the leave-one-out scores: loo_ard_batch)")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "_batch_n", None))
-        cid = L.CV_CRITERION_IDS[criterion]
-        return self._ard_score_batch("cv_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: self._lib.sigp_cv_grad_ard_batch(
-            self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, block, gap, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+        return self._family_ard("cv", theta, (block, gap), criterion, sigma_f, grad, predictions, sigma_f_first=True, first=first, group=group)
+
+    def _common_scale_batch(self, theta, evaluate, d=None):
+        """An objective over ONE common length scale for theta [F, 2] = (log l, log sn~) per fit -> (value [F], grad [F, 2]) in one device
+        call.  A fit whose exp(theta) is not finite rides along at harmless parameters; it, and any whose value or gradient is not finite,
+        gets inf in its value and both gradient entries.  With ``d``: ``evaluate(theta [F, d + 1]) -> (value, grad [F, d + 1])`` is a
+        per-feature objective, called at (log l x d, log sn~) and reduced by d/dlog l = sum_k d/dlog l_k, row by row as
+        ``_common_scale`` adds them.  Without: ``evaluate(l [F], sn~ [F]) -> (value, grad [F, 2])``."""
+        ell, sn, ok = _finite_exp(theta)
+        if d is None:
+            f, g = evaluate(np.where(ok, ell, 1.0), np.where(ok, sn, 1.0))
+        else:
+            f, g = evaluate(np.where(ok[:, None], np.concatenate([np.repeat(theta[:, :1], d, axis=1), theta[:, 1:]], axis=1), 0.0))
+            f, g = np.array(f, dtype=np.float64), np.array([[np.sum(gi[:-1]), gi[-1]] for gi in g])
+        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
+        f[~ok] = np.inf
+        g[~ok] = np.inf
+        return f, g
+
+    def _family_objective_batch(self, family, theta, args, first, criterion, sigma_f, group):
+        """``cv_objective_batch`` and ``hindcast_objective_batch`` behind their signatures: the refusals in their order, then
+        ``<family>_ard_batch`` through ``_common_scale_batch``"""
+        fam = _FAMILIES[family]
+        if criterion not in fam["ids"]:
+            raise ValueError(fam["criteria"])
+        own = self._family_kw(family, args, sigma_f, *self._shape(batch=True))
+        self._require_ard_engine()
+        d = self._require_staged(family + "_objective_batch")
+        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+        if theta.ndim != 2 or theta.shape[1] != 2:
+            raise ValueError("theta must be [F, 2] = (log l, log sn~) per fit, got %s" % (theta.shape,))
+        return self._common_scale_batch(theta, lambda th: getattr(self, family + "_ard_batch")(th, first=first, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group, **own), d)
 
     def cv_objective_batch(self, theta, block, gap=0, first=0, criterion="cv_nlpd", sigma_f="refit", group=8):
         """A leave-block-out score over ONE common length scale for many fits in one device call: theta [F, 2] = (log l, log sn~) per fit
         -> (value [F], grad [F, 2]).  It is ``cv_ard_batch`` at equal scales with d/dlog l = sum_k d/dlog l_k: per fit the bits
         ``cv_objective`` returns for it where ``cv_ard_batch`` carries ``cv_ard``'s.  A fit whose exp(theta) is not finite (it rides along at
         harmless parameters) or whose K~ is not SPD gets inf in its value and both gradient entries."""
-        if criterion not in L.CV_CRITERION_IDS:
-            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse'")
-        block, gap = self._cv_args(block, gap, sigma_f, n=getattr(self, "_batch_n", None))
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        d = getattr(self, "_batch_d", None)
-        if d is None:
-            raise RuntimeError("cv_objective_batch: stage the data sets with upload_batch() first")
-        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
-        if theta.ndim != 2 or theta.shape[1] != 2:
-            raise ValueError("theta must be [F, 2] = (log l, log sn~) per fit, got %s" % (theta.shape,))
-        with np.errstate(over="ignore"):
-            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
-        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
-        th = np.where(ok[:, None], np.concatenate([np.repeat(theta[:, :1], d, axis=1), theta[:, 1:]], axis=1), 0.0)
-        f, g = self.cv_ard_batch(th, block, gap=gap, first=first, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group)
-        f, g = np.array(f, dtype=np.float64), np.array([[np.sum(gi[:-1]), gi[-1]] for gi in g])       # row by row, as cv_objective adds them
-        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
-        f[~ok] = np.inf
-        g[~ok] = np.inf
-        return f, g
+        return self._family_objective_batch("cv", theta, (block, gap), first, criterion, sigma_f, group)
 
     def optimize_ard_batch(self, X, y, theta0, criterion="loo_nlpd", sigma_f="refit", group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0):
         """``optimize_ard`` for EVERY data set of a retrospective run at once: X [B, n, d], y [B, n] -> dict(x [F, d + 1], fun [F], nit [F],
@@ -1289,36 +1243,50 @@ class GPR:
         [F, d + 1], [d + 1], [F, 2] or [2] (the common log l is repeated for all d features); F = S B rows are S starts per data set, start
         i on data set i % B, and all F results come back.  RBF / Matern, fp64.  The leave-block-out scores in lockstep:
         ``optimize_cv_batch``."""
-        from .optim import bfgs_lockstep
         if criterion != "nlml" and criterion not in L.LOO_CRITERION_IDS:
             raise ValueError("criterion must be 'nlml', 'loo_nlpd' or 'loo_sse' (the leave-block-out scores 'cv_nlpd' / 'cv_sse': optimize_cv_batch)")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
+        bfgs = dict(maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
         if criterion == "nlml":
-            return self.optimize_batch(X, y, theta0, group=group, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step, ard=True)
+            _check_sigma_f(sigma_f)
+            self._require_ard_engine()
+            return self.optimize_batch(X, y, theta0, group=group, ard=True, **bfgs)
+        return self._optimize_family_batch("loo", X, y, theta0, (), criterion, sigma_f, True, group, bfgs)
+
+    def _optimize_family_batch(self, family, X, y, theta0, args, criterion, sigma_f, ard, group, bfgs):
+        """``optimize_ard_batch``, ``optimize_cv_batch`` and ``optimize_hindcast_batch`` behind their refusal of another family's criterion:
+        the remaining refusals (``sigma_f``, the engine, the family's arguments on X's shape, the starts -- all before the upload), the
+        upload, and the lockstep BFGS on ``<family>_ard_batch`` (``ard``) or ``<family>_objective_batch``"""
+        from .optim import bfgs_lockstep
+        _check_sigma_f(sigma_f)
+        self._require_ard_engine()
         X = L.f64(X, 3)
-        B, d = X.shape[0], X.shape[2]
-        th0 = self._ard_starts(theta0, B, d)
+        B, n, d = X.shape
+        own = self._family_kw(family, args, sigma_f, n, d)
+        th0 = self._starts(theta0, B, d + 1, d) if ard else self._starts(theta0, B, 2)
         self.upload_batch(X, y, None, group=group, concurrency=1)
-        return bfgs_lockstep(lambda t: self.loo_ard_batch(t, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol,
-                             ftol=ftol, max_step=max_step)
+        objective = getattr(self, family + ("_ard_batch" if ard else "_objective_batch"))
+        return bfgs_lockstep(lambda t: objective(t, criterion=criterion, sigma_f=sigma_f, group=group, **own), th0, **bfgs)
+
+    @staticmethod
+    def _starts(theta0, B, p, d=None, refuse=True):
+        """theta0 -> the starts [F, p] of a lockstep run on B data sets: F = S B rows are S starts per data set (start i on data set
+        i % B), anything else is broadcast to one start per data set.  With ``d`` (per-feature scales, p = d + 1) theta0 may be [F, 2] or
+        [2] as well: the common log l is repeated for every feature.  ``refuse=False`` leaves a theta0 of another width to NumPy's
+        ``broadcast_to`` (``optimize_batch`` over two parameters)."""
+        th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
+        if d is not None and th0.ndim == 2 and th0.shape[1] == 2 and d != 1:      # (log l, log sn~): the common log l for every feature
+            th0 = np.concatenate([np.repeat(th0[:, :1], d, axis=1), th0[:, 1:]], axis=1)
+        if refuse and (th0.ndim != 2 or th0.shape[1] != p):
+            raise ValueError("theta0 must hold 2 entries per start (log l, log sn~) with ard=False" if d is None else
+                             "theta0 must hold d + 1 = %d entries per start, or 2 (log l is repeated for every feature)" % p)
+        if th0.ndim == 2 and th0.shape[0] != B and th0.shape[1] == p and th0.shape[0] % B == 0:
+            return np.array(th0)                                  # S starts per data set: start i uses data set i % B
+        return np.broadcast_to(th0[0] if th0.ndim == 2 and th0.shape[0] == 1 else th0, (B, p))
 
     @staticmethod
     def _ard_starts(theta0, B, d):
-        """theta0 [F, d + 1], [d + 1], [F, 2] or [2] -> the starts [F, d + 1] of a lockstep run over per-feature scales on B data sets: the
-        common log l repeated for every feature; F = S B rows are S starts per data set (start i on data set i % B), anything else is
-        broadcast to one start per data set."""
-        p = d + 1
-        th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
-        if th0.ndim == 2 and th0.shape[1] == 2 and d != 1:      # (log l, log sn~): the common log l for every feature
-            th0 = np.concatenate([np.repeat(th0[:, :1], d, axis=1), th0[:, 1:]], axis=1)
-        if th0.ndim != 2 or th0.shape[1] != p:
-            raise ValueError("theta0 must hold d + 1 = %d entries per start, or 2 (log l is repeated for every feature)" % p)
-        if th0.shape[0] != B and th0.shape[0] % B == 0:
-            return np.array(th0)                                  # S starts per data set: start i uses data set i % B
-        return np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, p))
+        """``_starts`` over per-feature scales: theta0 [F, d + 1], [d + 1], [F, 2] or [2] -> [F, d + 1]"""
+        return GPR._starts(theta0, B, d + 1, d)
 
     def optimize_cv_batch(self, X, y, theta0, block, gap=0, criterion="cv_nlpd", sigma_f="refit", ard=True, group=8, maxiter=50, gtol=1e-5, ftol=1e-10,
                           max_step=2.0):
@@ -1332,29 +1300,9 @@ class GPR:
         repeated for all d features), as ``optimize_ard_batch`` takes it; F = S B rows are S starts per data set, start i on data set
         i % B, and all F results come back.  ``ard=False``: one common length scale (``cv_objective_batch``), ``theta0`` [2] or [F, 2],
         x [F, 2].  RBF / Matern, fp64; block + 2 gap <= 128 and every fold must leave a training row."""
-        from .optim import bfgs_lockstep
         if criterion not in L.CV_CRITERION_IDS:
-            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse' (the leave-one-out scores and 'nlml': optimize_ard_batch)")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        X = L.f64(X, 3)
-        B, n, d = X.shape
-        block, gap = self._cv_args(block, gap, sigma_f, n=n)
-        if ard:
-            th0 = self._ard_starts(theta0, B, d)
-        else:
-            th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
-            if th0.ndim != 2 or th0.shape[1] != 2:
-                raise ValueError("theta0 must hold 2 entries per start (log l, log sn~) with ard=False")
-            th0 = np.array(th0) if th0.shape[0] != B and th0.shape[0] % B == 0 else np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, 2))
-        self.upload_batch(X, y, None, group=group, concurrency=1)
-        if ard:
-            return bfgs_lockstep(lambda t: self.cv_ard_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group), th0, maxiter=maxiter,
-                                 gtol=gtol, ftol=ftol, max_step=max_step)
-        return bfgs_lockstep(lambda t: self.cv_objective_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, group=group), th0, maxiter=maxiter, gtol=gtol,
-                             ftol=ftol, max_step=max_step)
+            raise ValueError(_FAMILIES["cv"]["criteria"] + " (the leave-one-out scores and 'nlml': optimize_ard_batch)")
+        return self._optimize_family_batch("cv", X, y, theta0, (block, gap), criterion, sigma_f, ard, group, dict(maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step))
 
     def hindcast_ard_batch(self, theta, lead=1, min_train=None, first=0, criterion="hindcast_nlpd", sigma_f="refit", grad="exact", group=8, predictions=False):
         """``hindcast_ard`` for many fits in one device call on the data sets staged by ``upload_batch`` / ``fit_batch`` (RBF / Matern, fp64):
@@ -1369,41 +1317,14 @@ class GPR:
         predictions; its group mates are unaffected.  The gradient pass forms every number by ``hindcast_ard``'s own chain of operations:
         where the lockstep factorisation has the single fit's bits (small orders), every fit carries the bits ``hindcast_ard`` returns for
         it.  ``min_train=None`` means max(2, d + 1) with d of the staged data sets, as in ``hindcast_batch``."""
-        if criterion not in L.HINDCAST_CRITERION_IDS:
-            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse' (the leave-one-out scores: loo_ard_batch, the leave-block-out scores: cv_ard_batch)")
-        if grad not in (None, "exact"):
-            raise ValueError("grad must be None or 'exact'")
-        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, getattr(self, "_batch_n", None), getattr(self, "_batch_d", None))
-        cid = L.HINDCAST_CRITERION_IDS[criterion]
-        return self._ard_score_batch("hindcast_ard_batch", theta, grad, group, predictions, cid, lambda th, F, d, n, mean, var, score, g: self._lib.sigp_hindcast_grad_ard_batch(
-            self._h, int(first), F, self._kid, L.ptr(th), d + 1, d + 1, lead, min_train, L.LOO_MODES[sigma_f], cid, L.ptr(mean), L.ptr(var), n, L.ptr(score), L.ptr(g), d + 1))
+        return self._family_ard("hindcast", theta, (lead, min_train), criterion, sigma_f, grad, predictions, first=first, group=group)
 
     def hindcast_objective_batch(self, theta, lead=1, min_train=None, first=0, criterion="hindcast_nlpd", sigma_f="refit", group=8):
         """A hindcast score over ONE common length scale for many fits in one device call: theta [F, 2] = (log l, log sn~) per fit ->
         (value [F], grad [F, 2]).  It is ``hindcast_ard_batch`` at equal scales with d/dlog l = sum_k d/dlog l_k: per fit the bits
         ``hindcast_objective`` returns for it where ``hindcast_ard_batch`` carries ``hindcast_ard``'s.  A fit whose exp(theta) is not finite
         (it rides along at harmless parameters) or whose K~ is not SPD gets inf in its value and both gradient entries."""
-        if criterion not in L.HINDCAST_CRITERION_IDS:
-            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse'")
-        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, getattr(self, "_batch_n", None), getattr(self, "_batch_d", None))
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        d = getattr(self, "_batch_d", None)
-        if d is None:
-            raise RuntimeError("hindcast_objective_batch: stage the data sets with upload_batch() first")
-        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
-        if theta.ndim != 2 or theta.shape[1] != 2:
-            raise ValueError("theta must be [F, 2] = (log l, log sn~) per fit, got %s" % (theta.shape,))
-        with np.errstate(over="ignore"):
-            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
-        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
-        th = np.where(ok[:, None], np.concatenate([np.repeat(theta[:, :1], d, axis=1), theta[:, 1:]], axis=1), 0.0)
-        f, g = self.hindcast_ard_batch(th, lead=lead, min_train=min_train, first=first, criterion=criterion, sigma_f=sigma_f, grad="exact", group=group)
-        f, g = np.array(f, dtype=np.float64), np.array([[np.sum(gi[:-1]), gi[-1]] for gi in g])       # row by row, as hindcast_objective adds them
-        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
-        f[~ok] = np.inf
-        g[~ok] = np.inf
-        return f, g
+        return self._family_objective_batch("hindcast", theta, (lead, min_train), first, criterion, sigma_f, group)
 
     def optimize_hindcast_batch(self, X, y, theta0, lead=1, min_train=None, criterion="hindcast_nlpd", sigma_f="refit", ard=True, group=8, maxiter=50, gtol=1e-5,
                                 ftol=1e-10, max_step=2.0):
@@ -1415,42 +1336,19 @@ class GPR:
         repeated for all d features), as ``optimize_cv_batch`` takes it; F = S B rows are S starts per data set, start i on data set
         i % B, and all F results come back.  ``ard=False``: one common length scale (``hindcast_objective_batch``), ``theta0`` [2] or
         [F, 2], x [F, 2].  ``min_train=None`` means max(2, d + 1).  RBF / Matern, fp64; lead <= 128 and at least one scored row."""
-        from .optim import bfgs_lockstep
         if criterion not in L.HINDCAST_CRITERION_IDS:
-            raise ValueError("criterion must be 'hindcast_nlpd' or 'hindcast_sse' (the leave-block-out scores: optimize_cv_batch; the leave-one-out scores and "
-                             "'nlml': optimize_ard_batch)")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        if self.kernel == "netdiffusion" or self.dtype != "f64":
-            raise ValueError("per-feature length scales: RBF / Matern kernels on the fp64 engine only")
-        X = L.f64(X, 3)
-        B, n, d = X.shape
-        lead, min_train = self._hindcast_args(lead, min_train, sigma_f, n, d)
-        if ard:
-            th0 = self._ard_starts(theta0, B, d)
-        else:
-            th0 = np.atleast_2d(np.asarray(theta0, dtype=np.float64))
-            if th0.ndim != 2 or th0.shape[1] != 2:
-                raise ValueError("theta0 must hold 2 entries per start (log l, log sn~) with ard=False")
-            th0 = np.array(th0) if th0.shape[0] != B and th0.shape[0] % B == 0 else np.broadcast_to(th0[0] if th0.shape[0] == 1 else th0, (B, 2))
-        self.upload_batch(X, y, None, group=group, concurrency=1)
-        objective = self.hindcast_ard_batch if ard else self.hindcast_objective_batch
-        return bfgs_lockstep(lambda t: objective(t, lead=lead, min_train=min_train, criterion=criterion, sigma_f=sigma_f, group=group), th0, maxiter=maxiter, gtol=gtol,
-                             ftol=ftol, max_step=max_step)
+            raise ValueError(_FAMILIES["hindcast"]["criteria"] + " (the leave-block-out scores: optimize_cv_batch; the leave-one-out scores and 'nlml': optimize_ard_batch)")
+        return self._optimize_family_batch("hindcast", X, y, theta0, (lead, min_train), criterion, sigma_f, ard, group,
+                                           dict(maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step))
 
     def _loo_objective_batch(self, theta, criterion, sigma_f, group):
         """(value [F], grad [F, 2]) of a leave-one-out score for theta [F, 2] on the staged data sets, one device call (``loo_batch``)."""
-        theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
-        with np.errstate(over="ignore"):
-            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
-        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
-        r = self.loo_batch(np.where(ok, ell, 1.0), np.where(ok, sn, 1.0), sigma_f=sigma_f, group=group, predictions=False, grad=True)
         key = L.LOO_CRITERIA[criterion]
-        f, g = r[key].copy(), r[key + "_grad"].copy()
-        ok &= np.isfinite(f) & np.all(np.isfinite(g), axis=1)
-        f[~ok] = np.inf
-        g[~ok] = np.inf
-        return f, g
+
+        def scores(ell, sn):
+            r = self.loo_batch(ell, sn, sigma_f=sigma_f, group=group, predictions=False, grad=True)
+            return r[key].copy(), r[key + "_grad"].copy()
+        return self._common_scale_batch(np.atleast_2d(np.asarray(theta, dtype=np.float64)), scores)
 
     def optimize_batch(self, X, y, theta0, group=8, maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0, M=None, expm="eigh", method=None,
                        criterion="nlml", sigma_f="refit", ard=False):
@@ -1496,24 +1394,10 @@ class GPR:
         X = L.f64(X, 3)
         B = X.shape[0]
         self.upload_batch(X, y, None, group=group, concurrency=1)
-        th0 = np.asarray(theta0, dtype=np.float64)
-        p = 2
         if ard:
-            d = X.shape[2]
-            p = d + 1
-            th0 = np.atleast_2d(th0)
-            if th0.ndim == 2 and th0.shape[1] == 2 and d != 1:      # (log l, log sn~): the common log l for every feature
-                th0 = np.concatenate([np.repeat(th0[:, :1], d, axis=1), th0[:, 1:]], axis=1)
-            if th0.ndim != 2 or th0.shape[1] != p:
-                raise ValueError("theta0 must hold d + 1 = %d entries per start, or 2 (log l is repeated for every feature)" % p)
-            if th0.shape[0] == 1:
-                th0 = th0[0]
-        if th0.ndim == 2 and th0.shape[0] != B and th0.shape[1] == p and th0.shape[0] % B == 0:
-            th0 = np.array(th0)                                   # S starts per data set: start i uses data set i % B
-        else:
-            th0 = np.broadcast_to(th0, (B, p))
-        if ard:
+            th0 = self._starts(theta0, B, X.shape[2] + 1, X.shape[2])
             return bfgs_lockstep(lambda t: self.nlml_ard_batch(t, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
+        th0 = self._starts(theta0, B, 2, refuse=False)
         if criterion != "nlml":   # the same lockstep BFGS on a leave-one-out score: one sigp_loo_grad_batch call per round
             return bfgs_lockstep(lambda t: self._loo_objective_batch(t, criterion, sigma_f, group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
         return bfgs_lockstep(lambda t: self.nlml_batch(t, grad="exact", group=group), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
@@ -1528,37 +1412,44 @@ class GPR:
             raise ValueError("small_score_batch runs the reference kernel (RBF / Matern: loo_ard_batch, hindcast_ard_batch)")
         if criterion not in L.LOO_CRITERION_IDS and criterion not in L.HINDCAST_CRITERION_IDS:
             raise ValueError("criterion must be 'loo_nlpd', 'loo_sse', 'hindcast_nlpd' or 'hindcast_sse' (block-CV gradients are not built for the reference kernel)")
-        if sigma_f not in L.LOO_MODES:
-            raise ValueError("sigma_f must be 'refit' or 'fixed'")
-        sb = getattr(self, "_small", None)
-        if sb is None:
-            raise RuntimeError("small_score_batch: stage the data sets with upload_batch(X_list, y_list, Xs_list, M=M_list) first")
+        _check_sigma_f(sigma_f)
+        sb = self._small_staged("small_score_batch")
         theta = L.f64(np.atleast_2d(theta), 2)
         if theta.shape[1] != 2:
             raise ValueError("theta must be [F, 2]")
+        kind, key = criterion.split("_")
+        run = dict(loo=sigma_f) if kind == "loo" else dict(hindcast=dict(lead=lead, min_train=min_train, sigma_f=sigma_f))
+        val, g = self._small_run(sb, theta, first, sets, expm, criterion, kind + "_grad", score_grad=key, **run)
+        g[~np.isfinite(val)] = np.inf
+        return val, g
+
+    def _small_staged(self, what):
+        sb = getattr(self, "_small", None)
+        if sb is None:
+            raise RuntimeError("%s: stage the data sets with upload_batch(X_list, y_list, Xs_list, M=M_list) first" % what)
+        return sb
+
+    def _small_run(self, sb, theta, first, sets, expm, value, gradient, **run):
+        """One launch of the one-workgroup kernel for theta [F, 2] on the staged ``SmallBatch``, pair i on data set (first + i) % B or
+        ``sets[i]``: the pairs whose exp(theta) is finite and whose Sigma~ can be formed are queued (scipy's expm overflowing is the except
+        branch of north/June1st.py:254-256), ``sb.run(**run)`` runs them, and its entries ``value`` [.] and ``gradient`` [., 2] (None: left
+        out) come back scattered into (value [F], gradient [F, 2]), +inf for every pair that did not run."""
         F, B = theta.shape[0], len(self._small_ids)
-        with np.errstate(over="ignore"):
-            ell, sn = np.exp(theta[:, 0]), np.exp(theta[:, 1])
-        ok = np.isfinite(ell) & np.isfinite(sn) & (ell > 0)
-        val = np.full(F, np.inf)
-        g = np.full((F, 2), np.inf)
+        ell, sn, ok = _finite_exp(theta)
+        val, g = np.full(F, np.inf), np.full((F, 2), np.inf)
         sb.clear_fits()
-        run = []
+        ran = []
         for i in np.flatnonzero(ok):
             try:
                 sb.add_fit(self._small_ids[(first + i) % B if sets is None else int(sets[i])], ell[i], sn[i], expm=expm)
-                run.append(i)
+                ran.append(i)
             except (FloatingPointError, OverflowError, ValueError):
                 pass
-        if run:
-            kind, key = criterion.split("_")
-            if kind == "loo":
-                r = sb.run(loo=sigma_f, score_grad=key)
-            else:
-                r = sb.run(hindcast=dict(lead=lead, min_train=min_train, sigma_f=sigma_f), score_grad=key)
-            val[run] = r[criterion]
-            g[run] = r[kind + "_grad"]
-            g[~np.isfinite(val)] = np.inf
+        if ran:
+            r = sb.run(**run)
+            val[ran] = r[value]
+            if gradient is not None:
+                g[ran] = r[gradient]
         return val, g
 
     def optimize_small_batch(self, X, y, theta0, criterion="hindcast_nlpd", lead=1, min_train=2, sigma_f="refit", M=None, expm="eigh", maxiter=50,

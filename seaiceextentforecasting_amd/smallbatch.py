@@ -174,13 +174,7 @@ class SmallBatch:
             if not isinstance(hindcast, dict) or set(hindcast) - {"lead", "min_train", "sigma_f"}:
                 raise ValueError("hindcast must be dict(lead=1, min_train=2, sigma_f='refit')")
             hc_mode = hindcast.get("sigma_f", "refit")
-            if hc_mode not in L.LOO_MODES:
-                raise ValueError("sigma_f must be 'refit' or 'fixed'")
-            hc_lead, hc_mt = int(hindcast.get("lead", 1)), int(hindcast.get("min_train", 2))
-            if hc_lead < 1 or hc_lead > L.HINDCAST_SMALL_MAX_LEAD:
-                raise ValueError("hindcast: 1 <= lead <= %d required" % L.HINDCAST_SMALL_MAX_LEAD)
-            if hc_mt < 1:
-                raise ValueError("hindcast: min_train >= 1 required")
+            hc_lead, hc_mt = self.gp._hindcast_args(hindcast.get("lead", 1), hindcast.get("min_train", 2), hc_mode, max_lead=L.HINDCAST_SMALL_MAX_LEAD)
             for X, _, _, _ in self._data:
                 if hc_mt + hc_lead - 1 > X.shape[0] - 1:
                     raise ValueError("hindcast: a data set of %d rows has no scored row (min_train + lead - 1 = %d)" % (X.shape[0], hc_mt + hc_lead - 1))
