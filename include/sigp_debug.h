@@ -18,7 +18,10 @@ int sigp_debug_time_kbuild(sigp_handle* h, int n, int d, int nb, int kernel_id, 
 /* sustained v_mfma_f64_16x16x4_f64 rate; seed < 0: pseudo-random operands (tools/mfma_peak.py) */
 int sigp_debug_mfma_peak(sigp_handle* h, int blocks, int iters, double* tflops, double seed);
 /* time the lower-tile update on a synthetic panel: rt row tiles, depth K; small = 0 generic 128-tile kernel,
- * 1 generic 64-tile kernel, 2 syrk128_kernel; dbg = ablation bits; clock_ghz = in-kernel clock (tools/syrk_bench.py) */
+ * 1 generic 64-tile kernel, 2 syrk128_kernel; dbg = ablation bits; clock_ghz = in-kernel clock (tools/syrk_bench.py).
+ * Measurement bits of syrk128_kernel: 256 phase stamps (prologue / K loop / epilogue cycles, turnaround, on stderr); 1024 one workgroup
+ * per CU (extra dynamic LDS, same code); 2048 persistent walk of the product instantiation, one workgroup per slot; 4096 (with 256) per-CU
+ * timeline of the last launch; 8192 / 16384 wave priority 3 outside / inside the K loop */
 int sigp_debug_time_syrk(sigp_handle* h, int rt, int K, int patch, int small, int reps, double* ms_avg, double* tflops, int dbg,
                          double* clock_ghz);
 /* do small kernels on different streams overlap? (tools/stream_conc.py) */

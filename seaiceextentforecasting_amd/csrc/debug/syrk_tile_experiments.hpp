@@ -132,8 +132,12 @@ __global__ __launch_bounds__(512) void syrk_wide_kernel(GemmArgsT<T> g) {
 
 // ---- 128 x 64 workgroup tile (4 waves of 64 x 32), three workgroups per CU ---------------------------------------------------
 // The opposite of the wide tile: half the tile's columns, so a workgroup needs 48 KiB of LDS and ~130 VGPRs per wave and THREE of
-// them fit on a CU.  What the update kernel loses cycles to is not its operand stream but the moments when every resident
-// workgroup of a CU is outside its K loop (C-tile load / store under memory load): a third workgroup covers more of them.  Costs
+// them fit on a CU.  The idea was that the update kernel loses its cycles in the moments when every resident workgroup of a CU is
+// outside its K loop (C-tile load / store under memory load), which a third workgroup would cover.  The per-CU timeline
+// (tools/syrk_bench.py timeline, docs/EXPERIMENTS.md) says otherwise: with two workgroups per CU those moments are 0.2-0.5 % of the
+// steady state, and a workgroup alone in its K loop runs a slice in 4340 cycles against 4096 of matrix-pipe time; the pipe idles
+// INSIDE the K loops (about 5 %, whether one or two workgroups are in theirs), where vector-ALU address arithmetic of the operand
+// DMA competed with the MFMAs for issue.  Costs
 // 50 % more global -> LDS bytes and fragment reads per flop.  Same MFMA sequence per 16x16 accumulator and k order: bit-identical.
 constexpr int SYN_LDS_BYTES = 2 * (SY_T + SY_T / 2) * SY_SLICE_BYTES;   // 2 buffers x (128 A rows + 64 B rows) x 128 B = 48 KiB
 template <typename T>

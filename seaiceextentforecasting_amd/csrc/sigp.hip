@@ -9,6 +9,9 @@
 #include <cstring>
 #include <functional>
 #include <limits>
+#ifdef SIGP_DEBUG_TOOLS
+#include <map>     // sigp_debug.inc (the update kernel's per-CU timeline)
+#endif
 #include <mutex>
 #include <thread>
 #include <chrono>
@@ -472,6 +475,7 @@ template <typename T, bool SET>
 int launch_syrk128_t(sigp_handle* h, hipStream_t st, const GemmArgsT<T>& g, bool may_persist = false) {
   const int nt = gemm_grid_size(g.r0, g.r1, g.c0, g.c1, g.lower, g.patch);
   if (nt <= 0) return SIGP_OK;
+  if (!sy_row_stride_ok(g.lda, sizeof(T)) || !sy_row_stride_ok(g.ldb, sizeof(T))) return fail(h, SIGP_BAD_ARG, "syrk128: operand row stride beyond the tile's 32-bit DMA offsets");
   static AttrOnce attr;
   HIPCHK(h, attr.set(h->device, (const void*)syrk128_kernel<T, SET>, SY_LDS_BYTES));
 #ifdef SIGP_DEBUG_TOOLS   // tile-walk experiments (persistent grid, XCD-chunked walk): measured slower, libsigp_debug.so only
@@ -495,6 +499,31 @@ int launch_syrk128_t(sigp_handle* h, hipStream_t st, const GemmArgsT<T>& g, bool
     }
   }
   const long total = (long)nt * std::max(1, g.batch);
+  if (g.dbg & (1024 | 2048)) {
+    // occupancy / walk measurements of the product instantiation (tools/syrk_bench.py occupancy): dbg 1024 asks for SY_LDS_LONE_BYTES of
+    // dynamic LDS -- the same code at one workgroup per CU; dbg 2048 walks the (member, tile) list with one resident workgroup per slot
+    // (2 per CU, 1 with dbg 1024), static stride, the DG / RD forms included
+    if constexpr (!SET) {
+      const int lds = (g.dbg & 1024) ? SY_LDS_LONE_BYTES : SY_LDS_BYTES;
+      const bool sym = h->opt_diag_tiles && g.lower && g.A == g.B && g.lda == g.ldb && g.sA == g.sB && g.zA == g.zB && g.r0 <= g.c0;
+      if (!sym || g.patch != 0 || std::max(1, g.zcount) != 1) return fail(h, SIGP_BAD_ARG, "dbg 1024 / 2048: plain walk of a symmetric update only");
+      if (g.dbg & 2048) {
+        GemmArgsT<T> gp = g;
+        gp.ntile = nt;
+        const long slots = (long)h->ncu * ((g.dbg & 1024) ? 1 : 2);
+        HIPCHK(h, hipFuncSetAttribute((const void*)syrk128_kernel<T, false, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SY_LDS_LONE_BYTES));
+        hipLaunchKernelGGL((syrk128_kernel<T, false, true, 0, true>), dim3((unsigned)std::min(slots, total), 1), dim3(256), lds, st, gp);
+      } else {
+        // (set on every call: the product path's once-per-device limit for this instantiation is SY_LDS_BYTES)
+        HIPCHK(h, hipFuncSetAttribute((const void*)syrk128_kernel<T, false, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SY_LDS_LONE_BYTES));
+        hipLaunchKernelGGL((syrk128_kernel<T, false, false, 0, true>), dim3(nt, std::max(1, g.batch), 1), dim3(256), lds, st, g);
+      }
+      HIPCHK(h, hipGetLastError());
+      return SIGP_OK;
+    } else {
+      return fail(h, SIGP_BAD_ARG, "dbg 1024 / 2048: the trailing update only");
+    }
+  }
   if (may_persist && h->persist_now && h->opt_update_wgs > 0 && g.patch == 0 && total > h->opt_update_wgs) {
     GemmArgsT<T> gp = g;
     gp.ntile = nt;

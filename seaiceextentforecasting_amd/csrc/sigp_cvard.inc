@@ -44,6 +44,7 @@ static int cv_ard_products(sigp_handle* h, hipStream_t st, int nb, long n, long 
   }
   {   // P B: tile (bi, bj) = rows bi of P against rows bj of the band store, the K window of B's three block columns
     ProfScope ps(h, st, SIGP_KC_MLII, nb * (2.0 * n_pad * n_pad * CVA_BAND), nb * (8.0 * n_pad * n_pad));
+    if (!sy_row_stride_ok(ld, sizeof(double))) return fail(h, SIGP_BAD_ARG, "cv band product: row stride beyond the tile's 32-bit DMA offsets");
     static AttrOnce b_attr;
     HIPCHK(h, b_attr.set(h->device, (const void*)cv_band_product_kernel, SY_LDS_BYTES));
     hipLaunchKernelGGL(cv_band_product_kernel, dim3((unsigned)T, (unsigned)T, (unsigned)nb), dim3(256), SY_LDS_BYTES, st, (const double*)h->gK, ld, (const double*)adj.band, h->gD,

@@ -174,7 +174,7 @@ static int debug_time_syrk_t(sigp_handle* h, int rt, int K, int patch, int small
   g.A = P; g.lda = ldp; g.B = P; g.ldb = ldp; g.C = Cm; g.ldc = ldc; g.K = K; g.r0 = 0; g.r1 = rt; g.c0 = 0; g.c1 = rt; g.lower = 1; g.patch = patch; g.dbg = dbg;
   unsigned long long* stamp = nullptr;
   const int ngrid = gemm_grid_size(0, rt, 0, rt, 1, patch);
-  if (clock_ghz && small == 2) { HIPCHK(h, hipMalloc((void**)&stamp, (size_t)ngrid * 40)); HIPCHK(h, hipMemset(stamp, 0, (size_t)ngrid * 40)); g.stamp = stamp; }
+  if (clock_ghz && small == 2) { HIPCHK(h, hipMalloc((void**)&stamp, (size_t)ngrid * 104)); HIPCHK(h, hipMemset(stamp, 0, (size_t)ngrid * 104)); g.stamp = stamp; }   // 5 + 8 (timeline) words per tile
   if (small == 1) { g.r1 *= 2; g.c1 *= 2; }
   double tot = 0;
   for (int r = 0; r < reps + 2; ++r) {
@@ -190,14 +190,78 @@ static int debug_time_syrk_t(sigp_handle* h, int rt, int K, int patch, int small
     std::vector<unsigned long long> hs((size_t)ngrid * 5);
     HIPCHK(h, hipMemcpy(hs.data(), stamp, hs.size() * 8, hipMemcpyDeviceToHost));
     if (dbg & 256) {
-      double p0 = 0, p1 = 0, p2 = 0;
-      for (int i = 0; i < ngrid; ++i) { p0 += (double)hs[2 * (size_t)ngrid + 3 * i]; p1 += (double)hs[2 * (size_t)ngrid + 3 * i + 1]; p2 += (double)hs[2 * (size_t)ngrid + 3 * i + 2]; }
-      fprintf(stderr, "[syrk phases] cycles per tile (wave 0): prologue %.0f  K loop %.0f  epilogue %.0f\n", p0 / ngrid, p1 / ngrid, p2 / ngrid);
+      // full tiles only: in the plain lower walk every column of the tile space starts with its diagonal tile (the shorter DG form)
+      std::vector<char> is_diag((size_t)ngrid, 0);
+      if (patch == 0) { size_t i = 0; for (int bj = 0; bj < rt; ++bj) { is_diag[i] = 1; i += (size_t)(rt - bj); } }
+      double p0 = 0, p1 = 0, p2 = 0; int nfull = 0;
+      for (int i = 0; i < ngrid; ++i) {
+        if (is_diag[i] && ngrid > rt) continue;
+        p0 += (double)hs[2 * (size_t)ngrid + 3 * i]; p1 += (double)hs[2 * (size_t)ngrid + 3 * i + 1]; p2 += (double)hs[2 * (size_t)ngrid + 3 * i + 2]; ++nfull;
+      }
+      fprintf(stderr, "[syrk phases] cycles per tile (wave 0): prologue %.0f  K loop %.0f  epilogue %.0f  (per K-slice %.0f)\n", p0 / nfull, p1 / nfull, p2 / nfull,
+              p1 / nfull / (K / Num<Real>::KT));
     }
     double sc = 0, sr = 0;
     for (int i = 0; i < ngrid; ++i) { sc += (double)hs[2 * i]; sr += (double)(hs[2 * i + 1] >> 8); }
     if (dbg & 32) { fprintf(stderr, "[xcc by block]"); for (int i = 0; i < std::min(ngrid, 96); ++i) fprintf(stderr, " %d", (int)(hs[2 * i + 1] & 0xf)); fprintf(stderr, "\n"); }
     *clock_ghz = sr > 0 ? sc / (sr * 10.0) : 0.0;   // s_memrealtime ticks at 100 MHz
+    if (dbg & 256) {
+      // turnaround: what a slot spends per tile OUTSIDE the stamped body (dispatch or walk step, kernarg loads, retirement) =
+      // launch time x clock / tiles per slot - stamped cycles per tile (which, under dbg 256, include the wait for the C stores)
+      const double slots = (double)h->ncu * ((dbg & 1024) ? 1 : 2), per_slot = tot / reps * 1e-3 * *clock_ghz * 1e9 * slots / ngrid;
+      fprintf(stderr, "[syrk turnaround] %s%s launch cycles per tile and slot %.0f  stamped body %.0f  turnaround %.0f\n", (dbg & 1024) ? "1 wg/CU " : "2 wg/CU ",
+              (dbg & 2048) ? "persistent" : "one tile per wg", per_slot, sc / ngrid, per_slot - sc / ngrid);
+    }
+    if ((dbg & 4096) && (dbg & 256) && *clock_ghz > 0) {
+      // timeline of the last launch (dbg 4096): per CU, how much of the steady state -- from the moment every slot has been filled once to the
+      // last tile's start -- has 2 / 1 / 0 workgroups inside their stamped body, and inside their K loop; what is left is ramp and tail
+      std::vector<unsigned long long> tl((size_t)ngrid * 8);
+      HIPCHK(h, hipMemcpy(tl.data(), stamp + 5 * (size_t)ngrid, tl.size() * 8, hipMemcpyDeviceToHost));
+      const int slots_cu = (dbg & 1024) ? 1 : 2, slots = h->ncu * slots_cu;
+      std::vector<double> starts((size_t)ngrid);
+      double t_first = 1e300, t_end = 0, lag = 0;
+      for (int i = 0; i < ngrid; ++i) {
+        starts[i] = (double)tl[8 * (size_t)i + 1];
+        double em = 0; for (int w = 0; w < 4; ++w) em = std::max(em, (double)tl[8 * (size_t)i + 2 + w]);
+        t_first = std::min(t_first, starts[i]); t_end = std::max(t_end, em); lag += em - (double)tl[8 * (size_t)i + 2];
+      }
+      std::vector<double> ss = starts; std::sort(ss.begin(), ss.end());
+      if (ngrid > 2 * slots) {
+        const double w0 = ss[slots - 1], w1 = ss[ngrid - 1];
+        struct Ev { double t; int dres, dloop; };
+        std::map<unsigned, std::vector<Ev>> per_cu;
+        int started = 0;
+        for (int i = 0; i < ngrid; ++i) {
+          const double s0 = starts[i], e0 = (double)tl[8 * (size_t)i + 2], cyc = (double)hs[2 * (size_t)i];
+          double em = 0; for (int w = 0; w < 4; ++w) em = std::max(em, (double)tl[8 * (size_t)i + 2 + w]);
+          const double tpc = cyc > 0 ? (e0 - s0) / cyc : 0.0;      // ticks per cycle of this body
+          const double l0 = s0 + (double)hs[2 * (size_t)ngrid + 3 * i] * tpc, l1 = l0 + (double)hs[2 * (size_t)ngrid + 3 * i + 1] * tpc;
+          auto& v = per_cu[(unsigned)tl[8 * (size_t)i]];
+          v.push_back({s0, 1, 0}); v.push_back({em, -1, 0}); v.push_back({l0, 0, 1}); v.push_back({l1, 0, -1});
+          started += s0 > w0 && s0 <= w1;
+        }
+        double R[4] = {0, 0, 0, 0}, Lp[4] = {0, 0, 0, 0};
+        for (auto& kv : per_cu) {
+          auto& v = kv.second;
+          std::sort(v.begin(), v.end(), [](const Ev& a, const Ev& b) { return a.t < b.t; });
+          int res = 0, lp = 0; double tprev = w0;
+          for (const Ev& e : v) {
+            const double tc = std::min(std::max(e.t, w0), w1);
+            R[std::min(std::max(res, 0), 3)] += tc - tprev; Lp[std::min(std::max(lp, 0), 3)] += tc - tprev; tprev = tc;
+            res += e.dres; lp += e.dloop;
+          }
+          R[std::min(std::max(res, 0), 3)] += w1 - tprev; Lp[std::min(std::max(lp, 0), 3)] += w1 - tprev;
+        }
+        const double all = (w1 - w0) * (double)per_cu.size(), tick_cyc = *clock_ghz * 10.0;
+        const double mean_res = (R[1] + 2 * R[2] + 3 * R[3]) / all;
+        fprintf(stderr, "[syrk timeline] %d CUs seen; launch %.1f us = ramp %.1f + steady %.1f + tail %.1f (stamped), event-timed %.1f us\n", (int)per_cu.size(),
+                (t_end - t_first) * 0.01, (w0 - t_first) * 0.01, (w1 - w0) * 0.01, (t_end - w1) * 0.01, tot / reps * 1e3);
+        fprintf(stderr, "[syrk timeline] steady state, share of CU time with k workgroups in their body: k=0 %.4f  k=1 %.4f  k=2 %.4f  k>2 %.4f; in their K loop: k=0 %.4f  k=1 %.4f  k=2 %.4f\n",
+                R[0] / all, R[1] / all, R[2] / all, R[3] / all, Lp[0] / all, Lp[1] / all, (Lp[2] + Lp[3]) / all);
+        fprintf(stderr, "[syrk timeline] slot time outside a body per tile started: %.0f cycles; last wave ends %.0f cycles after wave 0\n",
+                started > 0 ? (slots_cu - mean_res) * all / started * tick_cyc : 0.0, lag / ngrid * tick_cyc);
+      }
+    }
     (void)hipFree(stamp);
   }
   const double nt = (double)rt * (rt + 1) / 2;

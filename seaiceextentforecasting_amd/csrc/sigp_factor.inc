@@ -139,6 +139,7 @@ int launch_chain_link(sigp_handle* h, hipStream_t st, const LinkArgsT<Real>& a, 
 // panel_strip_kernel: nstrips 128-row strips from row block a.rb0 down, of nb lockstep members (option strip_tri picks the instantiation)
 template <typename Real>
 int launch_panel_strip(sigp_handle* h, hipStream_t st, const StripArgsT<Real>& a, int nstrips, int nb) {
+  if (!sy_row_stride_ok(a.ld, sizeof(Real)) || !sy_row_stride_ok(a.ldm, sizeof(Real))) return fail(h, SIGP_BAD_ARG, "panel_strip: row stride beyond the tile's 32-bit DMA offsets");
   static AttrOnce strip_attr, strip_attr_full;
   if (h->opt_strip_tri) {
     HIPCHK(h, strip_attr.set(h->device, (const void*)panel_strip_kernel<Real>, SY_LDS_BYTES));

@@ -99,6 +99,7 @@ int sigp_predict_cov(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, 
   else { t.part = h->covPart; t.tile_stride = (long)NB * NB; t.ldp = NB; t.slice_stride = P * NB * NB; }
   {
     ProfScope ps(h, st, SIGP_KC_EPILOGUE, (double)P * 2.0 * NB * NB * n_pad, 8.0 * P * (2.0 * NB * n_pad + (double)S * NB * NB), (int)(n_pad / S));
+    if (!sy_row_stride_ok(ld, sizeof(double))) return fail(h, SIGP_BAD_ARG, "predictive covariance: row stride beyond the tile's 32-bit DMA offsets");
     static AttrOnce attr;
     HIPCHK(h, attr.set(h->device, (const void*)predcov_partial_kernel, SY_LDS_BYTES));
     hipLaunchKernelGGL(predcov_partial_kernel, dim3((unsigned)P, (unsigned)S), dim3(256), SY_LDS_BYTES, st, (const double*)h->covZ, ld, (int)nkb, t);

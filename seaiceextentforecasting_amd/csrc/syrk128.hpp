@@ -9,6 +9,8 @@
 //   * one 16-B read feeds two MFMA k-steps (lane lq holds k = 2*lq, 2*lq+1 of an 8-wide k-group; A and B use
 //     the same k permutation, so the sum over k is unchanged);
 //   * the sign is folded into the accumulator (acc = -C; acc += A B^T; C = -acc) so A needs no negation.
+//   * a DMA address is scalar base + 32-bit lane offset (the bases step through K in scalar registers): the K loop has no vector-ALU
+//     address arithmetic next to its MFMAs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -20,6 +22,11 @@ namespace sigp {
 constexpr int SY_T = 128;                      // tile
 constexpr int SY_SLICE_BYTES = 128;            // K-slice per row: 16 doubles / 32 floats
 constexpr int SY_LDS_BYTES = 2 * 2 * SY_T * SY_SLICE_BYTES;   // 2 buffers x (A,B) x 128 rows x 128 B = 64 KiB
+constexpr int SY_LDS_LONE_BYTES = 96 * 1024;   // debug library only (dbg 1024): a request no two workgroups of a CU can both get (160 KiB per
+                                               // CU) -- the same code at ONE workgroup per CU; the kernel never touches the extra 32 KiB
+
+// the tile's DMA adds a 32-bit byte offset (up to 128 rows of an operand) to a scalar base: what a launcher has to check of a row stride
+__host__ __device__ constexpr bool sy_row_stride_ok(long ld, int elem_bytes) { return ld > 0 && ld * elem_bytes < (1L << 25); }
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
@@ -70,6 +77,10 @@ __device__ __forceinline__ void syrk128_tile(const T* Ag, long lda, const T* Bg,
   // results are bit-identical to the untransposed form.  (fp64 puts rows lq + 4 r in a lane: nothing contiguous either way.)
   constexpr bool TRANSPOSED_ACC = sizeof(T) == 4;
 
+  // (dbg 8192 / 16384, debug library only: wave priority 3 outside / inside the K loop, 0 in the other part -- which of the CU's two
+  // workgroups the issue arbiter prefers when both have an instruction ready)
+  if (dbg & 8192) __builtin_amdgcn_s_setprio(3);
+  if (dbg & 16384) __builtin_amdgcn_s_setprio(0);
   acc_t acc[4][4];
   if (SET || (dbg & 8)) {
 #pragma unroll
@@ -133,16 +144,27 @@ __device__ __forceinline__ void syrk128_tile(const T* Ag, long lda, const T* Bg,
   // DMA coordinates: per wave-instruction 8 rows x 128 B; lane -> (row = lane>>3, slot' = lane&7)
   const int drow_ = wave * 8 + (lane >> 3);                  // + 32*p
   const int dks = ((lane & 7) ^ ((drow_ >> 1) & 7)) * NE;    // source k offset (elements) of this lane's 16 B
-  const T* Asrc = Ag + (long)drow_ * lda + dks;
-  const T* Bsrc = Bg + (long)drow_ * ldb + dks;
-  const long a32 = 32 * lda, b32 = 32 * ldb;
+  // A DMA address is a UNIFORM base -- the tile's first row at the slice's k offset, a scalar register pair -- plus a per-lane 32-bit byte
+  // offset that is the same in every slice (row drow_ + 32 p, swizzled 16-byte slot): the scalar-base form of global_load_lds.  The K loop
+  // then carries no vector-ALU address arithmetic (per-lane 64-bit pointers cost 16 v_lshl_add_u64 per slice, issued through the port the
+  // MFMAs go through, and 8 more VGPRs).  128 rows x row stride x sizeof(T) has to fit 32 bits: lda, ldb < 2^22 elements (every caller's
+  // row stride is a padded matrix order, below 2^18).
+  unsigned aoff[4], boff[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    aoff[p] = (unsigned)(((long)(drow_ + 32 * p) * lda + dks) * (long)sizeof(T));
+    boff[p] = (unsigned)(((long)(drow_ + 32 * p) * ldb + dks) * (long)sizeof(T));
+  }
 #define SY_ISSUE(k0, buf)                                                                                     \
   {                                                                                                           \
+    unsigned long sy_a = (unsigned long)(Ag + (k0)), sy_b = (unsigned long)(Bg + (k0));                       \
+    asm("" : "+s"(sy_a), "+s"(sy_b));   /* opaque scalar bases: folded into per-lane pointers otherwise */    \
     _Pragma("unroll") for (int p = 0; p < 4; ++p) {                                                           \
+      asm("" : "+v"(aoff[p]), "+v"(boff[p]));   /* 32-bit HERE: widened outside the loop they become pairs */ \
       if (RD == 0 || (RD == 1 && p == 0))                                                                     \
-        __builtin_amdgcn_global_load_lds((gbl_ptr_t)(Asrc + p * a32 + (k0)),                                  \
+        __builtin_amdgcn_global_load_lds((gbl_ptr_t)((const char*)sy_a + aoff[p]),                              \
                                          (lds_ptr_t)(As + ((buf) * SY_T + p * 32 + wave * 8) * KTe), 16, 0, 0); \
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(Bsrc + p * b32 + (k0)),                                    \
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)((const char*)sy_b + boff[p]),                                \
                                        (lds_ptr_t)(Bs + ((buf) * SY_T + p * 32 + wave * 8) * KTe), 16, 0, 0); \
     }                                                                                                         \
   }
@@ -163,6 +185,8 @@ __device__ __forceinline__ void syrk128_tile(const T* Ag, long lda, const T* Bg,
   SY_ISSUE(0, 0);
   __syncthreads();
   if (stamp) ph0 = __builtin_amdgcn_s_memtime();   // C tile and first K-slice have landed
+  if (dbg & 8192) __builtin_amdgcn_s_setprio(0);
+  if (dbg & 16384) __builtin_amdgcn_s_setprio(3);
   if (nst > 1) SY_ISSUE(KTe, 1);
 #pragma unroll
   for (int i = 0; i < 4; ++i) a0[i] = *(const v16_t*)(As + arow0 + i * IS * KTe + fo0);
@@ -261,6 +285,8 @@ __device__ __forceinline__ void syrk128_tile(const T* Ag, long lda, const T* Bg,
   }
 #undef SY_ISSUE
   if (stamp) ph1 = __builtin_amdgcn_s_memtime();   // K loop issued
+  if (dbg & 8192) __builtin_amdgcn_s_setprio(3);
+  if (dbg & 16384) __builtin_amdgcn_s_setprio(0);
 
   if (!(dbg & 16) || acc[0][0][0] == (T)12345.678) {   // dbg 16: timing ablation without the C store
 #pragma unroll
@@ -287,7 +313,8 @@ __device__ __forceinline__ void syrk128_tile(const T* Ag, long lda, const T* Bg,
 // block, when at most 16 of its rows are in use) take the RD form -- 8 of 64 pairs.
 template <typename T, bool SET, bool PERSIST = false, int ABL = 0, bool DIAG_SKIP = false>
 __global__ __launch_bounds__(256, 2) void syrk128_kernel(GemmArgsT<T> g) {
-  static_assert(!DIAG_SKIP || (!SET && !PERSIST && ABL == 0), "DIAG_SKIP: the product trailing update only");
+  static_assert(!DIAG_SKIP || (!SET && ABL == 0), "DIAG_SKIP: the product trailing update only");
+  static_assert(!(DIAG_SKIP && PERSIST) || DBG_MASK != 0, "the persistent walk of the product instantiation: measured, not shipped (debug library only)");
   constexpr int KTe = Num<T>::KT;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* As = (T*)smem_raw;                 // [2][128][KT]
@@ -295,7 +322,8 @@ __global__ __launch_bounds__(256, 2) void syrk128_kernel(GemmArgsT<T> g) {
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   unsigned long long* const stamp = DBG_MASK ? g.stamp : nullptr;
-  // Persistent form (g.ntile > 0): the grid is a fixed number of resident workgroups, FEWER than the chip's 2-per-CU slots,
+  // Persistent form (g.ntile > 0): the grid is a fixed number of resident workgroups, FEWER than the chip's 2-per-CU slots (or, for the
+  // DIAG_SKIP instantiation under dbg 2048, exactly one per slot: measured slower than one tile per workgroup, docs/EXPERIMENTS.md),
   // each walking the flattened (member, tile) list with a stride of the grid size.  The slots left open are what the
   // panel stream's latency-chain kernels (diagonal blocks, top-block solves) start in without waiting for an update
   // workgroup to retire.  Tiles cost the same, so the static deal is balanced to within one tile.
@@ -337,16 +365,28 @@ __global__ __launch_bounds__(256, 2) void syrk128_kernel(GemmArgsT<T> g) {
     } else {
       syrk128_tile<T, SET, ABL>(Ag, g.lda, Bg, g.ldb, Cw, g.ldc, K, g.dbg, As, Bs, stamp != nullptr, ph0, ph1, tid_t);
     }
+    // stamp records: one per workgroup, or one per tile of the (member, tile) list in the persistent form
+    const size_t st_i = PERSIST ? (size_t)t : (size_t)blockIdx.y * gridDim.x + blockIdx.x, st_n = PERSIST ? (size_t)total : (size_t)gridDim.x * gridDim.y;
     if (stamp && (g.dbg & 256)) {   // phase breakdown: wait for the C stores, then {prologue, loop, epilogue} cycles of wave 0
       __builtin_amdgcn_s_waitcnt(0);
       if (tid == 0) {
-        unsigned long long* o = stamp + 2 * ((size_t)gridDim.x * gridDim.y) + 3 * (blockIdx.y * gridDim.x + blockIdx.x);
+        unsigned long long* o = stamp + 2 * st_n + 3 * st_i;
         o[0] = ph0 - st_c0; o[1] = ph1 - ph0; o[2] = __builtin_amdgcn_s_memtime() - ph1;
       }
     }
     if (stamp && tid == 0) {
-      stamp[2 * (blockIdx.y * gridDim.x + blockIdx.x)] = __builtin_amdgcn_s_memtime() - st_c0;
-      stamp[2 * (blockIdx.y * gridDim.x + blockIdx.x) + 1] = ((__builtin_amdgcn_s_memrealtime() - st_r0) << 8) | (__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xf);
+      stamp[2 * st_i] = __builtin_amdgcn_s_memtime() - st_c0;
+      stamp[2 * st_i + 1] = ((__builtin_amdgcn_s_memrealtime() - st_r0) << 8) | (__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xf);
+    }
+    if (stamp && (g.dbg & 4096) && (tid & 63) == 0) {   // timeline (with dbg 256): which CU, and when on the chip-wide 100 MHz clock, the body ran
+      unsigned long long* o = stamp + 5 * st_n + 8 * st_i;
+      const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+      if (tid == 0) {
+        o[0] = ((unsigned long long)(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xf) << 8) |
+               ((__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) >> 8) & 0xff);   // XCC_ID, HW_ID {CU_ID, SH_ID, SE_ID}
+        o[1] = st_r0;
+      }
+      o[2 + wave] = now;   // end of each wave's body
     }
     if (PERSIST) __syncthreads();   // every wave is done with the LDS buffers before the next tile's first DMA lands in them
   }

@@ -47,6 +47,35 @@ elif mode == "phases":
         for dbg in (256, 256 + 1, 256 + 8 + 16):
             lib.sigp_debug_time_syrk(h, rt, K, 0, 2, 3, C.byref(ms), C.byref(tf), dbg, C.byref(ghz))
             print("%3d %4d dbg %3d | %6.3f ms  %6.1f TFLOP/s  %.2f GHz" % (rt, K, dbg, ms.value, tf.value, ghz.value), flush=True)
+elif mode == "occupancy":
+    # dbg 1024: one workgroup per CU (96 KiB of dynamic LDS requested, same code); dbg 2048: persistent walk of the product instantiation, one
+    # workgroup per slot.  With dbg 256 the debug entry prints prologue / K loop / per-slice / epilogue cycles and the turnaround on stderr.
+    small = 2 + (16 if "f32" in sys.argv[2:] else 0)
+    for rt, K in ((127, 1024), (127, 4096)):
+        for dbg in (0, 256, 1024, 256 + 1024, 2048, 256 + 2048, 2048 + 1024, 256 + 2048 + 1024, 0):
+            rc = lib.sigp_debug_time_syrk(h, rt, K, 0, small, 3, C.byref(ms), C.byref(tf), dbg, C.byref(ghz))
+            assert rc == 0, rc
+            print("%3d %4d dbg %4d (%s, %s) | %6.3f ms  %6.1f TFLOP/s  %.2f GHz" % (rt, K, dbg, "1 wg/CU" if dbg & 1024 else "2 wg/CU",
+                  "persistent" if dbg & 2048 else "tile per wg", ms.value, tf.value, ghz.value), flush=True)
+elif mode == "timeline":
+    # dbg 4096 (+ 256): per-CU timeline of the last launch -- ramp / steady state / tail of the launch, and the share of the steady state a CU
+    # has 2 / 1 / 0 workgroups inside their body and inside their K loop (stderr).  Two tile counts tell a per-launch cost from a per-tile one.
+    small = 2 + (16 if "f32" in sys.argv[2:] else 0)
+    for rt, K in ((127, 1024), (181, 1024), (127, 4096)):
+        for dbg in (256 + 4096, 256 + 4096 + 1024, 256 + 4096 + 2048):
+            rc = lib.sigp_debug_time_syrk(h, rt, K, 0, small, 3, C.byref(ms), C.byref(tf), dbg, C.byref(ghz))
+            assert rc == 0, rc
+            print("%3d %4d dbg %4d (%s, %s) | %6.3f ms  %6.1f TFLOP/s  %.2f GHz" % (rt, K, dbg, "1 wg/CU" if dbg & 1024 else "2 wg/CU",
+                  "persistent" if dbg & 2048 else "tile per wg", ms.value, tf.value, ghz.value), flush=True)
+elif mode == "prio":
+    # dbg 8192: wave priority 3 in the C phases (and between tiles), 0 in the K loop; dbg 16384: the reverse
+    small = 2 + (16 if "f32" in sys.argv[2:] else 0)
+    for rt, K in ((127, 1024), (181, 1024)):
+        for dbg in (0, 8192, 16384, 2048, 2048 + 8192, 2048 + 16384, 0):
+            rc = lib.sigp_debug_time_syrk(h, rt, K, 0, small, 3, C.byref(ms), C.byref(tf), dbg + 256 + 4096, C.byref(ghz))
+            assert rc == 0, rc
+            print("%3d %4d dbg %5d (%s, prio %s) | %6.3f ms  %6.1f TFLOP/s  %.2f GHz" % (rt, K, dbg, "persistent" if dbg & 2048 else "tile per wg",
+                  "C phases" if dbg & 8192 else "K loop" if dbg & 16384 else "-", ms.value, tf.value, ghz.value), flush=True)
 else:
     rt, K, small = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
     lib.sigp_debug_time_syrk(h, rt, K, 0, small, 3, C.byref(ms), C.byref(tf), 0, None)
