@@ -104,6 +104,48 @@ int sigp_debug_run_hindcast_adjoint(sigp_handle* h, int64_t lead, int64_t min_tr
  * matrices overlap, which = 1 beyond the LDS limit. */
 int sigp_debug_run_hindcast_w(sigp_handle* h, int which, const double* U, const double* Cb, const double* z, const double* zbar, double* W, int n, int n_pad,
                               int64_t ld, int lead, int members, int64_t sC, int64_t sZ, int64_t c_elems, int64_t z_elems);
+
+/*
+ * Run-and-return entries of the score-gradient kernels (tests/test_hip_ard_pass.py, tests/test_hip_score_products.py), same convention: host
+ * operands in, the engine's launches through the engine's launchers, every buffer back whole; SIGP_BAD_ARG, nothing launched, for a
+ * descriptor that leaves the buffer sizes given in elements, a row or member stride that is not a multiple of 16 bytes, members whose
+ * outputs overlap, and what the kernels do not implement.  fp64 handles only.
+ *
+ * sigp_debug_run_ard_pass: ONE call of ard_tile_pass_members<wsel> -- the memset of the centred copy, ard_center_kernel and
+ * ard_grad_partial_kernel<8 | 32, wsel> (d <= 8 | d > 8, as the engine chooses) -- then the matching finish kernel (wsel = 0, ARD_W_NLML:
+ * ard_grad_finish_kernel;  1, ARD_W_LOO: loo_ard_finish_kernel).  Per member m < members (<= 8):
+ *   U        [n_pad][dp] at m sU: the scaled features, ZERO in rows >= n and columns >= d (the kernels read them); dp >= d rounded up to 16
+ *   M        [n_pad][ld] at m sP: K~^-1 (wsel 0) or the adjoint matrix (1); only the lower 128-tiles' entries (i, j), j < i < n, and the
+ *            diagonal i < n (finish kernel) enter the results
+ *   vec      wsel 0: a [n_pad] at m sVec;  wsel 1: a LooArdVecs arena at m sVec -- a at 0, v at 3 n_pad, eps at 4 n_pad (4 n_pad + 1 doubles;
+ *            beta and gamma between them are not read).  Entries >= n of a and v do not enter the results
+ *   q        wsel 0: q[m sQ] = y^T a (sf = q / n);  wsel 1: not read, may be NULL
+ *   sn, sn_m the noise factor of the last gradient component: sn_m [members] if not NULL, else sn for every member
+ *   Uc       OUT [(members - 1) sU + n_pad dp]: the centred copy as the pass left it (the entry sizes the handle's workspace itself)
+ *   partial  IN/OUT [tiles = T (T + 1), T = n_pad / 128][dp] at m sPartial: columns < d rounded up to 16 are written, the rest keeps the
+ *            caller's sentinels
+ *   grad     IN/OUT [d + 1] at m sGrad
+ * kernel_id = SIGP_KERNEL_RBF / SIGP_KERNEL_MATERN52.  n_pad a multiple of 128, <= 4096; d <= 1024.
+ */
+int sigp_debug_run_ard_pass(sigp_handle* h, int wsel, int kernel_id, int n, int n_pad, int d, int dp, int members, const double* U, int64_t sU, int64_t u_elems,
+                            const double* M, int64_t ld, int64_t sP, int64_t m_elems, const double* vec, int64_t sVec, int64_t vec_elems, const double* q, int64_t sQ,
+                            int64_t q_elems, double sn, const double* sn_m, double* Uc, double* partial, int64_t sPartial, int64_t partial_elems, double* grad,
+                            int64_t sGrad, int64_t grad_elems);
+/* ONE launch of cv_band_product_kernel through the launcher sigp_cv_grad_ard uses: C = P B on T x T 128-tiles, every tile written whole.
+ * P and C [128 T][ld] per member, both sP apart (the kernel has one member stride for the two); band [128 T][384] per member, sBand apart:
+ * row i holds the three 128-column blocks of B around its own.  Tile (bi, bj) reads block columns max(bj - 1, 0) .. min(bj + 2, T) of P's
+ * block row bi and the matching band columns of block row bj -- nothing else.  T <= 32, members <= 8.  C comes back whole. */
+int sigp_debug_run_cv_band(sigp_handle* h, const double* P, const double* band, double* C, int T, int64_t ld, int members, int64_t sP, int64_t sBand, int64_t p_elems,
+                           int64_t band_elems, int64_t c_elems);
+/* predcov_partial_kernel through the launcher sigp_predict_cov uses, then -- finish != 0 -- predcov_finish_kernel, with sigp_predict_cov's
+ * tile descriptor.  Z [m_pad][ldz >= 128 nkb]; slice s of S covers block columns [s nkb / S, (s + 1) nkb / S).  S = 1: the in-place form (the
+ * lower tiles' products go to C, part is not touched);  1 < S <= nkb: the workspace form, part [S][P][128][128], P = c (c + 1) / 2,
+ * c = m_pad / 128.  The finish step writes C = sigma_f (prior + [i == j and noise] sn - sum_s partial_s), mirrored.  Prior: the symmetric part
+ * of Kss [m_pad][ldk] if not NULL, else the unit covariance kernel_id (RBF / MATERN52, length scale ell) of Xs [m_pad][dp >= d].
+ * part [part_elems] and C [m_pad][m_pad] come in with the caller's sentinels and go back whole.  m_pad a multiple of 128, <= 2048. */
+int sigp_debug_run_predcov(sigp_handle* h, const double* Z, int64_t ldz, int m_pad, int nkb, int S, int finish, const double* Xs, int dp, int d, const double* Kss, int64_t ldk,
+                           int kernel_id, double ell, double sn, double sigma_f, int noise, double* part, double* C, int64_t z_elems, int64_t xs_elems, int64_t kss_elems,
+                           int64_t part_elems, int64_t c_elems);
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,10 @@ __global__ __launch_bounds__(256) void ard_center_kernel(const double* __restric
 //   - with the centred features, in chunks of 16:  sum_j W_ij (u_ik - u_jk)^2 = u_ik^2 rowsum(W)_i + [W (U_J o U_J)]_ik - 2 u_ik [W U_J]_ik,
 //     the two products on the matrix pipe (B operand: rows 16 t + 4 lq + c of U_J, 16 consecutive features per quarter wave);
 //   - the 16 x (4 waves x 4 quarter waves) partial sums of a chunk are added in a fixed order: partial[tile][k], no atomics.
+// The expanded square cancels at the scale of the CENTRED data's spread: a component's error is about u (spread / difference)^2 of its sum with
+// |.| inside (S).  Measured one launch at a time against long double (tests/test_hip_ard_pass.py, docs/EXPERIMENTS.md): error / S = 3e-16 for
+// N(0,1) features, 5e-16 behind an offset of 1e4 (the centring removes it), and 3.2e-9 -- ABOVE 1e-9, a factor of 3 inside the end-to-end
+// tolerance of 1e-8 -- for a feature in two clusters at +-3000 with unit scatter; an fp64 emulation of the formula gives the same 3.4e-9.
 // sf = q[0] / n is read from device memory (the fit's epilogue left y^T a there): no host round trip before the pass.
 // WSEL picks the weight: ARD_W_NLML, the adjoint of the nlML above; ARD_W_LOO, the adjoint of a leave-one-out score (looard.hpp) --
 // W = (2 M_ij + v_i a_j + a_i v_j + 2 eps a_i a_j) o h with M = P diag(gamma) P read where P is read (its lower 128-tiles), v = P beta and
@@ -53,6 +57,15 @@ __global__ __launch_bounds__(256) void ard_center_kernel(const double* __restric
 // blockIdx.y = lockstep member (sigp_nlml_grad_ard_batch, sigp_loo_grad_ard_batch): member b reads U, Uc, P, a, q (ARD_W_NLML) or v, eps
 // (ARD_W_LOO) and writes partial at b times the strides of ms (in doubles); the offsets are added to the pointers before anything is read,
 // so a member executes the instructions a single fit does.  Single fits launch one member with zero strides.
+// What each operand must hold where the formula does not reach (tests/test_hip_ard_pass.py fills the second kind with NaN):
+//   ZERO (read and used):        U in columns >= d up to dp (the staged rows and their norms take whole chunks of 4 features) and, as the
+//                                engine's staging leaves it, in rows >= n (they reach masked entries alone);  Uc in both, which the pass's
+//                                memset and ard_center_kernel see to: its padding rows are B operands of the products (0 x anything must be 0).
+//   ANYTHING (loaded at most, never used: the mask gi < n && gj + c < gi selects 0.0, it does not multiply):
+//                                P / M on and above the diagonal inside the lower 128-tiles, every 128-tile above the diagonal (not even
+//                                loaded), rows and columns >= n;  a and v from n on;  q under ARD_W_LOO, v and eps under ARD_W_NLML (null
+//                                pointers in the engine);  whatever lies between the members' strided buffers.
+//   The finish kernels read, besides the partials, the diagonal of P / M and a (v, eps) on rows < n alone.
 enum { ARD_W_NLML = 0, ARD_W_LOO = 1 };
 struct ArdMemberStrides { long U, P, a, q, partial, v, eps; };   // U and Uc alike; q: the slot's result rows (512 doubles apart); v, eps: ARD_W_LOO alone
 template <int DC, int WSEL = ARD_W_NLML>

@@ -25,6 +25,18 @@ static int cv_adj_zero(sigp_handle* h, hipStream_t st, int nb, long n_pad, const
   return SIGP_OK;
 }
 
+// ONE launch of cv_band_product_kernel for nb members: C = P B, T x T tiles each, P and C [n_pad][ld] sP apart, the band stores sBand apart.
+// cv_ard_products and the debug library's run-and-return entry (sigp_debug_run_cv_band) both launch through here.  The refusal guards the
+// tile's 32-bit DMA offsets (syrk128.hpp); it needs a row of 32 MiB, a matrix no test can allocate: it is not reached by any test.
+static int launch_cv_band_product(sigp_handle* h, hipStream_t st, int nb, const double* P, long ld, const double* band, double* Cm, int T, long sP, long sBand) {
+  if (!sy_row_stride_ok(ld, sizeof(double))) return fail(h, SIGP_BAD_ARG, "cv band product: row stride beyond the tile's 32-bit DMA offsets");
+  static AttrOnce b_attr;
+  HIPCHK(h, b_attr.set(h->device, (const void*)cv_band_product_kernel, SY_LDS_BYTES));
+  hipLaunchKernelGGL(cv_band_product_kernel, dim3((unsigned)T, (unsigned)T, (unsigned)nb), dim3(256), SY_LDS_BYTES, st, P, ld, band, Cm, ld, T, sP, sBand);
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
+
 // The gradient's steps between cv_launch (with adj) and the ARD pass, for nb lockstep members: P into gK, a, eps and v into the members'
 // vectors (w = member 0's, the others sW apart; z = the members' solved ride row 0, sZ apart), P B into gD, M = (P B) P^T into gU.  One
 // member with zero strides is the single fit.  Four profile entries, their figures times nb.
@@ -44,12 +56,7 @@ static int cv_ard_products(sigp_handle* h, hipStream_t st, int nb, long n, long 
   }
   {   // P B: tile (bi, bj) = rows bi of P against rows bj of the band store, the K window of B's three block columns
     ProfScope ps(h, st, SIGP_KC_MLII, nb * (2.0 * n_pad * n_pad * CVA_BAND), nb * (8.0 * n_pad * n_pad));
-    if (!sy_row_stride_ok(ld, sizeof(double))) return fail(h, SIGP_BAD_ARG, "cv band product: row stride beyond the tile's 32-bit DMA offsets");
-    static AttrOnce b_attr;
-    HIPCHK(h, b_attr.set(h->device, (const void*)cv_band_product_kernel, SY_LDS_BYTES));
-    hipLaunchKernelGGL(cv_band_product_kernel, dim3((unsigned)T, (unsigned)T, (unsigned)nb), dim3(256), SY_LDS_BYTES, st, (const double*)h->gK, ld, (const double*)adj.band, h->gD,
-                       ld, T, sP, adj.sBand);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = launch_cv_band_product(h, st, nb, h->gK, ld, adj.band, h->gD, T, sP, adj.sBand))) return rc;
   }
   {   // M = (P B) P^T: tile (bi, bj), bi >= bj, = rows bi of P B against rows bj of P (= its columns), the whole K span
     ProfScope ps(h, st, SIGP_KC_MLII, nb * ((double)n_pad * n_pad * (n_pad + NB)), 0.0);

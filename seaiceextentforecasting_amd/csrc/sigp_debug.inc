@@ -755,3 +755,149 @@ int sigp_debug_run_hindcast_w(sigp_handle* h, int which, const double* U, const 
   HIPCHK(h, hipMemcpy(W, dW.p, cb, hipMemcpyDeviceToHost));
   return SIGP_OK;
 }
+
+// ---- run-and-return entries of the score-gradient kernels (tests/test_hip_ard_pass.py, tests/test_hip_score_products.py) -------------------
+// Same convention: host operands in, the launches the engine issues through the launchers the engine uses, every buffer back whole;
+// SIGP_BAD_ARG, nothing launched, for a descriptor that leaves the buffer sizes given in elements, a stride that is not a multiple of
+// 16 bytes, members whose outputs overlap and what the kernels do not implement.
+static int debug_upload(sigp_handle* h, DebugDeviceBuf& b, const double* src, long elems) {
+  HIPCHK(h, hipMalloc(&b.p, (size_t)elems * sizeof(double)));
+  HIPCHK(h, hipMemcpy(b.p, src, (size_t)elems * sizeof(double), hipMemcpyHostToDevice));
+  return SIGP_OK;
+}
+
+// One call of ard_tile_pass_members<W> (its memset of ardXc, ard_center_kernel, ard_grad_partial_kernel<8 | 32, W> by d) and the matching finish
+// kernel.  wsel = ARD_W_NLML: vec = a [members][sVec], q [members][sQ] (q[0] = y^T a);  ARD_W_LOO: vec = a LooArdVecs arena per member (a at 0,
+// v at 3 n_pad, eps at 4 n_pad), q is not used.  The member strides are the engine's: ArdMemberStrides{sU, sP, sVec, sQ, sPartial, sVec, sVec}
+// and LooArdStrides{sP, 0, sVec, sPartial, sGrad}.
+int sigp_debug_run_ard_pass(sigp_handle* h, int wsel, int kernel_id, int n, int n_pad, int d, int dp, int members, const double* U, int64_t sU, int64_t u_elems,
+                            const double* M, int64_t ld, int64_t sP, int64_t m_elems, const double* vec, int64_t sVec, int64_t vec_elems, const double* q, int64_t sQ,
+                            int64_t q_elems, double sn, const double* sn_m, double* Uc, double* partial, int64_t sPartial, int64_t partial_elems, double* grad,
+                            int64_t sGrad, int64_t grad_elems) {
+  constexpr long LIM = 1L << 28;
+  if (!h || !U || !M || !vec || !Uc || !partial || !grad) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: fp64 only");
+  if (wsel != ARD_W_NLML && wsel != ARD_W_LOO) return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: wsel");
+  if (wsel == ARD_W_NLML && !q) return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: ARD_W_NLML reads q");
+  if (kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: RBF / MATERN52 only");
+  if (n < 1 || n_pad < n || n_pad % 128 || n_pad > 4096 || d < 1 || d > 1024 || dp < ((d + 15) & ~15) || dp > 4096 || members < 1 || members > 8)
+    return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: n / n_pad / d / dp / members (dp must hold d rounded up to 16 features)");
+  if (ld < n_pad || ld > LIM || sU < 0 || sP < 0 || sVec < 0 || sQ < 0 || sPartial < 0 || sGrad < 0 || std::max({sU, sP, sVec, sQ, sPartial, sGrad}) > LIM ||
+      std::max({u_elems, m_elems, vec_elems, q_elems, partial_elems, grad_elems}) > LIM || std::min({u_elems, m_elems, vec_elems, partial_elems, grad_elems}) < 1 || q_elems < 0)
+    return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: strides");
+  // 16-byte accesses: rows of U, Uc and P, the vectors a and v
+  if (dp % 2 || ld % 2 || sU % 2 || sP % 2 || sVec % 2) return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: a row or member stride is not a multiple of 16 bytes");
+  const long ntiles = kbuild_tiles(n_pad), mb1 = members - 1;
+  const long u_hi = (long)n_pad * dp - 1, m_hi = (long)(n_pad - 1) * ld + n_pad - 1, v_hi = wsel == ARD_W_LOO ? LooArdVecs::size(n_pad) - 1 : (long)n_pad - 1;
+  const long p_hi = ntiles * dp - 1;
+  if (mb1 * sU + u_hi >= u_elems || mb1 * sP + m_hi >= m_elems || mb1 * sVec + v_hi >= vec_elems || (wsel == ARD_W_NLML && mb1 * sQ >= q_elems) ||
+      mb1 * sPartial + p_hi >= partial_elems || mb1 * sGrad + d >= grad_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: the descriptor reaches outside the operand buffers");
+  if (members > 1 && (sU <= u_hi || sPartial <= p_hi || sGrad <= d)) return fail(h, SIGP_BAD_ARG, "debug_run_ard_pass: members would write the same entries");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  const long uc_elems = mb1 * sU + (long)n_pad * dp;
+  if ((rc = ensure(h, &h->ardXc, &h->cap_ardXc, uc_elems))) return rc;
+  DebugDeviceBuf dU, dM, dV, dQ, dP, dG, dS;
+  if ((rc = debug_upload(h, dU, U, u_elems)) || (rc = debug_upload(h, dM, M, m_elems)) || (rc = debug_upload(h, dV, vec, vec_elems)) ||
+      (rc = debug_upload(h, dP, partial, partial_elems)) || (rc = debug_upload(h, dG, grad, grad_elems)))
+    return rc;
+  if (q && q_elems > 0 && (rc = debug_upload(h, dQ, q, q_elems))) return rc;
+  if (sn_m && (rc = debug_upload(h, dS, sn_m, members))) return rc;
+  hipStream_t st = h->slots[0].s_upd;
+  const double* dv = (const double*)dV.p;
+  const ArdMemberStrides ms{sU, sP, sVec, sQ, sPartial, sVec, sVec};
+  if (wsel == ARD_W_NLML) {
+    if ((rc = ard_tile_pass_members<ARD_W_NLML>(h, st, members, (const double*)dU.p, n, d, dp, n_pad, ms, kernel_id, (const double*)dM.p, ld, dv, (const double*)dQ.p, nullptr,
+                                                nullptr, (double*)dP.p)))
+      return rc;
+    hipLaunchKernelGGL(ard_grad_finish_kernel, dim3((unsigned)(d + 1), (unsigned)members), dim3(256), 0, st, (const double*)dP.p, ntiles, dp, d, n, (const double*)dM.p, (long)ld,
+                       dv, (const double*)dQ.p, sn, (double*)dG.p, ms, (long)sGrad, (const double*)dS.p);
+  } else {
+    const LooArdVecs w{(double*)dV.p, n_pad};
+    if ((rc = ard_tile_pass_members<ARD_W_LOO>(h, st, members, (const double*)dU.p, n, d, dp, n_pad, ms, kernel_id, (const double*)dM.p, ld, w.a(), nullptr, w.v(), w.eps(),
+                                               (double*)dP.p)))
+      return rc;
+    hipLaunchKernelGGL(loo_ard_finish_kernel, dim3((unsigned)(d + 1), (unsigned)members), dim3(256), 0, st, (const double*)dP.p, ntiles, dp, d, n, (const double*)dM.p, (long)ld, w,
+                       sn, (double*)dG.p, LooArdStrides{sP, 0, sVec, sPartial, sGrad}, (const double*)dS.p);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(Uc, h->ardXc, (size_t)uc_elems * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(partial, dP.p, (size_t)partial_elems * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(grad, dG.p, (size_t)grad_elems * sizeof(double), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+// ONE launch of cv_band_product_kernel through launch_cv_band_product: C = P B on T x T tiles per member.  P and C [128 T][ld] per member, sP
+// apart (the kernel has ONE member stride for both); band [128 T][384] per member, sBand apart.
+int sigp_debug_run_cv_band(sigp_handle* h, const double* P, const double* band, double* Cm, int T, int64_t ld, int members, int64_t sP, int64_t sBand, int64_t p_elems,
+                           int64_t band_elems, int64_t c_elems) {
+  constexpr long LIM = 1L << 28;
+  if (!h || !P || !band || !Cm) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "debug_run_cv_band: fp64 only");
+  if (T < 1 || T > 32 || members < 1 || members > 8) return fail(h, SIGP_BAD_ARG, "debug_run_cv_band: T / members");
+  const long n_pad = (long)T * NB;
+  if (ld < n_pad || ld > LIM || sP < 0 || sBand < 0 || sP > LIM || sBand > LIM || p_elems < 1 || band_elems < 1 || c_elems < 1 || std::max({p_elems, band_elems, c_elems}) > LIM)
+    return fail(h, SIGP_BAD_ARG, "debug_run_cv_band: strides");
+  if (ld % 2 || sP % 2 || sBand % 2) return fail(h, SIGP_BAD_ARG, "debug_run_cv_band: a row or member stride is not a multiple of 16 bytes");
+  const long mb1 = members - 1, m_hi = (n_pad - 1) * ld + n_pad - 1, b_hi = n_pad * CVA_BAND - 1;
+  if (mb1 * sP + m_hi >= p_elems || mb1 * sP + m_hi >= c_elems || mb1 * sBand + b_hi >= band_elems)
+    return fail(h, SIGP_BAD_ARG, "debug_run_cv_band: the descriptor reaches outside the operand buffers");
+  if (members > 1 && sP <= m_hi) return fail(h, SIGP_BAD_ARG, "debug_run_cv_band: members would write the same entries");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  DebugDeviceBuf dP, dB, dC;
+  if ((rc = debug_upload(h, dP, P, p_elems)) || (rc = debug_upload(h, dB, band, band_elems)) || (rc = debug_upload(h, dC, Cm, c_elems))) return rc;
+  hipStream_t st = h->slots[0].s_upd;
+  if ((rc = launch_cv_band_product(h, st, members, (const double*)dP.p, ld, (const double*)dB.p, (double*)dC.p, T, sP, sBand))) return rc;
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(Cm, dC.p, (size_t)c_elems * sizeof(double), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}
+
+// predcov_partial_kernel through launch_predcov_partial, then (finish != 0) predcov_finish_kernel, with sigp_predict_cov's tile descriptor:
+// S = 1 the in-place form (the partials go to C, `part` is not touched), S > 1 the workspace form part [S][P][128][128].  Cm [m_pad][m_pad] and
+// part come in with the caller's sentinels and go back whole.  Kss [m_pad][ldk] or NULL (the prior of Xs [m_pad][dp] by kernel_id, ell).
+int sigp_debug_run_predcov(sigp_handle* h, const double* Z, int64_t ldz, int m_pad, int nkb, int S, int finish, const double* Xs, int dp, int d, const double* Kss, int64_t ldk,
+                           int kernel_id, double ell, double sn, double sigma_f, int noise, double* part, double* Cm, int64_t z_elems, int64_t xs_elems, int64_t kss_elems,
+                           int64_t part_elems, int64_t c_elems) {
+  constexpr long LIM = 1L << 28;
+  if (!h || !Z || !part || !Cm || (!Xs && !Kss)) return SIGP_BAD_ARG;
+  if (h->dtype != SIGP_F64) return fail(h, SIGP_BAD_ARG, "debug_run_predcov: fp64 only");
+  if (m_pad < NB || m_pad % NB || m_pad > 2048 || nkb < 1 || nkb > 256) return fail(h, SIGP_BAD_ARG, "debug_run_predcov: m_pad / nkb");
+  if (S < 1 || S > nkb) return fail(h, SIGP_BAD_ARG, "debug_run_predcov: 1 <= S <= nkb slices (a slice is never empty)");
+  if (!Kss && ((kernel_id != SIGP_KERNEL_RBF && kernel_id != SIGP_KERNEL_MATERN52) || !(ell > 0) || d < 1 || dp < d || dp > 4096))
+    return fail(h, SIGP_BAD_ARG, "debug_run_predcov: without Kss the prior needs RBF / MATERN52, ell > 0 and Xs [m_pad][dp >= d]");
+  const long c = m_pad / NB, P = c * (c + 1) / 2;
+  if (ldz < (long)nkb * NB || ldz > LIM || (Kss && (ldk < m_pad || ldk > LIM)) || std::max({z_elems, xs_elems, kss_elems, part_elems, c_elems}) > LIM || z_elems < 1 ||
+      part_elems < 1 || c_elems < 1)
+    return fail(h, SIGP_BAD_ARG, "debug_run_predcov: strides");
+  if (ldz % 2) return fail(h, SIGP_BAD_ARG, "debug_run_predcov: a row stride is not a multiple of 16 bytes");
+  if ((long)(m_pad - 1) * ldz + (long)nkb * NB > z_elems || (long)m_pad * m_pad > c_elems || (S > 1 && (long)S * P * NB * NB > part_elems) ||
+      (Kss && (long)(m_pad - 1) * ldk + m_pad > kss_elems) || (!Kss && (long)m_pad * dp > xs_elems))
+    return fail(h, SIGP_BAD_ARG, "debug_run_predcov: the descriptor reaches outside the operand buffers");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc;
+  DebugDeviceBuf dZ, dX, dK, dW, dC;
+  if ((rc = debug_upload(h, dZ, Z, z_elems)) || (rc = debug_upload(h, dW, part, part_elems)) || (rc = debug_upload(h, dC, Cm, c_elems))) return rc;
+  if (Kss && (rc = debug_upload(h, dK, Kss, kss_elems))) return rc;
+  if (!Kss && (rc = debug_upload(h, dX, Xs, xs_elems))) return rc;
+  hipStream_t st = h->slots[0].s_upd;
+  PredcovTiles t{};
+  t.inplace = S == 1;
+  if (t.inplace) { t.part = (double*)dC.p; t.tile_stride = 0; t.ldp = m_pad; t.slice_stride = 0; }
+  else { t.part = (double*)dW.p; t.tile_stride = (long)NB * NB; t.ldp = NB; t.slice_stride = P * NB * NB; }
+  if ((rc = launch_predcov_partial(h, st, (const double*)dZ.p, ldz, nkb, P, S, t))) return rc;
+  if (finish) {
+    PredcovFinish f{};
+    f.t = t; f.S = S; f.C = (double*)dC.p; f.ldc = m_pad; f.Xs = (const double*)dX.p; f.dp = dp; f.d = d;
+    f.Kss = (const double*)dK.p; f.ldk = ldk; f.kp = make_kparams(Kss ? SIGP_KERNEL_RBF : kernel_id, Kss ? 1.0 : ell, sn, 0); f.sigma_f = sigma_f; f.noise = noise != 0;
+    hipLaunchKernelGGL(predcov_finish_kernel, dim3((unsigned)P, 16), dim3(256), 0, st, f);
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, hipStreamSynchronize(st));
+  HIPCHK(h, hipMemcpy(part, dW.p, (size_t)part_elems * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(Cm, dC.p, (size_t)c_elems * sizeof(double), hipMemcpyDeviceToHost));
+  return SIGP_OK;
+}

@@ -17,6 +17,18 @@ static int predcov_slices(const sigp_handle* h, long P, long nkb) {
   return (int)std::max(1L, std::min(S, nkb));
 }
 
+// ONE launch of predcov_partial_kernel: P tile pairs x S slices of Z Z^T, Z [m_pad][ldz] with nkb block columns, into the tiles of t.
+// sigp_predict_cov and the debug library's run-and-return entry (sigp_debug_run_predcov) both launch through here.  The refusal guards the
+// tile's 32-bit DMA offsets (syrk128.hpp); it needs a row of 32 MiB, a matrix no test can allocate: it is not reached by any test.
+static int launch_predcov_partial(sigp_handle* h, hipStream_t st, const double* Z, long ldz, int nkb, long P, int S, const PredcovTiles& t) {
+  if (!sy_row_stride_ok(ldz, sizeof(double))) return fail(h, SIGP_BAD_ARG, "predictive covariance: row stride beyond the tile's 32-bit DMA offsets");
+  static AttrOnce attr;
+  HIPCHK(h, attr.set(h->device, (const void*)predcov_partial_kernel, SY_LDS_BYTES));
+  hipLaunchKernelGGL(predcov_partial_kernel, dim3((unsigned)P, (unsigned)S), dim3(256), SY_LDS_BYTES, st, Z, ldz, nkb, t);
+  HIPCHK(h, hipGetLastError());
+  return SIGP_OK;
+}
+
 int sigp_predict_cov(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, int noise, double* mean, double* cov, int64_t ldc) {
   if (!h) return SIGP_BAD_ARG;
   if (!Xs || !mean || !cov) return fail(h, SIGP_BAD_ARG, "predict_cov: bad argument (Xs [m][ldxs], mean [m], cov [m][ldc] required)");
@@ -99,11 +111,7 @@ int sigp_predict_cov(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, 
   else { t.part = h->covPart; t.tile_stride = (long)NB * NB; t.ldp = NB; t.slice_stride = P * NB * NB; }
   {
     ProfScope ps(h, st, SIGP_KC_EPILOGUE, (double)P * 2.0 * NB * NB * n_pad, 8.0 * P * (2.0 * NB * n_pad + (double)S * NB * NB), (int)(n_pad / S));
-    if (!sy_row_stride_ok(ld, sizeof(double))) return fail(h, SIGP_BAD_ARG, "predictive covariance: row stride beyond the tile's 32-bit DMA offsets");
-    static AttrOnce attr;
-    HIPCHK(h, attr.set(h->device, (const void*)predcov_partial_kernel, SY_LDS_BYTES));
-    hipLaunchKernelGGL(predcov_partial_kernel, dim3((unsigned)P, (unsigned)S), dim3(256), SY_LDS_BYTES, st, (const double*)h->covZ, ld, (int)nkb, t);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = launch_predcov_partial(h, st, h->covZ, ld, (int)nkb, P, S, t))) return rc;
   }
   {
     PredcovFinish f{};
