@@ -555,13 +555,33 @@ int sigp_small_run_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_in
  * fits in LDS at feature chunk 8 -- leave-one-out: n <= 128 up to m = 6, n <= 127 at m = 7, 8; hindcast at lead = 1: n <= 128 up to m = 5,
  * n <= 127 above, and at n = 128, m = 0 up to lead = 6 -- for the LARGEST n and m uploaded.  SIGP_BAD_ARG: what the score entry refuses, a
  * bad criterion, and a launch beyond these limits.  To fit, the launch may build K~ from shorter feature chunks than the score entry does
- * (as sigp_small_run_cv); the bytes then agree where no set has more features than the chunk.  Not covered: leave-block-out gradients. */
+ * (as sigp_small_run_cv); the bytes then agree where no set has more features than the chunk.  The leave-block-out scores: sigp_small_run_cv_grad (below). */
 int sigp_small_run_loo_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int sigma_mode,
                             int criterion, double* out8, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var,
                             int64_t nstride);
 int sigp_small_run_hindcast_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t lead,
                                  int64_t min_train, int sigma_mode, int criterion, double* out8, double* mean, double* var, int64_t mstride,
                                  double* hc_mean, double* hc_var, int64_t nstride);
+/* Gradients of the leave-block-out scores in the one-workgroup kernel: sigp_small_run_cv with `criterion` (SIGP_LOO_NLPD / SIGP_LOO_SSE) added, in
+ * the same single launch, one workgroup per fit.  out8 [nprob][8] = the six outputs of sigp_small_run_cv, then d S / d log l and d S / d log sn~
+ * of the score the criterion names, (l, sn~) held and sigma_f re-profiled per fold as sigma_mode says; out8[0..5], mean / var and cv_mean /
+ * cv_var carry the bytes sigp_small_run_cv returns for the same arguments.  The adjoint is sigp_cv_grad_ard's (G = 1/2 (v a^T + a v^T) + P B P +
+ * eps a a^T), contracted as sigp_small_run_loo_grad contracts its own: with X = L~^-1, G = X^T C X, C = 1/2 (u z^T + z u^T) + X B X^T + eps z z^T,
+ * u = X beta, and b^T C b = (b.u)(b.z) + p^T B p + eps (b.z)^2 with p = X^T b, summed over b = X a_c (weights l dw_c) and over the columns of X
+ * (weight sn~).  Per fold H = P_SS^-1, t = H rbar, beta_f, B_f and eps_f are formed in LDS behind the fold's scores; B, symmetric with
+ * |i - j| < block + 2 gap, is kept as its lower band [n][block + 2 gap].  Folds run one after the other and every entry is added by one thread:
+ * overlapping windows add in ascending fold order, no atomics, the same bits on every run and whatever a fit's place in the queue.
+ * lam_mode 1 sets without sigp_small_set_dweights: NaN in d S / d log l alone.  A non-SPD K~ or a failed pivot of a fold's P_SS: +inf in
+ * out8[4..7] (the latter with NaN rows, as sigp_small_run_cv).
+ * Limits (SmallLayout, smallgp_layout.hpp) for the LARGEST n and m uploaded: every n <= 96 with every m <= 8 at every window block + 2 gap <=
+ * SIGP_CV_SMALL_MAX_WINDOW; beyond that what fits in LDS at feature chunk 8 -- at m = 0 n <= 123 / 121 / 119 / 116 / 109 for windows
+ * 1 / 5 / 8 / 16 / 32, at m = 8 n <= 119 / 117 / 115 / 113 / 106.  SIGP_BAD_ARG: what sigp_small_run_cv refuses, a bad criterion, and a launch
+ * beyond these limits (the message names n, m, the window and the bytes).  To fit, the launch may build K~ from shorter feature chunks than
+ * sigp_small_run_cv does; the bytes then agree where both use the same chunk or no set has more features than this launch's chunk.  The seven
+ * other instantiations of the kernel keep their instructions. */
+int sigp_small_run_cv_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block,
+                           int64_t gap, int sigma_mode, int criterion, double* out8, double* mean, double* var, int64_t mstride, double* cv_mean,
+                           double* cv_var, int64_t nstride);
 /* The hindcast scores AND the exact derivatives of one of them with respect to theta = (log l_1 .. log l_d, log sn~) (RBF / Matern-5/2,
  * fp64), so that the length scales can be chosen by the score the retro loop reports (September1st_retro.py:176-248) instead of a grid.
  * theta, ntheta = d + 1, criterion (SIGP_LOO_NLPD / SIGP_LOO_SSE) and mean / var [n] (both or neither) as sigp_loo_grad_ard.  Sets the

@@ -59,9 +59,9 @@ int sigp_small_set_dweights(sigp_handle* h, const double* dlam_pool, int64_t cou
 struct SmallRequest {
   SmallFlavour flavour = SmallFlavour::Plain;
   int sigma_mode = 0;                                  // Loo, Cv, Hindcast: SIGP_LOO_REFIT / SIGP_LOO_FIXED
-  int64_t block = 0, gap = 0;                          // Cv
+  int64_t block = 0, gap = 0;                          // Cv, CvGrad
   int64_t lead = 0, min_train = 0;                     // Hindcast, HindcastGrad
-  int criterion = 0;                                   // LooGrad, HindcastGrad: SIGP_LOO_NLPD / SIGP_LOO_SSE
+  int criterion = 0;                                   // LooGrad, HindcastGrad, CvGrad: SIGP_LOO_NLPD / SIGP_LOO_SSE
   double *row_mean = nullptr, *row_var = nullptr;      // Loo, Cv, Hindcast: the caller's [nprob][pitch]
   int64_t pitch = 0;
 };
@@ -92,6 +92,12 @@ static void small_count_flops(double& fl, const SmallSet& s, const SmallRequest&
     // ... then X, b_c = X a_c and x_c^T C x_c: Loo X^T b_c and the lower triangle of P; Hindcast the band and the scan against every column
     case SmallFlavour::LooGrad: fl += 2.0 * inverse + 2.0 * n * n + 2.0 * n * n * s.N + 4.0 * n * (s.N + n); break;
     case SmallFlavour::HindcastGrad: fl += 4.0 * n * rq.lead + 2.0 * n * n + inverse + n * n * s.N + (8.0 * rq.lead + 5.0) * n * (s.N + n); break;
+    // Cv's, then per fold H and B_f, b_c = X a_c, p_c = X^T b_c for the features and for X's own columns (P) and the band against every p_c
+    case SmallFlavour::CvGrad: {
+      const double wd = rq.block + 2.0 * rq.gap;
+      fl += inverse + 2.0 * n * n + n * n * wd + (n / rq.block) * (wd * wd * wd / 3 + wd * wd * rq.block) + 2.0 * n * n * s.N + inverse + (2.0 * wd + 4.0) * n * (s.N + n);
+      break;
+    }
   }
 }
 
@@ -99,7 +105,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
                           double* mean, double* var, int64_t mstride, const SmallRequest& rq) {
   if (!h || h->sm_sets.empty()) return fail(h, SIGP_BAD_ARG, "small_run: call sigp_small_upload first");
   const SmallFlavour F = rq.flavour;
-  const bool cv = F == SmallFlavour::Cv, hc = F == SmallFlavour::Hindcast || F == SmallFlavour::HindcastGrad, rows = small_has_rows(F);
+  const bool cv = F == SmallFlavour::Cv || F == SmallFlavour::CvGrad, hc = F == SmallFlavour::Hindcast || F == SmallFlavour::HindcastGrad, rows = small_has_rows(F);
   const char* cvloo = cv ? "cv" : "loo";
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
   if (rows && (!rq.row_mean || !rq.row_var || rq.pitch < h->sm_nmax)) {
@@ -108,7 +114,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   }
   // the leave-block-out launch picks its own feature chunk: the largest of {the upload's, 16, 8} whose image leaves room for the folds
   int ch = h->sm_ch; long lds = h->sm_lds;
-  if (cv) {
+  if (F == SmallFlavour::Cv) {
     ch = small_pick_chunk(h->sm_nmax, h->sm_mmax, F, h->sm_ch);
     lds = SmallLayout{h->sm_nmax, h->sm_mmax, ch ? ch : 8, F}.bytes();
     if (!ch)
@@ -116,7 +122,18 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
                   lds - SmallLayout{h->sm_nmax, h->sm_mmax, 8, SmallFlavour::Plain}.bytes(), lds, SM_LDS_MAX);
   }
   // so do the score gradients, whose image adds Bc, gv and (hindcast) the saved band
-  if (small_is_score_grad(F)) {
+  // ... and the leave-block-out gradient, whose image has the folds' scratch as well and the band of the adjoint, block + 2 gap wide
+  if (F == SmallFlavour::CvGrad) {
+    const int64_t window = rq.block > SIGP_CV_SMALL_MAX_WINDOW || rq.gap > SIGP_CV_SMALL_MAX_WINDOW ? SIGP_CV_SMALL_MAX_WINDOW + 1 : rq.block + 2 * rq.gap;
+    if (window > SIGP_CV_SMALL_MAX_WINDOW)
+      return fail(h, SIGP_BAD_ARG, "small_run_cv_grad: block = %lld, gap = %lld: the window block + 2 gap is at most SIGP_CV_SMALL_MAX_WINDOW = %d", (long long)rq.block, (long long)rq.gap,
+                  SIGP_CV_SMALL_MAX_WINDOW);
+    ch = small_pick_chunk(h->sm_nmax, h->sm_mmax, F, h->sm_ch, (int)window);
+    lds = SmallLayout{h->sm_nmax, h->sm_mmax, ch ? ch : 8, F, (int)window}.bytes();
+    if (!ch)
+      return fail(h, SIGP_BAD_ARG, "small_run_cv_grad: n = %d with m = %d and window = %d needs %ld bytes of LDS at feature chunk 8; the limit is %ld (every n <= 96 with m <= %d and window <= %d fits)",
+                  h->sm_nmax, h->sm_mmax, (int)window, lds, SM_LDS_MAX, SM_MMAX, SIGP_CV_SMALL_MAX_WINDOW);
+  } else if (small_is_score_grad(F)) {
     const int lead = hc ? (int)rq.lead : 0;
     ch = small_pick_chunk(h->sm_nmax, h->sm_mmax, F, h->sm_ch, lead);
     lds = SmallLayout{h->sm_nmax, h->sm_mmax, ch ? ch : 8, F, lead}.bytes();
@@ -180,6 +197,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
       case SmallFlavour::Hindcast: launch = small_launch<256, SmallFlavour::Hindcast>; break;
       case SmallFlavour::LooGrad: launch = small_launch<256, SmallFlavour::LooGrad>; break;
       case SmallFlavour::HindcastGrad: launch = small_launch<256, SmallFlavour::HindcastGrad>; break;
+      case SmallFlavour::CvGrad: launch = small_launch<256, SmallFlavour::CvGrad>; break;
     }
     HIPCHK(h, launch(h, st, nprob, lds, ch, d_out, d_mean, d_var, (int)ms, x));
   }
@@ -277,6 +295,19 @@ int sigp_small_run_hindcast_grad(sigp_handle* h, int64_t nprob, const int64_t* s
   SmallRequest rq;
   rq.flavour = SmallFlavour::HindcastGrad; rq.sigma_mode = sigma_mode; rq.criterion = criterion; rq.lead = lead; rq.min_train = min_train;
   rq.row_mean = hc_mean; rq.row_var = hc_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, rq);
+}
+
+// sigp_small_run_cv, then the derivatives of one of its two scores in the same single launch (SmallFlavour::CvGrad: the adjoint of cvard.hpp fold by fold,
+// its B kept as a band in LDS)
+int sigp_small_run_cv_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block, int64_t gap, int sigma_mode,
+                           int criterion, double* out8, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_cv_grad: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (criterion != SIGP_LOO_NLPD && criterion != SIGP_LOO_SSE) return fail(h, SIGP_BAD_ARG, "small_run_cv_grad: criterion must be SIGP_LOO_NLPD or SIGP_LOO_SSE");
+  if (block < 1 || gap < 0) return fail(h, SIGP_BAD_ARG, "small_run_cv_grad: block >= 1 and gap >= 0 required");
+  SmallRequest rq;
+  rq.flavour = SmallFlavour::CvGrad; rq.sigma_mode = sigma_mode; rq.criterion = criterion; rq.block = block; rq.gap = gap;
+  rq.row_mean = cv_mean; rq.row_var = cv_var; rq.pitch = nstride;
   return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, rq);
 }
 

@@ -63,6 +63,14 @@
 // The band L~(t, s_t..t) is saved in hb before the inverse overwrites L~.  Every thread adds its terms in a fixed order and smallgp_allsum adds
 // the threads: the same bits on every run.  lam_mode 1 sets without dweights: NaN in dS/dlog l alone.
 //
+// CvGrad (8 outputs): Cv's six -- the same statements in the same order --, then the derivative of the score x.crit with the adjoint of cvard.hpp:
+// per fold H = P_SS^-1 = W^T W (over M in Pw), rbar, kappa on the scored rows, t = H rbar, sbar = sum kappa_i H_ii,
+//     beta_f = -t [+ refit: 2 sbar r / (n - w)],   B_f = (t r^T + r t^T)/2 + s H diag(kappa) H [- refit: sbar r r^T / (n - w)],   eps_f = -sbar / (n - w) or -sbar / n,
+// beta into gv[0], the lower band of B = sum_f E_f B_f E_f^T into hb [n][block + 2 gap], fold after fold, every entry added by one thread: overlapping
+// windows add in ascending fold order.  C = (u z^T + z u^T)/2 + X B X^T + eps z z^T, u = X beta, so
+//     b^T C b = (u.b)(z.b) + p^T B p + eps (z.b)^2,   p = X^T b  (a vector in Ac, free once Bc is staged, before the band is summed)
+// over b_c = X a_c and over the columns of X, ch at a time.  A failed pivot of a P_SS: +inf in out[4..7] and NaN rows.
+//
 // NT = threads per workgroup: 256 (four wavefronts per fit) is the default at every order; NT = 64 (one wavefront per fit, every
 // barrier of the column loop a wave-local no-op) is kept as a measurement switch ("small_nt64") -- on the reference-size grid it
 // is SLOWER (1.71 vs 1.02 ms for 48 000 fits of n = 6 .. 45): the rank-1 updates have ~n^2/2 elements, enough for four waves,
@@ -94,9 +102,9 @@ struct SmallExtras {
   double* row_var;
   int pitch;
   int sigma_fixed;         // Loo, Cv, Hindcast: 0 = sigma_f re-profiled without the rows left out, 1 = the full fit's sigma_f
-  int block, gap;          // Cv
+  int block, gap;          // Cv, CvGrad
   int lead, min_train;     // Hindcast
-  int crit;                // LooGrad, HindcastGrad: the score that is differentiated, 0 = nlpd, 1 = sse (SIGP_LOO_NLPD / SIGP_LOO_SSE)
+  int crit;                // LooGrad, HindcastGrad, CvGrad: the score that is differentiated, 0 = nlpd, 1 = sse (SIGP_LOO_NLPD / SIGP_LOO_SSE)
 };
 
 // one workgroup's fit: its sizes, its pieces in LDS and this thread's place in the 16-wide element mapping
@@ -345,10 +353,21 @@ __device__ __forceinline__ void smallgp_tail_loo(const SmallFit& w, const SmallE
   smallgp_write_scores<NT>(w, tn, ts, o);
 }
 
+// kappa = d nlpd / d var, rho = d nlpd / d r of a scored row with residual r and variance v; for the sse 0 and 2 r
+__device__ __forceinline__ void small_kappa_rho(int crit, double r, double v, double& kappa, double& rho) {
+  if (crit == 0) { kappa = 1.0 / (2.0 * v) - r * r / (2.0 * v * v); rho = r / v; }
+  else { kappa = 0.0; rho = 2.0 * r; }
+}
+
 // Pw, Ww, tv: the folds' scratch behind the plain layout (SmallLayout)
-template <int NT>
-__device__ __forceinline__ void smallgp_tail_cv(const SmallFit& w, const SmallExtras& x, double* Pw, double* Ww, double* tv, const double* __restrict__ y,
-                                                double zz, double sf, double* o, double* __restrict__ rmean, double* __restrict__ rvar) {
+// KEEP: the adjoint of cvard.hpp fold by fold for the gradient -- beta into gv[0], the lower band of B into bb [n][wb] (bb(i, i - j), wb = block + 2 gap),
+// eps returned; gv[1], gv[2], gv[3] hold a fold's r, rbar and kappa, Pw its H = W^T W once M is dead, tv its t = H rbar once t0 = W a~_S is.  Folds
+// run one after the other and within a fold every entry belongs to one thread: overlapping windows add in ascending fold order.  Returns
+// whether a fold's P_SS failed its pivot test.
+template <int NT, bool KEEP = false>
+__device__ __forceinline__ bool smallgp_tail_cv(const SmallFit& w, const SmallExtras& x, double* Pw, double* Ww, double* tv, const double* __restrict__ y,
+                                                double zz, double sf, double* o, double* __restrict__ rmean, double* __restrict__ rvar, double* gv = nullptr,
+                                                double* bb = nullptr, double* eps_out = nullptr) {
   const int n = w.n, ldk = w.ldk, tid = w.tid;
   const double qnan = __builtin_nan("");
   const double* Kp = w.Kp;
@@ -356,6 +375,12 @@ __device__ __forceinline__ void smallgp_tail_cv(const SmallFit& w, const SmallEx
   __shared__ int s_cvbad;
   if (tid == 0) s_cvbad = 0;
   smallgp_atilde<NT>(w);
+  const int wb = x.block + 2 * x.gap;
+  double eps = 0.0;
+  if constexpr (KEEP) {
+    for (int i = tid; i < n; i += NT) gv[i] = 0.0;
+    for (int e = tid; e < n * wb; e += NT) bb[e] = 0.0;
+  }
   __syncthreads();
   double tn = 0.0, ts = 0.0;
   const int F = (n + x.block - 1) / x.block;
@@ -398,12 +423,57 @@ __device__ __forceinline__ void smallgp_tail_cv(const SmallFit& w, const SmallEx
         rvar[gi] = v;
         tn += 0.5 * log(2.0 * M_PI * v) + r * r / (2.0 * v);
         ts = fma(r, r, ts);
+        if constexpr (KEEP) small_kappa_rho(x.crit, r, v, gv[3 * n + tid], gv[2 * n + tid]);
+      } else if constexpr (KEEP) {
+        gv[2 * n + tid] = 0.0; gv[3 * n + tid] = 0.0;
       }
+      if constexpr (KEEP) gv[n + tid] = r;
     }
     __syncthreads();
+    if constexpr (KEEP) {
+      const double *fr = gv + n, *frb = gv + 2 * n, *fk = gv + 3 * n;
+      const int cl = c0 - r0, ch = c1 - r0;             // the scored rows within the window
+      const double nw = (double)(n - wd);
+      double tt = 0.0;                                  // as the scoring thread summed it
+      for (int k = 0; k < wd; ++k) tt = fma(tv[k], tv[k], tt);
+      const double s = x.sigma_fixed ? sf : (zz - tt) / nw;
+      for (int e = tid; e < wd * wd; e += NT) {         // H = W^T W over M, both triangles
+        const int i = e / wd, j = e - i * wd;
+        if (j <= i) {
+          double hij = 0.0;
+          for (int k = i; k < wd; ++k) hij = fma(Ww[k * SM_CVP + i], Ww[k * SM_CVP + j], hij);
+          Pw[i * SM_CVP + j] = hij;
+          Pw[j * SM_CVP + i] = hij;
+        }
+      }
+      __syncthreads();
+      double sbar = 0.0;
+      for (int k = cl; k < ch; ++k) sbar = fma(fk[k], Pw[k * SM_CVP + k], sbar);
+      if (tid < wd) {
+        double t = 0.0;
+        for (int k = cl; k < ch; ++k) t = fma(Pw[tid * SM_CVP + k], frb[k], t);
+        tv[tid] = t;
+      }
+      __syncthreads();
+      const double sr = x.sigma_fixed ? 0.0 : sbar / nw;
+      if (tid < wd) gv[r0 + tid] += fma(2.0 * sr, fr[tid], -tv[tid]);
+      for (int e = tid; e < wd * wd; e += NT) {
+        const int i = e / wd, j = e - i * wd;
+        if (j <= i) {
+          double hk = 0.0;
+          for (int k = cl; k < ch; ++k) hk = fma(Pw[i * SM_CVP + k] * fk[k], Pw[k * SM_CVP + j], hk);
+          bb[(r0 + i) * wb + i - j] += 0.5 * (tv[i] * fr[j] + fr[i] * tv[j]) + s * hk - sr * fr[i] * fr[j];
+        }
+      }
+      eps -= x.sigma_fixed ? sbar / (double)n : sr;
+      __syncthreads();
+    }
   }
-  if (smallgp_write_scores<NT>(w, tn, ts, o, &s_cvbad))
+  const bool failed = smallgp_write_scores<NT>(w, tn, ts, o, &s_cvbad);
+  if (failed)
     for (int i = tid; i < n; i += NT) { rmean[i] = qnan; rvar[i] = qnan; }
+  if constexpr (KEEP) *eps_out = eps;
+  return failed;
 }
 
 template <int NT>
@@ -458,12 +528,7 @@ __device__ __forceinline__ void smallgp_tail_grad(const SmallFit& w, const Small
   }
 }
 
-// ---- the score gradients (LooGrad, HindcastGrad) -----------------------------------------------------------------------------------------------
-// kappa = d nlpd / d var, rho = d nlpd / d r of a scored row with residual r and variance v; for the sse 0 and 2 r
-__device__ __forceinline__ void small_kappa_rho(int crit, double r, double v, double& kappa, double& rho) {
-  if (crit == 0) { kappa = 1.0 / (2.0 * v) - r * r / (2.0 * v * v); rho = r / v; }
-  else { kappa = 0.0; rho = 2.0 * r; }
-}
+// ---- the score gradients (LooGrad, HindcastGrad, CvGrad) ----------------------------------------------------------------------------------------
 
 // dw of the chunk's features into wk and the chunk's raw columns into Ac (as the Grad tail stages them), then Bc(i, c) = sum_{k <= i} X(i, k) Ac(k, c);
 // a barrier ahead of the staging and one behind Bc
@@ -633,6 +698,69 @@ __device__ __forceinline__ void smallgp_tail_hindcast_grad(const SmallFit& w, co
   if (tid == 0) { o[6] = pb.ell * G1; o[7] = pb.sn * G0; }
 }
 
+// this thread's share of sum_c wc_c b_c^T C b_c over the ncol <= ch columns of b [n][ldb] for the leave-block-out C (wc = nullptr: weights 1):
+// (u.b)(z.b) + p^T B p + eps (z.b)^2 with p = X^T b, which goes through Ac one column per thread element first (B is a band: p has to exist as a
+// vector).  first: column c of b is zero above row first + c (b = columns first .. of X itself; 0 and b dense otherwise).  A barrier ahead of p
+// (the last slab's readers) and one behind it.
+template <int NT>
+__device__ __forceinline__ double smallgp_quad_cv(const SmallFit& w, const double* b, int ldb, int ncol, const double* wc, int first, bool tri, const double* bb, int wb,
+                                                  const double* u, double eps) {
+  const int n = w.n, ldk = w.ldk, lda = w.lda, tid = w.tid;
+  const double* z = w.z;
+  double* p = w.Ac;
+  __syncthreads();
+  for (int e = tid; e < n * ncol; e += NT) {
+    const int j = e / ncol, c = e - j * ncol;
+    const int k0 = tri ? max(j, first + c) : j;
+    double a = 0.0;
+    for (int k = k0; k < n; ++k) a = fma(w.Kp[k * ldk + j], b[k * ldb + c], a);
+    p[j * lda + c] = a;
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int e = tid; e < n * ncol; e += NT) {              // row i of B against p_c: the diagonal once, the band below it for both triangles
+    const int i = e / ncol, c = e - i * ncol;
+    const double* bi = bb + i * wb;
+    const int dmax = min(i, wb - 1);
+    double q = 0.0;
+    for (int d = 1; d <= dmax; ++d) q = fma(bi[d], p[(i - d) * lda + c], q);
+    const double pi = p[i * lda + c];
+    acc = fma((wc ? wc[c] : 1.0) * pi, fma(bi[0], pi, 2.0 * q), acc);
+  }
+  for (int c = tid; c < ncol; c += NT) {
+    double ub = 0.0, zb = 0.0;
+    for (int i = tri ? first + c : 0; i < n; ++i) { const double bi = b[i * ldb + c]; ub = fma(u[i], bi, ub); zb = fma(z[i], bi, zb); }
+    acc = fma(wc ? wc[c] : 1.0, ub * zb + eps * zb * zb, acc);
+  }
+  return acc;
+}
+
+// after smallgp_invert and smallgp_tail_cv<NT, true> (beta in gv[0], the band in bb, eps): o[6], o[7]
+template <int NT>
+__device__ __forceinline__ void smallgp_tail_cv_grad(const SmallFit& w, const SmallSet& st, const SmallProb& pb, const SmallExtras& x, const double* __restrict__ A,
+                                                     const double* __restrict__ lam, const double* __restrict__ dlam, double* Bc, double* gv, const double* bb, double eps,
+                                                     double* o) {
+  const int n = w.n, N = w.N, ldk = w.ldk, ch = w.ch, tid = w.tid, wb = x.block + 2 * x.gap;
+  const double* beta = gv;
+  double* u = gv + n;
+  for (int i = tid; i < n; i += NT) {                     // the fold loop ended on a barrier: beta is complete, a fold's r is dead
+    double a = 0.0;
+    for (int k = 0; k <= i; ++k) a = fma(w.Kp[i * ldk + k], beta[k], a);
+    u[i] = a;
+  }
+  double g1 = 0.0;
+  for (int k0 = 0; k0 < N; k0 += ch) {
+    const int kc = min(ch, N - k0);
+    smallgp_stage_b<NT>(w, st, pb, A, lam, dlam, k0, kc, Bc);
+    g1 += smallgp_quad_cv<NT>(w, Bc, w.lda, kc, w.wk, 0, false, bb, wb, u, eps);
+  }
+  double g0 = 0.0;
+  for (int c0 = 0; c0 < n; c0 += ch) g0 += smallgp_quad_cv<NT>(w, w.Kp + c0, ldk, min(ch, n - c0), nullptr, c0, true, bb, wb, u, eps);
+  const double G1 = smallgp_allsum<NT>(g1, w.red);
+  const double G0 = smallgp_allsum<NT>(g0, w.red);
+  if (tid == 0) { o[6] = pb.ell * G1; o[7] = pb.sn * G0; }
+}
+
 template <int NT, SmallFlavour F>
 __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict__ sets, const SmallProb* __restrict__ probs,
                                                       const double* __restrict__ Apool, const double* __restrict__ ypool,
@@ -643,7 +771,7 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
   __shared__ int s_info;
   const SmallProb pb = probs[blockIdx.x];
   const SmallSet st = sets[pb.set];
-  const SmallLayout lay{st.n, st.m, ch, F, F == SmallFlavour::HindcastGrad ? x.lead : 0};
+  const SmallLayout lay{st.n, st.m, ch, F, F == SmallFlavour::HindcastGrad ? x.lead : F == SmallFlavour::CvGrad ? x.block + 2 * x.gap : 0};
   double* lds = (double*)smem_raw;
   SmallFit w;
   w.n = st.n; w.N = st.N; w.m = st.m; w.R = lay.rows();
@@ -675,6 +803,14 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
       smallgp_invert<NT>(w);
       smallgp_tail_loo<NT, true>(w, x, y, zz, sf, o, rmean, rvar, lds + lay.gv());
       smallgp_tail_loo_grad<NT>(w, st, pb, x, A, lam, dlam, lds + lay.Bc(), lds + lay.gv(), zz, sf, o);
+    } else if constexpr (F == SmallFlavour::CvGrad) {
+      smallgp_invert<NT>(w);
+      double eps;
+      if (smallgp_tail_cv<NT, true>(w, x, lds + lay.Pw(), lds + lay.Ww(), lds + lay.tv(), y, zz, sf, o, rmean, rvar, lds + lay.gv(), lds + lay.hb(), &eps)) {
+        if (w.tid == 0) { o[6] = __builtin_huge_val(); o[7] = __builtin_huge_val(); }
+        return;                        // uniform
+      }
+      smallgp_tail_cv_grad<NT>(w, st, pb, x, A, lam, dlam, lds + lay.Bc(), lds + lay.gv(), lds + lay.hb(), eps, o);
     } else {
       smallgp_invert<NT>(w);
       if constexpr (F == SmallFlavour::Cv) smallgp_tail_cv<NT>(w, x, lds + lay.Pw(), lds + lay.Ww(), lds + lay.tv(), y, zz, sf, o, rmean, rvar);

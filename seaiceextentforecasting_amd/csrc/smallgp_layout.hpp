@@ -26,11 +26,13 @@ constexpr long SM_LDS_MAX = 160 * 1024 - 64;   // bytes of dynamic LDS one workg
 //   Loo       the leave-one-out predictions and scores
 //   Cv        the leave-block-out predictions and scores
 //   Hindcast  the expanding-window hindcast predictions and scores
-//   LooGrad / HindcastGrad   what Loo / Hindcast form, then the derivatives of one of the two scores w.r.t. (log l, log sn~)
-enum class SmallFlavour { Plain, Grad, Loo, Cv, Hindcast, LooGrad, HindcastGrad };
+//   LooGrad / HindcastGrad / CvGrad   what Loo / Hindcast / Cv form, then the derivatives of one of the two scores w.r.t. (log l, log sn~)
+enum class SmallFlavour { Plain, Grad, Loo, Cv, Hindcast, LooGrad, HindcastGrad, CvGrad };
 
 // does the flavour differentiate a row score?
-__host__ __device__ constexpr bool small_is_score_grad(SmallFlavour f) { return f == SmallFlavour::LooGrad || f == SmallFlavour::HindcastGrad; }
+__host__ __device__ constexpr bool small_is_score_grad(SmallFlavour f) {
+  return f == SmallFlavour::LooGrad || f == SmallFlavour::HindcastGrad || f == SmallFlavour::CvGrad;
+}
 // doubles per fit of `out`
 __host__ __device__ constexpr int small_out_width(SmallFlavour f) { return f == SmallFlavour::Plain ? 4 : f == SmallFlavour::Grad || small_is_score_grad(f) ? 8 : 6; }
 // does the flavour write a prediction per training row (mean / var [nprob][pitch]) and the scores out[4], out[5]?
@@ -46,7 +48,7 @@ __host__ __device__ constexpr bool small_has_rows(SmallFlavour f) {
 //   kss [SM_MMAX]            k~**_j
 //   red [SM_RED]             reduction scratch
 //   at  [n]                  a~ = L~^-T z, then SM_SLACK doubles
-//   Cv alone, behind all of that:
+//   Cv and CvGrad, behind all of that:
 //   Pw  [SM_CVW][SM_CVP]     a fold's P_SS, then its factor M (lower)
 //   Ww  [SM_CVW][SM_CVP]     W = M^-1 (lower)
 //   tv  [SM_CVW]             t = W a~_S
@@ -54,14 +56,20 @@ __host__ __device__ constexpr bool small_has_rows(SmallFlavour f) {
 //   Bc  [n][lda]             b_c = X a_c for the chunk's columns (X = L~^-1): what the Grad tail forms and does not keep
 //   gv  [SM_GV][n]           the adjoint's vectors: Loo g, beta, gamma, u = X beta;  Hindcast rho, 2 kappa sigma, kappa w / s, zbar
 //   hb  [n][lead]            HindcastGrad alone: the band L~(t, s_t .. t), saved before the inverse overwrites L~
+//   CvGrad: Pw, Ww and tv at Cv's own offsets, and behind tv
+//   Bc  [n][lda]             as above; once it is staged Ac is free and holds p_c = X^T b_c of the chunk's columns
+//   gv  [SM_GV][n]           beta, then per fold r, rbar, kappa (a window has fewer than n rows); u = X beta after the folds
+//   hb  [n][lead]            the lower band of the adjoint's B, bb(i, i - j), lead = block + 2 gap <= SM_CVW
 // Limits of the two (every order the upload takes is laid out; what does not fit in SM_LDS_MAX at feature chunk 8 is refused):
 //   every order n <= 96 with every m <= SM_MMAX fits, HindcastGrad at every lead <= SIGP_HINDCAST_SMALL_MAX_LEAD = 32 (chunk 32 throughout);
 //   beyond that whatever bytes() <= SM_LDS_MAX admits: LooGrad n <= 128 up to m = 6 and n <= 127 at m = 7, 8;  HindcastGrad at lead = 1
 //   n <= 128 up to m = 5 and n <= 127 at m = 6 .. 8, and at n = 128, m = 0 up to lead = 6.
+// CvGrad: every order n <= 96 with every m <= SM_MMAX fits at every window <= SM_CVW (at n = 96, m = 8: chunk 32 up to window 10, chunk 16 beyond);
+//   above that what fits at chunk 8: at m = 0 n <= 123 / 121 / 119 / 116 / 109 for windows 1 / 5 / 8 / 16 / 32, at m = 8 n <= 119 / 117 / 115 / 113 / 106.
 struct SmallLayout {
   int n, m, ch;
   SmallFlavour flavour;
-  int lead = 0;                                // HindcastGrad: the pitch of hb
+  int lead = 0;                                // the pitch of hb: HindcastGrad the lead, CvGrad the window block + 2 gap
   __host__ __device__ constexpr int rows() const { return n + 1 + m; }
   __host__ __device__ constexpr int ldk() const { return n | 1; }
   __host__ __device__ constexpr int lda() const { return ch + 1; }
@@ -74,17 +82,17 @@ struct SmallLayout {
   __host__ __device__ constexpr long Pw() const { return at() + n + SM_SLACK; }
   __host__ __device__ constexpr long Ww() const { return Pw() + SM_CVW * SM_CVP; }
   __host__ __device__ constexpr long tv() const { return Ww() + SM_CVW * SM_CVP; }
-  __host__ __device__ constexpr long Bc() const { return Pw(); }
+  __host__ __device__ constexpr long Bc() const { return flavour == SmallFlavour::CvGrad ? tv() + SM_CVW : Pw(); }
   __host__ __device__ constexpr long gv() const { return Bc() + (long)n * lda(); }
   __host__ __device__ constexpr long hb() const { return gv() + (long)SM_GV * n; }
   __host__ __device__ constexpr long end() const {
-    return flavour == SmallFlavour::Cv ? tv() + SM_CVW : flavour == SmallFlavour::LooGrad ? hb() : flavour == SmallFlavour::HindcastGrad ? hb() + (long)n * lead : Pw();
+    return flavour == SmallFlavour::Cv ? tv() + SM_CVW : flavour == SmallFlavour::LooGrad ? hb() : flavour == SmallFlavour::HindcastGrad || flavour == SmallFlavour::CvGrad ? hb() + (long)n * lead : Pw();
   }
   __host__ __device__ constexpr long bytes() const { return end() * (long)sizeof(double); }
 };
 
 // The feature chunk of a launch whose largest fit has nmax rows and mmax test points: the largest of start, start / 2, ... down to 8
-// whose image fits (sigp_small_upload: start = 32, the Plain image; the Cv, LooGrad and HindcastGrad launches: start = the upload's chunk); 0 if none does.
+// whose image fits (sigp_small_upload: start = 32, the Plain image; the Cv and score-gradient launches: start = the upload's chunk); 0 if none does.
 __host__ __device__ constexpr int small_pick_chunk(int nmax, int mmax, SmallFlavour f, int start, int lead = 0) {
   for (int ch = start; ch >= 8; ch /= 2)
     if (SmallLayout{nmax, mmax, ch, f, lead}.bytes() <= SM_LDS_MAX) return ch;

@@ -1407,7 +1407,7 @@ class GPR:
         workgroup per pair, on the data sets staged by ``upload_batch`` (``SmallBatch.run(loo= / hindcast=, score_grad=)``): theta [F, 2] =
         (log l, log sn~), pair i uses data set (first + i) % B or ``sets[i]``.  ``criterion`` 'loo_nlpd' | 'loo_sse' | 'hindcast_nlpd' |
         'hindcast_sse'; ``lead`` / ``min_train`` as ``SmallBatch.run(hindcast=)``; ``expm`` as ``nlml_batch``.  Returns (score [F], grad [F, 2]),
-        +inf where K~ is not SPD or exp(theta) overflows."""
+        +inf where K~ is not SPD or exp(theta) overflows.  The leave-block-out scores: ``small_cv_score_batch``."""
         if self.kernel != "netdiffusion":
             raise ValueError("small_score_batch runs the reference kernel (RBF / Matern: loo_ard_batch, hindcast_ard_batch)")
         if criterion not in L.LOO_CRITERION_IDS and criterion not in L.HINDCAST_CRITERION_IDS:
@@ -1420,6 +1420,24 @@ class GPR:
         kind, key = criterion.split("_")
         run = dict(loo=sigma_f) if kind == "loo" else dict(hindcast=dict(lead=lead, min_train=min_train, sigma_f=sigma_f))
         val, g = self._small_run(sb, theta, first, sets, expm, criterion, kind + "_grad", score_grad=key, **run)
+        g[~np.isfinite(val)] = np.inf
+        return val, g
+
+    def small_cv_score_batch(self, theta, block, gap=0, criterion="cv_nlpd", sigma_f="refit", first=0, expm="eigh", sets=None):
+        """``small_score_batch`` for the leave-block-out scores of the reference kernel (``SmallBatch.run(cv_grad=)``): folds of ``block``
+        consecutive rows with ``gap`` rows removed on each side, block + 2 gap <= 32, as ``SmallBatch.run(cv=)``; ``criterion`` 'cv_nlpd' |
+        'cv_sse'.  Returns (score [F], grad [F, 2]) for theta [F, 2] = (log l, log sn~) in ONE launch, +inf where K~ or a fold's block of K~^-1
+        is not SPD or exp(theta) overflows."""
+        if self.kernel != "netdiffusion":
+            raise ValueError("small_cv_score_batch runs the reference kernel (RBF / Matern: cv_ard_batch)")
+        if criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse' (the leave-one-out and hindcast scores: small_score_batch)")
+        block, gap = self._cv_args(block, gap, sigma_f, max_window=L.CV_SMALL_MAX_WINDOW)
+        sb = self._small_staged("small_cv_score_batch")
+        theta = L.f64(np.atleast_2d(theta), 2)
+        if theta.shape[1] != 2:
+            raise ValueError("theta must be [F, 2]")
+        val, g = self._small_run(sb, theta, first, sets, expm, criterion, "cv_grad", cv_grad=dict(block=block, gap=gap, sigma_f=sigma_f, score=criterion.split("_")[1]))
         g[~np.isfinite(val)] = np.inf
         return val, g
 
@@ -1457,7 +1475,8 @@ class GPR:
         """``optimize_batch`` for the reference kernel by a leave-one-out or hindcast score instead of nlML (``optimize_batch`` keeps refusing
         those criteria for this kernel): X / y (/ M) are sequences of ragged data sets (n <= 128 rows each), theta0 [B, 2] or [2] ->
         dict(x [B, 2], fun [B], jac [B, 2], nit [B], converged [B], nfev = launches).  Lockstep BFGS (``optim.bfgs_lockstep``) over
-        ``small_score_batch``: each round is ONE launch, one workgroup per data set, score and exact gradient formed in LDS."""
+        ``small_score_batch``: each round is ONE launch, one workgroup per data set, score and exact gradient formed in LDS.  The leave-block-out
+        scores: ``optimize_small_cv_batch``."""
         from .optim import bfgs_lockstep
         if self.kernel != "netdiffusion":
             raise ValueError("optimize_small_batch runs the reference kernel (RBF / Matern: optimize_batch, optimize_ard_batch, optimize_hindcast_batch)")
@@ -1467,6 +1486,23 @@ class GPR:
         th0 = np.broadcast_to(np.asarray(theta0, dtype=np.float64), (len(self._small_ids), 2))
         return bfgs_lockstep(lambda t: self.small_score_batch(t, criterion=criterion, lead=lead, min_train=min_train, sigma_f=sigma_f, expm=expm), th0,
                              maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
+
+    def optimize_small_cv_batch(self, X, y, theta0, block, gap=0, criterion="cv_nlpd", sigma_f="refit", M=None, expm="eigh", maxiter=50, gtol=1e-5,
+                                ftol=1e-10, max_step=2.0):
+        """``optimize_small_batch`` by a leave-block-out score of the reference kernel ('cv_nlpd' | 'cv_sse'; folds as ``small_cv_score_batch``,
+        ``block`` has no default, as in ``optimize_cv_batch``): lockstep BFGS (``optim.bfgs_lockstep``) over ``small_cv_score_batch``, each round
+        ONE launch, one workgroup per data set, the score and its exact gradient formed in LDS.  Returns dict(x [B, 2], fun [B], jac [B, 2],
+        nit [B], converged [B], nfev = launches)."""
+        from .optim import bfgs_lockstep
+        if self.kernel != "netdiffusion":
+            raise ValueError("optimize_small_cv_batch runs the reference kernel (RBF / Matern: optimize_cv_batch)")
+        if criterion not in L.CV_CRITERION_IDS:
+            raise ValueError("criterion must be 'cv_nlpd' or 'cv_sse' (the leave-one-out and hindcast scores: optimize_small_batch)")
+        block, gap = self._cv_args(block, gap, sigma_f, max_window=L.CV_SMALL_MAX_WINDOW)
+        self.upload_batch(X, y, None, M=M)
+        th0 = np.broadcast_to(np.asarray(theta0, dtype=np.float64), (len(self._small_ids), 2))
+        return bfgs_lockstep(lambda t: self.small_cv_score_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, expm=expm), th0, maxiter=maxiter,
+                             gtol=gtol, ftol=ftol, max_step=max_step)
 
     def nlml_grid(self, X, y, ells, sns, concurrency=2, group=8, M=None):
         """nlML on the (l, sn~) grid for one data set -- the offline 20x20 search implied by

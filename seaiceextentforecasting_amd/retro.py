@@ -144,7 +144,7 @@ def retro_grid_search(script, SIC, SIEs_dt, fmin, fmax, SST=None, ells=LGRID, sn
             gp.close()
 
 
-def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, gp=None, theta0=None, expm="eigh", criterion="nlml", lead=1, min_train=2, **kw):
+def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, gp=None, theta0=None, expm="eigh", criterion="nlml", lead=1, min_train=2, block=5, gap=0, **kw):
     """The optimiser call the reference left commented out (north/June1st.py:259-262, `minimize(MLII, x0, method='CG', jac=True)`
     with x0 = log of the script's table entries), re-enabled for EVERY (region, year) of the retro loop
     (September1st_retro.py:176-180) at once: each optimiser round is one device launch, one workgroup per (region, year), with
@@ -157,10 +157,12 @@ def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, 
     ``criterion`` = "loo_nlpd", "loo_sse", "hindcast_nlpd" or "hindcast_sse" minimises that score instead of nlML (``GPR.optimize_small_batch``:
     lockstep BFGS, each round still one launch with the score and its exact gradient formed in LDS; ``lead`` / ``min_train`` as
     ``retro_grid_search``, sigma_f re-profiled; ``sigma_f="fixed"`` and the optimiser's tolerances go through ``**kw``); each region's dict then
-    also carries ``jac``, the gradient at ``x``.  What is held fixed is what ``retro_grid_search`` holds fixed.  The leave-block-out scores
-    have no gradient in this kernel."""
-    if criterion != "nlml" and criterion not in ("loo_nlpd", "loo_sse", "hindcast_nlpd", "hindcast_sse"):
-        raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'hindcast_nlpd' or 'hindcast_sse' (block-CV gradients are not built for the reference kernel)")
+    also carries ``jac``, the gradient at ``x``.  What is held fixed is what ``retro_grid_search`` holds fixed.
+
+    ``criterion`` = "cv_nlpd" or "cv_sse" minimises the leave-block-out score with folds of ``block`` consecutive years and ``gap`` years removed on
+    each side (defaults as ``retro_grid_search``; ``GPR.optimize_small_cv_batch``: the same lockstep BFGS, one launch per round), ``jac`` as above."""
+    if criterion != "nlml" and criterion not in ("loo_nlpd", "loo_sse", "hindcast_nlpd", "hindcast_sse", "cv_nlpd", "cv_sse"):
+        raise ValueError("criterion must be 'nlml', 'loo_nlpd', 'loo_sse', 'hindcast_nlpd', 'hindcast_sse', 'cv_nlpd' or 'cv_sse'")
     tab = SCRIPT_TABLE[script]
     own = gp is None
     gp = gp or GPR(kernel="netdiffusion")
@@ -176,6 +178,8 @@ def retro_optimise(script, SIC, SIEs_dt, fmin, fmax, SST=None, SIEs_trend=None, 
         x0 = np.asarray(x0) if theta0 is None else np.broadcast_to(np.asarray(theta0, dtype=np.float64), (len(Xl), 2))
         if criterion == "nlml":
             res = gp.optimize_batch(Xl, yl, x0, M=Ml, expm=expm, **kw)
+        elif criterion.startswith("cv_"):
+            res = gp.optimize_small_cv_batch(Xl, yl, x0, block, gap=gap, criterion=criterion, M=Ml, expm=expm, **kw)
         else:
             res = gp.optimize_small_batch(Xl, yl, x0, criterion=criterion, lead=lead, min_train=min_train, M=Ml, expm=expm, **kw)
         out = {"nfev": res["nfev"]}

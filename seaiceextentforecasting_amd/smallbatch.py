@@ -125,7 +125,7 @@ class SmallBatch:
         self._fits = []
         self._packed = None
 
-    def run(self, grad=False, loo=None, cv=None, hindcast=None, score_grad=None):
+    def run(self, grad=False, loo=None, cv=None, hindcast=None, score_grad=None, cv_grad=None):
         """All queued fits in one launch -> dict(sigma_f, nlml, info, sigma_n, mean [F, mmax], var [F, mmax]); with ``grad=True``
         also grad_ref [F, 2] (the reference's MLII formulae, north/June1st.py:248-252) and grad_exact [F, 2] (the derivative of the
         profiled nlML w.r.t. (log l, log sn~)); +inf where K~ is not positive definite (:254-256).
@@ -160,7 +160,25 @@ class SmallBatch:
         at lead = 1 n <= 128 up to m = 5 and n <= 127 above, and at n = 128, m = 0 lead <= 6; what does not fit raises ValueError (the
         library's SIGP_BAD_ARG, whose message names the bytes needed and the limit) and the batch still runs every other launch.  From order 97
         on the launch may build K~ from shorter feature chunks than the score launch does: sets with more features than the chunk then agree
-        with it to rounding, not byte for byte.  Leave-block-out gradients are not built: ``cv=`` with ``score_grad`` raises."""
+        with it to rounding, not byte for byte.  ``cv=`` with ``score_grad`` raises: the leave-block-out gradients come through ``cv_grad=``.
+
+        ``cv_grad=dict(block=, gap=0, sigma_f="refit", score="nlpd" | "sse")``: what ``cv=dict(block=, gap=, sigma_f=)`` returns -- the same bytes,
+        where no data set has more features than the launch's feature chunk -- and cv_grad [F, 2], the derivatives of that leave-block-out score
+        with respect to (log l, log sn~), in the same single launch (``sigp_small_run_cv_grad``; the adjoint of ``GPR.cv_ard``, its banded B kept
+        in LDS).  A flavour of its own: mutually exclusive with ``grad``, ``loo``, ``cv``, ``hindcast`` and ``score_grad``.  +inf in the scores and
+        the gradient where K~ or a fold's block of K~^-1 is not positive definite; "pade" fits as above.  Every batch whose largest order is
+        <= 96 runs (any m <= 8, any window block + 2 gap <= 32); beyond that the largest order is 123 / 121 / 119 / 116 / 109 at m = 0 and
+        119 / 117 / 115 / 113 / 106 at m = 8 for windows 1 / 5 / 8 / 16 / 32; what does not fit raises ValueError (the library's message names
+        n, m, the window, the bytes needed and the limit) and the batch still runs every other launch."""
+        if cv_grad is not None:
+            if grad or loo is not None or cv is not None or hindcast is not None or score_grad is not None:
+                raise ValueError("one launch forms the gradients, the leave-one-out, the leave-block-out or the hindcast predictions: run them separately "
+                                 "(cv_grad is a flavour of its own: the leave-block-out predictions and the gradient of one of their scores)")
+            if not isinstance(cv_grad, dict) or "block" not in cv_grad or set(cv_grad) - {"block", "gap", "sigma_f", "score"}:
+                raise ValueError("cv_grad must be dict(block=, gap=0, sigma_f='refit', score='nlpd' | 'sse')")
+            if cv_grad.get("score", "nlpd") not in self._SCORE_IDS:
+                raise ValueError("cv_grad: score must be 'nlpd' or 'sse'")
+            cv = {k: v for k, v in cv_grad.items() if k != "score"}
         if score_grad is not None:
             if cv is not None:
                 raise ValueError("score_grad: block-CV gradients are not built in the one-workgroup kernel (loo= and hindcast= have them)")
@@ -205,6 +223,8 @@ class SmallBatch:
                 flavour, extra = "hindcast_grad", extra + (self._SCORE_IDS[score_grad],)
         elif cv is not None:
             flavour, extra = "cv", (cv_block, cv_gap, L.LOO_MODES[cv_mode])
+            if cv_grad is not None:
+                flavour, extra = "cv_grad", extra + (self._SCORE_IDS[cv_grad.get("score", "nlpd")],)
         elif loo is not None:
             flavour, extra = "loo", (L.LOO_MODES[loo],)
             if score_grad is not None:
@@ -228,7 +248,7 @@ class SmallBatch:
             res.update({prefix + "_mean": rmean, prefix + "_var": rvar, prefix + "_nlpd": out[:, 4].copy(), prefix + "_sse": out[:, 5].copy()})
         if grad:
             res["grad_ref"], res["grad_exact"] = out[:, 4:6].copy(), out[:, 6:8].copy()
-        if score_grad is not None:
+        if score_grad is not None or cv_grad is not None:
             res[prefix + "_grad"] = out[:, 6:8].copy()
         return res
 
@@ -242,4 +262,5 @@ class SmallBatch:
                  "cv": ("cv", "sigp_small_run_cv", "small_run_cv", 6),
                  "hindcast": ("hindcast", "sigp_small_run_hindcast", "small_run_hindcast", 6),
                  "loo_grad": ("loo", "sigp_small_run_loo_grad", "small_run_loo_grad", 8),
-                 "hindcast_grad": ("hindcast", "sigp_small_run_hindcast_grad", "small_run_hindcast_grad", 8)}
+                 "hindcast_grad": ("hindcast", "sigp_small_run_hindcast_grad", "small_run_hindcast_grad", 8),
+                 "cv_grad": ("cv", "sigp_small_run_cv_grad", "small_run_cv_grad", 8)}
