@@ -582,6 +582,44 @@ int sigp_small_run_hindcast_grad(sigp_handle* h, int64_t nprob, const int64_t* s
 int sigp_small_run_cv_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, const double* ell, const double* sn_tilde, int64_t block,
                            int64_t gap, int sigma_mode, int criterion, double* out8, double* mean, double* var, int64_t mstride, double* cv_mean,
                            double* cv_var, int64_t nstride);
+/* The one-workgroup kernel with an RBF / Matern-5/2 covariance, one length scale per fit or one per feature (ARD): sigp_small_run with
+ * K~ = k(X, X) + sn~ I in place of X Sigma~ X^T, one workgroup per fit, one launch for the list, n <= 128.  The data sets come from
+ * sigp_small_upload as before with A = [X ; Xs], the RAW rows, lam_mode 0 and any lam (it is not read).  kernel_id: SIGP_KERNEL_RBF or
+ * SIGP_KERNEL_MATERN52, one per call.  ell [nprob][ldell]: ard = 0, fit p has the scale ell[p ldell] for every feature; ard = 1, fit p has
+ * ell[p ldell + k] for feature k < N of its set (ldell >= the largest N named).  The workgroup stages u = x / l_k (the IEEE division, as
+ * sigp_set_length_scales does), sums the squared distances by direct differences in ascending k (exact zeros on the diagonal and for duplicate
+ * rows; the same bits whatever the feature chunk) and maps them through the library's covariance functions at unit length scale; k** = 1.
+ * out4, mean, var and mstride as sigp_small_run; a non-SPD K~ as there (+inf, info = the pivot, NaN predictions).
+ * SIGP_BAD_ARG, the message naming the offender: a kernel id other than the two, ard not 0 / 1, a scale that is not finite and > 0 or whose
+ * reciprocal is not finite, ldell too small, and everything sigp_small_run refuses. */
+int sigp_small_run_k(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard,
+                     const double* sn_tilde, double* out4, double* mean, double* var, int64_t mstride);
+/* sigp_small_run_k, then value + EXACT gradient of the profiled nlML in every length scale and sn~ in the same single launch; out4, mean and
+ * var carry the bytes sigp_small_run_k returns.  grad [nprob][ldg]: ard = 0 (d/d log l, d/d log sn~), ldg >= 2; ard = 1
+ * d/d log l_0 .. d/d log l_{N-1}, d/d log sn~, ldg >= N + 1 of every set named, NaN behind a fit's N + 1 entries.  With W = K~^-1 - a~ a~^T /
+ * sigma_f and h as in sigp_nlml_grad_ard:  d/d log l_k = sum_{i>j} W_ij h_ij (u_ik - u_jk)^2,  d/d log sn~ = sn~ (tr K~^-1 - a~.a~ / sigma_f) / 2;
+ * one common scale: the sum over k in ascending k.  In LDS: X = L~^-1 over L~, the squared distances again into the strict upper triangle of the
+ * bordered matrix, each replaced by W_ij h_ij (n^3/3 multiply-adds, no second n x n buffer), then one pass per feature over the pairs; fixed
+ * summation order, no atomics: the same bits on every run.  A non-SPD K~: +inf in every gradient entry of the fit.  LDS: the image of
+ * sigp_small_run_grad.  SIGP_BAD_ARG: as sigp_small_run_k, grad = NULL and ldg too small. */
+int sigp_small_run_k_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard,
+                          const double* sn_tilde, double* out4, double* mean, double* var, int64_t mstride, double* grad, int64_t ldg);
+/* sigp_small_run_loo with that covariance: the leave-one-out tail reads K~, L~^-1, z and y alone and runs its own statements.  Arguments behind
+ * sn_tilde, outputs, limits and refusals as sigp_small_run_loo; out6[0..3], mean and var carry sigp_small_run_k's bytes. */
+int sigp_small_run_k_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard,
+                         const double* sn_tilde, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* loo_mean,
+                         double* loo_var, int64_t nstride);
+/* sigp_small_run_cv with that covariance: folds, windows, LDS limits and refusals as there (the layouts are the same).  The launch may pick a
+ * shorter feature chunk than sigp_small_run_k; the squared distances are one running sum in ascending k per entry, so out6[0..3], mean and var
+ * still carry sigp_small_run_k's bytes. */
+int sigp_small_run_k_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard,
+                        const double* sn_tilde, int64_t block, int64_t gap, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride,
+                        double* cv_mean, double* cv_var, int64_t nstride);
+/* sigp_small_run_hindcast with that covariance: rows, lead, min_train, limits and refusals as there; L~ and z are read where the factorisation
+ * left them.  The score gradients (sigp_small_run_*_grad) are not built for the stationary covariances. */
+int sigp_small_run_k_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard,
+                              const double* sn_tilde, int64_t lead, int64_t min_train, int sigma_mode, double* out6, double* mean, double* var,
+                              int64_t mstride, double* hc_mean, double* hc_var, int64_t nstride);
 /* The hindcast scores AND the exact derivatives of one of them with respect to theta = (log l_1 .. log l_d, log sn~) (RBF / Matern-5/2,
  * fp64), so that the length scales can be chosen by the score the retro loop reports (September1st_retro.py:176-248) instead of a grid.
  * theta, ntheta = d + 1, criterion (SIGP_LOO_NLPD / SIGP_LOO_SSE) and mean / var [n] (both or neither) as sigp_loo_grad_ard.  Sets the

@@ -86,6 +86,11 @@ SIGNATURES = {
     "sigp_small_run_loo_grad": (C.c_int, [_h, _i64, _ip64, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_small_run_cv_grad": (C.c_int, [_h, _i64, _ip64, _dp, _dp, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_small_run_hindcast_grad": (C.c_int, [_h, _i64, _ip64, _dp, _dp, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
+    "sigp_small_run_k": (C.c_int, [_h, _i64, _ip64, C.c_int, _dp, _i64, C.c_int, _dp, _dp, _dp, _dp, _i64]),
+    "sigp_small_run_k_grad": (C.c_int, [_h, _i64, _ip64, C.c_int, _dp, _i64, C.c_int, _dp, _dp, _dp, _dp, _i64, _dp, _i64]),
+    "sigp_small_run_k_loo": (C.c_int, [_h, _i64, _ip64, C.c_int, _dp, _i64, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
+    "sigp_small_run_k_cv": (C.c_int, [_h, _i64, _ip64, C.c_int, _dp, _i64, C.c_int, _dp, _i64, _i64, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
+    "sigp_small_run_k_hindcast": (C.c_int, [_h, _i64, _ip64, C.c_int, _dp, _i64, C.c_int, _dp, _i64, _i64, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_hindcast_grad_ard": (C.c_int, [_h, C.c_int, _dp, _i64, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "sigp_hindcast_grad_ard_batch": (C.c_int, [_h, _i64, _i64, C.c_int, _dp, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _dp, _dp, _i64, _dp, _dp, _i64]),
     "sigp_dist_unique_id": (C.c_int, [C.c_void_p]),

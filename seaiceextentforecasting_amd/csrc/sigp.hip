@@ -157,6 +157,7 @@ struct sigp_handle {
   double* sm_dlam = nullptr; long cap_sm_dlam = 0; long sm_lam_len = 0; bool sm_has_dlam = false;   // lam_mode 1: derivative weights
   SmallProb* sm_probs = nullptr; long cap_sm_probs = 0;
   double* sm_out = nullptr; long cap_sm_out = 0;   // [nprob][4 + 2*mstride]
+  double* sm_ell = nullptr; long cap_sm_ell = 0;   // sigp_small_run_k*: the fits' per-feature length scales [nprob][ldell]
   double* sm_loo_host = nullptr; long cap_sm_loo_host = 0;   // pinned [2][nprob][nstride]: the leave-one-out rows on their way to the caller
   int sm_ch = 32, sm_mmax = 0, sm_nmax = 0; long sm_lds = 0;
   int opt_small_nt64 = 0;                     // measurement switch: one wavefront per fit at orders <= 64
@@ -823,7 +824,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 620; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard; 6.2: sigp_hindcast_grad_ard_batch
+int sigp_version(void) { return 630; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard; 6.2: sigp_hindcast_grad_ard_batch; 6.3: sigp_small_run_k, _k_grad, _k_loo, _k_cv, _k_hindcast
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -860,7 +861,7 @@ int sigp_destroy(sigp_handle* h) {
   (void)hipDeviceSynchronize();
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
-  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out,
+  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out, h->sm_ell,
                     h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->cvAdj, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc, h->bStage};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);

@@ -64,16 +64,24 @@ struct SmallRequest {
   int criterion = 0;                                   // LooGrad, HindcastGrad, CvGrad: SIGP_LOO_NLPD / SIGP_LOO_SSE
   double *row_mean = nullptr, *row_var = nullptr;      // Loo, Cv, Hindcast: the caller's [nprob][pitch]
   int64_t pitch = 0;
+  // sigp_small_run_k*: a stationary covariance (SmallCov::Stationary) of the sets' raw rows; `ell` is then [nprob][ldell]
+  SmallCov cov = SmallCov::Factored;
+  int kernel_id = 0;                                   // SIGP_KERNEL_RBF / SIGP_KERNEL_MATERN52
+  int ard = 0;                                         // 1: fit p has the scales ell[p ldell + k], k < N of its set; 0: ell[p ldell] for every feature
+  int64_t ldell = 1;
+  double* grad = nullptr;                              // Grad: the caller's [nprob][ldg]
+  int64_t ldg = 0;
+  const char* name = "small_run";                      // the entry's name in the messages of the stationary checks
 };
 
 extern "C++" {
-// one launch of smallgp_kernel<NT, F> over nprob fits; the kernel's dynamic-LDS limit is lifted once per device
-template <int NT, SmallFlavour F>
+// one launch of smallgp_kernel<NT, F, C> over nprob fits; the kernel's dynamic-LDS limit is lifted once per device
+template <int NT, SmallFlavour F, SmallCov C = SmallCov::Factored>
 static hipError_t small_launch(sigp_handle* h, hipStream_t st, int64_t nprob, long lds, int ch, double* d_out, double* d_mean, double* d_var, int ms, const SmallExtras& x) {
   static AttrOnce attr;
-  const hipError_t e = attr.set(h->device, (const void*)smallgp_kernel<NT, F>, (int)SM_LDS_MAX);
+  const hipError_t e = attr.set(h->device, (const void*)smallgp_kernel<NT, F, C>, (int)SM_LDS_MAX);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((smallgp_kernel<NT, F>), dim3((unsigned)nprob), dim3(NT), (size_t)lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y, h->sm_lam, ch, d_out, d_mean, d_var, ms,
+  hipLaunchKernelGGL((smallgp_kernel<NT, F, C>), dim3((unsigned)nprob), dim3(NT), (size_t)lds, st, h->sm_sets_dev, h->sm_probs, h->sm_A, h->sm_y, h->sm_lam, ch, d_out, d_mean, d_var, ms,
                      h->sm_has_dlam ? h->sm_dlam : nullptr, x);
   return hipGetLastError();
 }
@@ -82,10 +90,15 @@ static hipError_t small_launch(sigp_handle* h, hipStream_t st, int64_t nprob, lo
 // adds the flops of one fit of the set s in the flavour of rq
 static void small_count_flops(double& fl, const SmallSet& s, const SmallRequest& rq) {
   const double n = s.n, inverse = n * n * n / 3;      // X = L~^-1
-  fl += n * n * s.N + n * n * n / 3 + 2.0 * n * n * (1 + s.m);
+  const bool stationary = rq.cov == SmallCov::Stationary;
+  // the build: a multiply-add per (pair, feature), or a difference and a multiply-add and the covariance function (~40 flops) per pair
+  fl += (stationary ? 1.5 * n * (n + 2.0 * s.m) * s.N + 20.0 * n * (n + 2.0 * s.m) : n * n * s.N) + n * n * n / 3 + 2.0 * n * n * (1 + s.m);
   switch (rq.flavour) {
     case SmallFlavour::Plain: break;
-    case SmallFlavour::Grad: fl += n * n * s.N + inverse + 2.0 * n * s.N; break;      // X A, A^T a~
+    case SmallFlavour::Grad:
+      if (stationary) fl += inverse + 1.5 * n * n * s.N + inverse + 20.0 * n * n + 2.0 * n * n * s.N;     // X, sq again, E = W o h, E against every feature's differences
+      else fl += n * n * s.N + inverse + 2.0 * n * s.N;                                // X A, A^T a~
+      break;
     case SmallFlavour::Loo: fl += inverse + 2.0 * n * n; break;                       // X's column norms and X^T z
     case SmallFlavour::Cv: fl += inverse + 2.0 * n * n; fl += n * n * (rq.block + 2.0 * rq.gap); break;   // ... and the folds' P_SS from X's columns
     case SmallFlavour::Hindcast: fl += 4.0 * n * rq.lead + 2.0 * n * n; break;        // the row segments and the prefix sums of z^2
@@ -108,6 +121,15 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   const bool cv = F == SmallFlavour::Cv || F == SmallFlavour::CvGrad, hc = F == SmallFlavour::Hindcast || F == SmallFlavour::HindcastGrad, rows = small_has_rows(F);
   const char* cvloo = cv ? "cv" : "loo";
   if (nprob < 1 || !set_index || !ell || !sn_tilde || !out) return fail(h, SIGP_BAD_ARG, "small_run: bad argument");
+  const bool stationary = rq.cov == SmallCov::Stationary, sgrad = stationary && F == SmallFlavour::Grad;
+  if (stationary) {
+    if (rq.kernel_id != SIGP_KERNEL_RBF && rq.kernel_id != SIGP_KERNEL_MATERN52)
+      return fail(h, SIGP_BAD_ARG, "%s: kernel_id = %d; the stationary covariances are SIGP_KERNEL_RBF and SIGP_KERNEL_MATERN52", rq.name, rq.kernel_id);
+    if (rq.ard != 0 && rq.ard != 1) return fail(h, SIGP_BAD_ARG, "%s: ard must be 0 (one length scale per fit) or 1 (one per feature), got %d", rq.name, rq.ard);
+    if (rq.ldell < 1) return fail(h, SIGP_BAD_ARG, "%s: ldell = %lld; ell is [nprob][ldell >= 1]", rq.name, (long long)rq.ldell);
+    if (sgrad && !rq.grad) return fail(h, SIGP_BAD_ARG, "%s: grad [nprob][ldg] required", rq.name);
+    if (sgrad && rq.ldg < 2) return fail(h, SIGP_BAD_ARG, "%s: ldg = %lld; grad holds (d/d log l, d/d log sn~) per fit: ldg >= 2", rq.name, (long long)rq.ldg);
+  }
   if (rows && (!rq.row_mean || !rq.row_var || rq.pitch < h->sm_nmax)) {
     if (hc) return fail(h, SIGP_BAD_ARG, "small_run_hindcast: hc_mean / hc_var [nprob][nstride >= %d] required", h->sm_nmax);
     return fail(h, SIGP_BAD_ARG, "small_run_%s: %s_mean / %s_var [nprob][nstride >= %d] required", cvloo, cvloo, cvloo, h->sm_nmax);
@@ -147,8 +169,19 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   std::vector<SmallProb> probs((size_t)nprob);
   for (int64_t i = 0; i < nprob; ++i) {
     if (set_index[i] < 0 || set_index[i] >= (int64_t)h->sm_sets.size()) return fail(h, SIGP_BAD_ARG, "small_run: fit %ld names data set %ld of %zu", (long)i, (long)set_index[i], h->sm_sets.size());
-    if (!(sn_tilde[i] >= 0) || !std::isfinite(ell[i])) return fail(h, SIGP_BAD_ARG, "small_run: finite ell and sn_tilde >= 0 required");
+    if (!(sn_tilde[i] >= 0) || (!stationary && !std::isfinite(ell[i]))) return fail(h, SIGP_BAD_ARG, "small_run: finite ell and sn_tilde >= 0 required");
     const int n = h->sm_sets[(size_t)set_index[i]].n;
+    if (stationary) {
+      const int N = h->sm_sets[(size_t)set_index[i]].N, nl = rq.ard ? N : 1;
+      if (nl > rq.ldell) return fail(h, SIGP_BAD_ARG, "%s: fit %ld names a data set of N = %d features; ldell = %lld holds fewer scales", rq.name, (long)i, N, (long long)rq.ldell);
+      if (sgrad && nl + 1 > rq.ldg)
+        return fail(h, SIGP_BAD_ARG, "%s: fit %ld has %d derivatives (%d length scale%s and sn~); ldg = %lld holds fewer", rq.name, (long)i, nl + 1, nl, nl > 1 ? "s" : "", (long long)rq.ldg);
+      for (int k = 0; k < nl; ++k) {
+        const double l = ell[i * rq.ldell + k];
+        if (!(l > 0) || !std::isfinite(l) || !std::isfinite(1.0 / l))
+          return fail(h, SIGP_BAD_ARG, "%s: fit %ld: length scale %d is %g; every scale must be finite and > 0 with a finite reciprocal", rq.name, (long)i, k, l);
+      }
+    }
     if (hc && rq.min_train + rq.lead - 1 > n - 1)
       return fail(h, SIGP_BAD_ARG, "small_run_hindcast: fit %ld names a data set without a scored row (min_train + lead - 1 = %lld > n - 1 = %d)", (long)i,
                   (long long)(rq.min_train + rq.lead - 1), n - 1);
@@ -159,12 +192,13 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
                     n, SIGP_CV_SMALL_MAX_WINDOW);
       cv_checked[(size_t)set_index[i]] = 1;
     }
-    probs[(size_t)i] = SmallProb{(int)set_index[i], 0, ell[i], sn_tilde[i]};
+    probs[(size_t)i] = SmallProb{(int)set_index[i], 0, ell[i * rq.ldell], sn_tilde[i]};
   }
   const long ms = std::max<int64_t>(mstride, 1);
   const long ns = rows ? (long)rq.pitch : 0;
-  const long ow = small_out_width(F);
-  const long per = ow + 2 * ms + 2 * ns;
+  const long ow = small_out_width(F, rq.cov);
+  const long ng = sgrad ? (long)rq.ldg : 0;
+  const long per = ow + 2 * ms + 2 * ns + ng;
   if (h->cap_sm_probs < nprob) {
     if (h->sm_probs) HIPCHK(h, hipFree(h->sm_probs));
     h->sm_probs = nullptr; h->cap_sm_probs = 0;
@@ -176,18 +210,32 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
   hipStream_t st = h->slots[0].s_upd;
   HIPCHK(h, hipMemcpyAsync(h->sm_probs, probs.data(), probs.size() * sizeof(SmallProb), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemsetAsync(h->sm_out, 0xff, (size_t)(nprob * per) * sizeof(double), st));   // NaN wherever a set has fewer test points than mstride
+  if (stationary && rq.ard) {
+    if ((rc = ensure(h, &h->sm_ell, &h->cap_sm_ell, nprob * rq.ldell))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->sm_ell, ell, (size_t)(nprob * rq.ldell) * sizeof(double), hipMemcpyHostToDevice, st));
+  }
   double* d_out = h->sm_out;
   double* d_mean = h->sm_out + nprob * ow;
   double* d_var = d_mean + nprob * ms;
   double* d_lmean = d_var + nprob * ms;        // [nprob][ns] each; NaN beyond a set's n (the memset above)
   double* d_lvar = d_lmean + nprob * ns;
+  double* d_grad = d_lvar + nprob * ns;        // [nprob][ng]; NaN behind a fit's derivatives
   {
     double fl = 0;
     for (const auto& pb : probs) small_count_flops(fl, h->sm_sets[(size_t)pb.set], rq);
     ProfScope ps(h, st, SIGP_KC_SMALL, fl, 0.0);
-    const SmallExtras x{d_lmean, d_lvar, (int)ns, rq.sigma_mode, (int)rq.block, (int)rq.gap, (int)rq.lead, (int)rq.min_train, rq.criterion};
+    const SmallExtras x{d_lmean, d_lvar, (int)ns, rq.sigma_mode, (int)rq.block, (int)rq.gap, (int)rq.lead, (int)rq.min_train, rq.criterion,
+                        make_kparams(stationary ? rq.kernel_id : 0, 1.0, 0.0, 0), stationary && rq.ard ? h->sm_ell : nullptr, (int)rq.ldell, (int)ng, d_grad};
     decltype(&small_launch<256, SmallFlavour::Plain>) launch = nullptr;
-    switch (F) {
+    if (stationary) switch (F) {
+      case SmallFlavour::Plain: launch = small_launch<256, SmallFlavour::Plain, SmallCov::Stationary>; break;
+      case SmallFlavour::Grad: launch = small_launch<256, SmallFlavour::Grad, SmallCov::Stationary>; break;
+      case SmallFlavour::Loo: launch = small_launch<256, SmallFlavour::Loo, SmallCov::Stationary>; break;
+      case SmallFlavour::Cv: launch = small_launch<256, SmallFlavour::Cv, SmallCov::Stationary>; break;
+      case SmallFlavour::Hindcast: launch = small_launch<256, SmallFlavour::Hindcast, SmallCov::Stationary>; break;
+      default: return fail(h, SIGP_BAD_ARG, "%s: the score gradients are not built for the stationary covariances", rq.name);
+    }
+    else switch (F) {
       // four wavefronts per fit at every order; one per fit (orders up to 64) is a measurement switch: on the reference-size grid
       // (48 000 fits, n = 6 .. 45) four wavefronts per fit take 1.02 ms, one wavefront per fit 1.71 ms
       case SmallFlavour::Plain: launch = h->sm_nmax <= 64 && h->opt_small_nt64 ? small_launch<64, SmallFlavour::Plain> : small_launch<256, SmallFlavour::Plain>; break;
@@ -219,6 +267,7 @@ static int small_run_impl(sigp_handle* h, int64_t nprob, const int64_t* set_inde
     }
     HIPCHK(h, hipMemcpyAsync(h->sm_loo_host, d_lmean, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, st));
   }
+  if (sgrad) HIPCHK(h, hipMemcpyAsync(rq.grad, d_grad, (size_t)nprob * ng * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   if (rows) {
     memcpy(rq.row_mean, h->sm_loo_host, (size_t)nprob * ns * sizeof(double));
@@ -309,6 +358,58 @@ int sigp_small_run_cv_grad(sigp_handle* h, int64_t nprob, const int64_t* set_ind
   rq.flavour = SmallFlavour::CvGrad; rq.sigma_mode = sigma_mode; rq.criterion = criterion; rq.block = block; rq.gap = gap;
   rq.row_mean = cv_mean; rq.row_var = cv_var; rq.pitch = nstride;
   return small_run_impl(h, nprob, set_index, ell, sn_tilde, out8, mean, var, mstride, rq);
+}
+
+// ---- the same kernel with an RBF / Matern-5/2 covariance of the sets' raw rows, one length scale per fit or one per feature (SmallCov::Stationary) --------
+static SmallRequest small_k_request(const char* name, SmallFlavour f, int kernel_id, int64_t ldell, int ard) {
+  SmallRequest rq;
+  rq.name = name; rq.flavour = f; rq.cov = SmallCov::Stationary; rq.kernel_id = kernel_id; rq.ldell = ldell; rq.ard = ard;
+  return rq;
+}
+
+int sigp_small_run_k(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard, const double* sn_tilde,
+                     double* out4, double* mean, double* var, int64_t mstride) {
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out4, mean, var, mstride, small_k_request("small_run_k", SmallFlavour::Plain, kernel_id, ldell, ard));
+}
+
+// sigp_small_run_k, then the exact gradient of the profiled nlML in every length scale and sn~ in the same single launch
+int sigp_small_run_k_grad(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard, const double* sn_tilde,
+                          double* out4, double* mean, double* var, int64_t mstride, double* grad, int64_t ldg) {
+  SmallRequest rq = small_k_request("small_run_k_grad", SmallFlavour::Grad, kernel_id, ldell, ard);
+  rq.grad = grad; rq.ldg = ldg;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out4, mean, var, mstride, rq);
+}
+
+int sigp_small_run_k_loo(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard, const double* sn_tilde,
+                         int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* loo_mean, double* loo_var, int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_k_loo: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  SmallRequest rq = small_k_request("small_run_k_loo", SmallFlavour::Loo, kernel_id, ldell, ard);
+  rq.sigma_mode = sigma_mode;
+  rq.row_mean = loo_mean; rq.row_var = loo_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
+}
+
+int sigp_small_run_k_cv(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard, const double* sn_tilde,
+                        int64_t block, int64_t gap, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* cv_mean, double* cv_var,
+                        int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_k_cv: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (block < 1 || gap < 0) return fail(h, SIGP_BAD_ARG, "small_run_k_cv: block >= 1 and gap >= 0 required");
+  SmallRequest rq = small_k_request("small_run_k_cv", SmallFlavour::Cv, kernel_id, ldell, ard);
+  rq.sigma_mode = sigma_mode; rq.block = block; rq.gap = gap;
+  rq.row_mean = cv_mean; rq.row_var = cv_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
+}
+
+int sigp_small_run_k_hindcast(sigp_handle* h, int64_t nprob, const int64_t* set_index, int kernel_id, const double* ell, int64_t ldell, int ard, const double* sn_tilde,
+                              int64_t lead, int64_t min_train, int sigma_mode, double* out6, double* mean, double* var, int64_t mstride, double* hc_mean, double* hc_var,
+                              int64_t nstride) {
+  if (sigma_mode != SIGP_LOO_REFIT && sigma_mode != SIGP_LOO_FIXED) return fail(h, SIGP_BAD_ARG, "small_run_k_hindcast: sigma_mode must be SIGP_LOO_REFIT or SIGP_LOO_FIXED");
+  if (lead < 1 || lead > SIGP_HINDCAST_SMALL_MAX_LEAD) return fail(h, SIGP_BAD_ARG, "small_run_k_hindcast: 1 <= lead <= %d required (got %lld)", (int)SIGP_HINDCAST_SMALL_MAX_LEAD, (long long)lead);
+  if (min_train < 1) return fail(h, SIGP_BAD_ARG, "small_run_k_hindcast: min_train >= 1 required (got %lld)", (long long)min_train);
+  SmallRequest rq = small_k_request("small_run_k_hindcast", SmallFlavour::Hindcast, kernel_id, ldell, ard);
+  rq.sigma_mode = sigma_mode; rq.lead = lead; rq.min_train = min_train;
+  rq.row_mean = hc_mean; rq.row_var = hc_var; rq.pitch = nstride;
+  return small_run_impl(h, nprob, set_index, ell, sn_tilde, out6, mean, var, mstride, rq);
 }
 
 // ---- ComplexNetworks tau(): cell-to-cell correlation matrix + thresholded mean (ComplexNetworks.py:31-47) ------------

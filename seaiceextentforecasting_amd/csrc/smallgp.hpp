@@ -71,6 +71,18 @@
 //     b^T C b = (u.b)(z.b) + p^T B p + eps (z.b)^2,   p = X^T b  (a vector in Ac, free once Bc is staged, before the band is summed)
 // over b_c = X a_c and over the columns of X, ch at a time.  A failed pivot of a P_SS: +inf in out[4..7] and NaN rows.
 //
+// Stationary covariances (SmallCov::Stationary; Plain, Grad, Loo, Cv, Hindcast): K~ = k(X, X) + sn~ I for the RBF / Matern-5/2 kernel with one length
+// scale or one per feature (ARD).  A set's A holds the raw rows [X ; Xs], its lam is ignored.  smallgp_build_stationary stages u = x / l_k (the IEEE
+// division, as ard_stage_kernel) ch features at a time and adds (u_ik - u_jk)^2 onto the running squared distance in ascending k -- exact zeros on the
+// diagonal and for duplicate rows, and the same bits whatever the chunk --, then one pass maps sq -> k~ with cov_from_sq at unit length scale.  From
+// there on the fit, the epilogue and the Loo / Cv / Hindcast tails are the factored flavours' own statements: they read K~, L~, X, z and y alone.
+// Grad (4 outputs, and grad [nprob][ldg]): value + exact gradient of the profiled nlML in all N + 1 directions (ardgrad.hpp's formula),
+//     d nlML / d log l_k = sum_{i>j} W_ij h_ij (u_ik - u_jk)^2,   W = K~^-1 - a~ a~^T / sigma_f,   d nlML / d log sn~ = sn~ (tr K~^-1 - a~.a~ / sigma_f) / 2 :
+// sq is formed again into the strict UPPER triangle of Kp (zero from the build on: neither the column Cholesky nor the in-place inverse writes there),
+// every entry is replaced by E_ij = (sum_{k >= i} X(k,i) X(k,j) - a~_i a~_j / sigma_f) h_ij, and one more pass over the re-staged chunks sums
+// g_k = sum_{i>j} E_ij (u_ik - u_jk)^2, every thread over its own pairs in a fixed order, then smallgp_allsum.  One common scale: the sum of the g_k in
+// ascending k.  The score gradients are not built for this covariance: their b_c = X a_c contraction rests on the factored form.
+//
 // NT = threads per workgroup: 256 (four wavefronts per fit) is the default at every order; NT = 64 (one wavefront per fit, every
 // barrier of the column loop a wave-local no-op) is kept as a measurement switch ("small_nt64") -- on the reference-size grid it
 // is SLOWER (1.71 vs 1.02 ms for 48 000 fits of n = 6 .. 45): the rank-1 updates have ~n^2/2 elements, enough for four waves,
@@ -78,6 +90,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ardgrad.hpp"
 #include "blockcv.hpp"
 #include "smallgp_layout.hpp"
 
@@ -105,6 +118,12 @@ struct SmallExtras {
   int block, gap;          // Cv, CvGrad
   int lead, min_train;     // Hindcast
   int crit;                // LooGrad, HindcastGrad, CvGrad: the score that is differentiated, 0 = nlpd, 1 = sse (SIGP_LOO_NLPD / SIGP_LOO_SSE)
+  // SmallCov::Stationary alone
+  KParams kp;              // make_kparams(kernel id, 1.0, ...): the covariance function at unit length scale
+  const double* scales;    // per-feature length scales [nprob][ldell]; nullptr: one scale per fit, SmallProb::ell
+  int ldell;
+  int ldg;                 // Grad: the pitch of grad
+  double* grad;            // Grad: [nprob][ldg], d/d log l_0 .. l_{N-1} (one scale: d/d log l), then d/d log sn~
 };
 
 // one workgroup's fit: its sizes, its pieces in LDS and this thread's place in the 16-wide element mapping
@@ -178,6 +197,56 @@ __device__ __forceinline__ void smallgp_build(const SmallFit& w, const SmallSet&
   __syncthreads();
 }
 
+// the chunk's scales into wk and u = x / l_k of the first `rows` rows of A into Ac (the IEEE division, as ard_stage_kernel); a barrier ahead and one behind
+template <int NT>
+__device__ __forceinline__ void smallgp_stage_u(const SmallFit& w, const SmallProb& pb, const double* __restrict__ A, const double* __restrict__ ls, int k0, int kc,
+                                                int rows) {
+  __syncthreads();
+  if (w.tid < kc) w.wk[w.tid] = ls ? ls[k0 + w.tid] : pb.ell;
+  __syncthreads();
+  for (int e = w.tid; e < rows * kc; e += NT) {
+    const int r = e / kc, k = e - r * kc;
+    w.Ac[r * w.lda + k] = A[(long)r * w.N + k0 + k] / w.wk[k];
+  }
+  __syncthreads();
+}
+
+// K~ (lower), k~*, k~** = 1 of a stationary covariance (kp: the kernel at unit length scale; ls: this fit's per-feature scales, nullptr: pb.ell for
+// every feature): the squared distances of the scaled rows by direct differences, every entry one running sum in ascending k across the chunks, then
+// cov_from_sq; sn~ on the diagonal and y in row n as smallgp_build
+template <int NT>
+__device__ __forceinline__ void smallgp_build_stationary(const SmallFit& w, const SmallProb& pb, const KParams& kp, const double* __restrict__ A,
+                                                         const double* __restrict__ ls, const double* __restrict__ y) {
+  constexpr int TY = NT / 16;
+  const int n = w.n, N = w.N, m = w.m, ldk = w.ldk, lda = w.lda, ch = w.ch, tid = w.tid, tx = w.tx, ty = w.ty;
+  double *Kp = w.Kp, *Ac = w.Ac;
+  for (int e = tid; e < w.R * ldk; e += NT) Kp[e] = 0.0;
+  if (tid < SM_MMAX) w.kss[tid] = 1.0;
+  for (int k0 = 0; k0 < N; k0 += ch) {
+    const int kc = min(ch, N - k0);
+    smallgp_stage_u<NT>(w, pb, A, ls, k0, kc, n + m);       // its first barrier publishes the zeros
+    for (int i = ty; i < n + m; i += TY) {
+      const int krow = i < n ? i : i + 1;               // test rows sit below the y row
+      const double* ai = Ac + i * lda;
+      const int jmax = i < n ? i : n - 1;
+      for (int j = tx; j <= jmax; j += 16) {
+        const double* aj = Ac + j * lda;
+        double acc = Kp[krow * ldk + j];
+        for (int k = 0; k < kc; ++k) { const double d = ai[k] - aj[k]; acc = fma(d, d, acc); }
+        Kp[krow * ldk + j] = acc;
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = ty; i < n + m; i += TY) {
+    const int krow = i < n ? i : i + 1;
+    const int jmax = i < n ? i : n - 1;
+    for (int j = tx; j <= jmax; j += 16) Kp[krow * ldk + j] = cov_from_sq(kp, Kp[krow * ldk + j]) + (i == j ? pb.sn : 0.0);
+  }
+  for (int i = tid; i < n; i += NT) Kp[n * ldk + i] = y[i];
+  __syncthreads();
+}
+
 // Right-looking column Cholesky, one column per step, of the leading ncol columns of P [nrow][ld] (lower): rows ncol.. ride along and
 // come out as L^-1 times themselves.  A non-positive or NaN pivot is replaced by 1 and the first one's 1-based index (LAPACK's info)
 // recorded in *bad, which the caller has zeroed.
@@ -203,9 +272,9 @@ __device__ __forceinline__ void smallgp_col_cholesky(double* P, int ld, int ncol
   }
 }
 
-// sigma_f, nlML, the test points' means and variances (north/June1st.py:267-268, 246, 276-277); o = this fit's row of `out`, mean / var
+// sigma_f, nlML, the test points' means and variances (north/June1st.py:267-268, 246, 276-277); o = this fit's row of `out` (OW doubles), mean / var
 // its rows.  Returns info; zz = z.z and sf = sigma_f on every thread.
-template <int NT, SmallFlavour F>
+template <int NT, int OW>
 __device__ __forceinline__ int smallgp_fit_epilogue(const SmallFit& w, const SmallProb& pb, const int* s_info, double* o, double* mean, double* var,
                                                     double& zz, double& sf) {
   const int n = w.n, ldk = w.ldk, tid = w.tid;
@@ -225,7 +294,7 @@ __device__ __forceinline__ int smallgp_fit_epilogue(const SmallFit& w, const Sma
       o[3] = sf * pb.sn;
     } else {
       o[0] = inf; o[1] = inf; o[2] = (double)info; o[3] = inf;
-      for (int k = 4; k < small_out_width(F); ++k) o[k] = inf;          // north/June1st.py:254-256
+      for (int k = 4; k < OW; ++k) o[k] = inf;          // north/June1st.py:254-256
     }
   }
   for (int j = 0; j < w.m; ++j) {
@@ -528,6 +597,69 @@ __device__ __forceinline__ void smallgp_tail_grad(const SmallFit& w, const Small
   }
 }
 
+// after smallgp_invert: the exact gradient of the profiled nlML of a stationary covariance in all N + 1 directions into g (ls: per-feature scales,
+// g[0 .. N-1] = d/d log l_k, g[N] = d/d log sn~; ls = nullptr: g[0] = d/d log l, g[1] = d/d log sn~).  The strict upper triangle of Kp holds sq, then E.
+template <int NT>
+__device__ __forceinline__ void smallgp_tail_grad_stationary(const SmallFit& w, const SmallProb& pb, const KParams& kp, const double* __restrict__ A,
+                                                             const double* __restrict__ ls, double sf, double* __restrict__ g) {
+  constexpr int TY = NT / 16;
+  const int n = w.n, N = w.N, ldk = w.ldk, lda = w.lda, ch = w.ch, tid = w.tid, tx = w.tx, ty = w.ty;
+  double *Kp = w.Kp, *Ac = w.Ac, *at = w.at;
+  smallgp_atilde<NT>(w);
+  double t0 = 0.0, q0 = 0.0;
+  for (int e = tid; e < n * n; e += NT) {
+    const int i = e / n, j = e - i * n;
+    if (j <= i) { const double xe = Kp[i * ldk + j]; t0 = fma(xe, xe, t0); }
+  }
+  // sq again, as the build summed it, into Kp(j, i), j < i
+  for (int k0 = 0; k0 < N; k0 += ch) {
+    const int kc = min(ch, N - k0);
+    smallgp_stage_u<NT>(w, pb, A, ls, k0, kc, n);           // its first barrier publishes a~
+    for (int i = ty; i < n; i += TY) {
+      const double* ai = Ac + i * lda;
+      for (int j = tx; j < i; j += 16) {
+        const double* aj = Ac + j * lda;
+        double acc = Kp[j * ldk + i];
+        for (int k = 0; k < kc; ++k) { const double d = ai[k] - aj[k]; acc = fma(d, d, acc); }
+        Kp[j * ldk + i] = acc;
+      }
+    }
+  }
+  for (int i = tid; i < n; i += NT) q0 = fma(at[i], at[i], q0);
+  __syncthreads();                                          // sq is complete: the next pass maps the entries to other threads
+  // E_ij = ([K~^-1]_ij - a~_i a~_j / sigma_f) h_ij over its own sq: the entry's thread reads the lower triangle (X) and a~ alone
+  const double isf = 1.0 / sf;
+  for (int e = tid; e < n * n; e += NT) {
+    const int i = e / n, j = e - i * n;
+    if (j < i) {
+      double p = 0.0;
+      for (int k = i; k < n; ++k) p = fma(Kp[k * ldk + i], Kp[k * ldk + j], p);
+      Kp[j * ldk + i] = fma(-at[i] * at[j], isf, p) * ard_h_from_sq(kp.kernel_id, Kp[j * ldk + i]);
+    }
+  }
+  const double T0 = smallgp_allsum<NT>(t0, w.red);
+  const double Q0 = smallgp_allsum<NT>(q0, w.red);
+  double common = 0.0;
+  for (int k0 = 0; k0 < N; k0 += ch) {
+    const int kc = min(ch, N - k0);
+    smallgp_stage_u<NT>(w, pb, A, ls, k0, kc, n);           // its first barrier: E is complete, the last chunk's readers are done
+    for (int c = 0; c < kc; ++c) {
+      double acc = 0.0;
+      for (int e = tid; e < n * n; e += NT) {
+        const int i = e / n, j = e - i * n;
+        if (j < i) { const double d = Ac[i * lda + c] - Ac[j * lda + c]; acc = fma(Kp[j * ldk + i] * d, d, acc); }
+      }
+      const double gk = smallgp_allsum<NT>(acc, w.red);
+      if (ls) { if (tid == 0) g[k0 + c] = gk; }
+      else common += gk;
+    }
+  }
+  if (tid == 0) {
+    if (!ls) g[0] = common;
+    g[ls ? N : 1] = 0.5 * pb.sn * (T0 - Q0 * isf);
+  }
+}
+
 // ---- the score gradients (LooGrad, HindcastGrad, CvGrad) ----------------------------------------------------------------------------------------
 
 // dw of the chunk's features into wk and the chunk's raw columns into Ac (as the Grad tail stages them), then Bc(i, c) = sum_{k <= i} X(i, k) Ac(k, c);
@@ -761,7 +893,7 @@ __device__ __forceinline__ void smallgp_tail_cv_grad(const SmallFit& w, const Sm
   if (tid == 0) { o[6] = pb.ell * G1; o[7] = pb.sn * G0; }
 }
 
-template <int NT, SmallFlavour F>
+template <int NT, SmallFlavour F, SmallCov C = SmallCov::Factored>
 __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict__ sets, const SmallProb* __restrict__ probs,
                                                       const double* __restrict__ Apool, const double* __restrict__ ypool,
                                                       const double* __restrict__ lampool, int ch, double* __restrict__ out,
@@ -782,14 +914,28 @@ __global__ __launch_bounds__(NT) void smallgp_kernel(const SmallSet* __restrict_
   const double* A = Apool + st.a_off;
   const double* lam = lampool + st.lam_off;
   const double* y = ypool + st.y_off;
-  double* o = out + (long)blockIdx.x * small_out_width(F);
+  constexpr int OW = small_out_width(F, C);
+  double* o = out + (long)blockIdx.x * OW;
+  const double* ls = nullptr;        // Stationary: this fit's per-feature scales
+  if constexpr (C == SmallCov::Stationary) ls = x.scales ? x.scales + (long)blockIdx.x * x.ldell : nullptr;
 
   if (w.tid == 0) s_info = 0;
-  smallgp_build<NT>(w, st, pb, A, lam, y);
+  if constexpr (C == SmallCov::Stationary) smallgp_build_stationary<NT>(w, pb, x.kp, A, ls, y);
+  else smallgp_build<NT>(w, st, pb, A, lam, y);
   smallgp_col_cholesky<NT>(w.Kp, w.ldk, w.n, w.R, &s_info, w.tid, w.tx, w.ty);
   double zz, sf;
-  const int info = smallgp_fit_epilogue<NT, F>(w, pb, &s_info, o, mean + (long)blockIdx.x * mstride, var + (long)blockIdx.x * mstride, zz, sf);
-  if constexpr (F != SmallFlavour::Plain) {
+  const int info = smallgp_fit_epilogue<NT, OW>(w, pb, &s_info, o, mean + (long)blockIdx.x * mstride, var + (long)blockIdx.x * mstride, zz, sf);
+  if constexpr (C == SmallCov::Stationary && F == SmallFlavour::Grad) {
+    static_assert(NT == 256, "the stationary flavours are built at four wavefronts per fit");
+    double* g = x.grad + (long)blockIdx.x * x.ldg;
+    if (info != 0) {                 // uniform
+      for (int k = w.tid; k <= (ls ? w.N : 1); k += NT) g[k] = __builtin_huge_val();
+      return;
+    }
+    smallgp_invert<NT>(w);
+    smallgp_tail_grad_stationary<NT>(w, pb, x.kp, A, ls, sf, g);
+  } else if constexpr (F != SmallFlavour::Plain) {
+    static_assert(C == SmallCov::Factored || !small_is_score_grad(F), "the score gradients rest on the factored form");
     if (info != 0) return;           // uniform
     double* rmean = x.row_mean + (long)blockIdx.x * x.pitch;
     double* rvar = x.row_var + (long)blockIdx.x * x.pitch;

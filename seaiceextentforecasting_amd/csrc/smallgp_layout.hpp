@@ -29,12 +29,19 @@ constexpr long SM_LDS_MAX = 160 * 1024 - 64;   // bytes of dynamic LDS one workg
 //   LooGrad / HindcastGrad / CvGrad   what Loo / Hindcast / Cv form, then the derivatives of one of the two scores w.r.t. (log l, log sn~)
 enum class SmallFlavour { Plain, Grad, Loo, Cv, Hindcast, LooGrad, HindcastGrad, CvGrad };
 
+// Where K~ comes from: Factored, the reference's own X Sigma~ X^T as A diag(w) A^T (smallgp.hpp's header), or Stationary, the RBF / Matern-5/2
+// kernel of the raw rows with one length scale or one per feature.  Stationary has Plain, Grad, Loo, Cv and Hindcast, in the factored flavours'
+// own layout: SmallLayout does not ask which.
+enum class SmallCov { Factored, Stationary };
+
 // does the flavour differentiate a row score?
 __host__ __device__ constexpr bool small_is_score_grad(SmallFlavour f) {
   return f == SmallFlavour::LooGrad || f == SmallFlavour::HindcastGrad || f == SmallFlavour::CvGrad;
 }
 // doubles per fit of `out`
 __host__ __device__ constexpr int small_out_width(SmallFlavour f) { return f == SmallFlavour::Plain ? 4 : f == SmallFlavour::Grad || small_is_score_grad(f) ? 8 : 6; }
+// ... of the covariance kind c: the stationary Grad flavour writes its N + 1 derivatives into an array of their own
+__host__ __device__ constexpr int small_out_width(SmallFlavour f, SmallCov c) { return c == SmallCov::Stationary && f == SmallFlavour::Grad ? 4 : small_out_width(f); }
 // does the flavour write a prediction per training row (mean / var [nprob][pitch]) and the scores out[4], out[5]?
 __host__ __device__ constexpr bool small_has_rows(SmallFlavour f) {
   return f == SmallFlavour::Loo || f == SmallFlavour::Cv || f == SmallFlavour::Hindcast || small_is_score_grad(f);

@@ -1504,6 +1504,81 @@ class GPR:
         return bfgs_lockstep(lambda t: self.small_cv_score_batch(t, block, gap=gap, criterion=criterion, sigma_f=sigma_f, expm=expm), th0, maxiter=maxiter,
                              gtol=gtol, ftol=ftol, max_step=max_step)
 
+    def upload_small_ard(self, X, y, Xs=None):
+        """Stage data sets of at most 128 rows for the one-workgroup kernel's RBF / Matern-5/2 flavours (``SmallStationaryBatch``): X / y / Xs
+        are sequences of ragged data sets or arrays X [B, n, d], y [B, n], Xs [B, m, d] (m <= 8).  They stay resident for
+        ``small_nlml_ard_batch`` / ``optimize_small_ard_batch``; what ``upload_batch`` staged for the blocked engine is untouched."""
+        from .smallstationary import SmallStationaryBatch
+        if isinstance(X, np.ndarray) and X.ndim == 2:
+            X, y, Xs = [X], [y], None if Xs is None else [Xs]
+        B = len(X)
+        Xs = [None] * B if Xs is None else list(Xs)
+        if len(y) != B or len(Xs) != B:
+            raise ValueError("X, y and Xs must have one entry per data set (%d)" % B)
+        sb = SmallStationaryBatch(self)
+        self._small_k_ids = [sb.add_dataset(X[b], y[b], Xs[b]) for b in range(B)]
+        self._small_k = sb
+        sb.upload()
+
+    def small_nlml_ard_batch(self, theta, first=0, grad="exact", sets=None):
+        """``nlml_ard_batch`` at the application's own size: the profiled nlML and its exact gradient for many fits in ONE launch, one
+        workgroup per fit (``sigp_small_run_k_grad``), on the data sets staged by ``upload_small_ard`` (RBF / Matern-5/2, fp64, n <= 128).
+        theta [F, p]: row i is (log l_1 .. log l_N, log sn~) of its data set (p = N + 1, all sets named sharing N) or (log l, log sn~), one
+        common scale (p = 2); fit i uses data set (first + i) % B or ``sets[i]`` -- several fits may share a data set (several starts).
+        Returns (nlml [F], grad [F, p] or None); +inf in the value and every gradient entry where K~ is not SPD or exp(theta) is not a
+        finite positive number with a finite reciprocal, the neighbours unaffected."""
+        _check_grad(grad)
+        sb = getattr(self, "_small_k", None)
+        if sb is None:
+            raise RuntimeError("small_nlml_ard_batch: stage the data sets with upload_small_ard(X_list, y_list) first")
+        theta = L.f64(np.atleast_2d(theta), 2)
+        F, p = theta.shape
+        B = len(self._small_k_ids)
+        ds = [self._small_k_ids[(first + i) % B if sets is None else int(sets[i])] for i in range(F)]
+        Ns = {sb._data[d][0].shape[1] for d in ds}
+        if p != 2 and (len(Ns) != 1 or p != next(iter(Ns)) + 1):
+            raise ValueError("theta must be [F, N + 1] (log l_1 .. log l_N, log sn~) for data sets sharing N, or [F, 2] (log l, log sn~); got %s for N in %s"
+                             % (theta.shape, sorted(Ns)))
+        with np.errstate(over="ignore", divide="ignore"):
+            e = np.exp(theta)
+            ok = np.all(np.isfinite(e), axis=1) & np.all(e[:, :-1] > 0, axis=1) & np.all(np.isfinite(1.0 / e[:, :-1]), axis=1)
+        val, g = np.full(F, np.inf), np.full((F, p), np.inf)
+        sb.clear_fits()
+        ran = np.flatnonzero(ok)
+        for i in ran:
+            sb.add_fit(ds[i], e[i, :-1], e[i, -1])
+        if len(ran):
+            r = sb.run(grad=grad is not None)
+            val[ran] = r["nlml"]
+            if grad is not None:
+                g[ran, :-1] = r["grad_ell"][:, :p - 1]
+                g[ran, -1] = r["grad_sn"]
+                g[~np.isfinite(val)] = np.inf
+        return val, (g if grad is not None else None)
+
+    def optimize_small_ard_batch(self, X, y, theta0, ard=True, criterion="nlml", maxiter=50, gtol=1e-5, ftol=1e-10, max_step=2.0):
+        """``optimize_batch(ard=True)`` at the application's own size: MLII over one length scale per feature (``ard=False``: one common
+        scale) and the noise for EVERY data set at once, X / y sequences of data sets of n <= 128 rows sharing N features (or X [B, n, N],
+        y [B, n]).  Lockstep BFGS (``optim.bfgs_lockstep``) over ``small_nlml_ard_batch``: each round is ONE launch, one workgroup per
+        (data set, start), value and exact gradient formed in LDS.  ``theta0`` is [F, N + 1], [N + 1], [F, 2] or [2] (the common log l is
+        repeated for every feature); F = S B rows are S starts per data set, start i on data set i % B, and all F results come back.
+        Returns dict(x [F, N + 1] or [F, 2], fun [F], jac, nit [F], converged [F], nfev = launches).  RBF / Matern-5/2, fp64.  The
+        validation scores have no gradient in the one-workgroup kernel for these covariances: the blocked engine minimises them
+        (``optimize_ard_batch``, ``optimize_cv_batch``, ``optimize_hindcast_batch``)."""
+        from .optim import bfgs_lockstep
+        if criterion != "nlml":
+            raise ValueError("optimize_small_ard_batch minimises 'nlml': the one-workgroup kernel has no score gradients for the RBF / Matern kernels "
+                             "(the leave-one-out scores: optimize_ard_batch, the leave-block-out scores: optimize_cv_batch, the hindcast scores: optimize_hindcast_batch)")
+        self._require_ard_engine()
+        Xl = list(X)
+        Ns = {np.shape(x)[-1] for x in Xl}
+        if len(Ns) != 1:
+            raise ValueError("optimize_small_ard_batch: all data sets share the number of features (got %s)" % sorted(Ns))
+        N, B = next(iter(Ns)), len(Xl)
+        th0 = self._starts(theta0, B, N + 1, N) if ard else self._starts(theta0, B, 2)
+        self.upload_small_ard(Xl, list(y))
+        return bfgs_lockstep(lambda t: self.small_nlml_ard_batch(t, grad="exact"), th0, maxiter=maxiter, gtol=gtol, ftol=ftol, max_step=max_step)
+
     def nlml_grid(self, X, y, ells, sns, concurrency=2, group=8, M=None):
         """nlML on the (l, sn~) grid for one data set -- the offline 20x20 search implied by
         north/June1st.py:210-211 (``ells = LGRID, sns = SGRID`` with the reference kernel reproduces it: one launch,
