@@ -135,6 +135,41 @@ int sigp_predict(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, doub
 #define SIGP_MAX_COV 8192
 int sigp_predict_cov(sigp_handle* h, const double* Xs, int64_t m, int64_t ldxs, int noise, double* mean, double* cov, int64_t ldc);
 
+/* Inducing-point (sparse) GP regression for n past the dense limit: the DTC predictive with Titsias' collapsed variational bound ("SGPR").
+ * K = sigma_f (k + sn~ I) with k the unit-variance RBF or Matern-5/2 covariance, data X [n][ldx] and y [n], m inducing points Z [m][ldz],
+ * jitter eps >= 0, sn~ > 0; sigma_f is profiled as in the dense fit.  Whitened form (never the normal equations sn~ K_mm + K_mn K_nm, which
+ * square the conditioning):
+ *     L  = chol(k(Z,Z) + eps I)                     m x m
+ *     V  = L^-1 k(Z,X)                              m x n, never held whole: chunks of "sparse_chunk" columns, ascending
+ *     B  = sn~ I + V V^T,  L_B = chol(B)            m x m
+ *     b  = V y,  w = L_B^-1 b,  t = |V|_F^2,  yy = y^T y
+ *     sigma_f = (yy - w^T w) / (sn~ n)
+ *     1/2 log|Q~ + sn~ I| = 1/2 (n - m) log sn~ + sum log diag(L_B)
+ *     nlml  = n/2 + 1/2 log|Q~ + sn~ I| + n/2 log sigma_f + n/2 log 2 pi        (the dense fit's expression with the DTC determinant)
+ *     bound = nlml + (n - t) / (2 sn~)                                            (the collapsed bound: >= nlml, equal when Z = X, eps = 0;
+ *                                                                                  n - t is summed as the column deficits 1 - |V[:, j]|^2)
+ * and at a new point x*, with p = L^-1 k(Z,x*), q = L_B^-1 p:
+ *     mean = q^T w,   var = sigma_f (1 + sn~ - p^T p + sn~ q^T q)                (the noise included, as in sigp_predict)
+ * X, y, Z, Xs are HOST pointers; X and y are streamed chunk by chunk.  sigp_set_train and the handle's dense state are not involved: a sparse
+ * fit clears built / factored / fitted, so sigp_predict, sigp_loo, ... refuse as before any fit, and a later dense fit returns what a fresh
+ * handle returns (sigp_sparse_predict then refuses).  nell = 1: isotropic length scale ell[0]; nell = d: per-feature scales -- the chunks, Z
+ * and Xs are divided by them while they are staged and the kernel runs at unit length scale (the bits of the isotropic fit at ell = 1 on
+ * pre-divided inputs).  kernel_id: SIGP_KERNEL_RBF or SIGP_KERNEL_MATERN52.  n < m is legal.  out [4] = { sigma_f, nlml, bound, info }.
+ * SIGP_BAD_ARG (the limit is named in sigp_last_error): an fp32 handle, the reference kernel, nell not 1 or d, a length scale or sn~ <= 0,
+ * jitter < 0, m outside 1 .. SIGP_SPARSE_MAX_INDUCING, n < 1.  SIGP_NOT_SPD: k(Z,Z) + eps I (duplicate inducing points without jitter) or B
+ * is not positive definite; out = { inf, inf, inf, pivot }; the handle stays usable.
+ * Every sum has one chain of additions in ascending chunk order (no atomics): the same bits on every run; another sparse_chunk is another
+ * summation order (agreement to rounding).  Cost about 2 n m^2 flops on the matrix pipe + n m covariances; device memory
+ * 8 (2 (m_pad + 128) m_pad + m_pad chunk + chunk (dp + ldx + 1)) bytes.  Device work is accounted under SIGP_KC_KBUILD (k(Z,Z), k(Z,X_c)),
+ * SIGP_KC_TRSM (the whitening), SIGP_KC_SYRK128 (V_c V_c^T) and the factorisations' own classes.
+ * Not covered: gradients, optimising Z, FITC, fp32, lockstep batches, sharded fits, the reference kernel, predict_cov / loo / cv / hindcast. */
+#define SIGP_SPARSE_MAX_INDUCING 8192
+int sigp_sparse_fit(sigp_handle* h, int kernel_id, const double* ell, int64_t nell, double sn_tilde, double jitter,
+                    const double* X, int64_t n, int64_t d, int64_t ldx, const double* y,
+                    const double* Z, int64_t m, int64_t ldz, double* out /* [4]: sigma_f, nlml, bound, info */);
+/* mean [ms], var [ms] at the rows of Xs [ms][ldxs >= d] (host) from the last sigp_sparse_fit: lockstep groups of up to 16 chunks of 128 points. */
+int sigp_sparse_predict(sigp_handle* h, const double* Xs, int64_t ms, int64_t ldxs, double* mean, double* var);
+
 /* Fused hot path: build -> potrf -> fit -> predict_ride with one host synchronisation.
  * Sigma may be NULL unless kernel_id == SIGP_KERNEL_NETDIFFUSION.
  * out[4] = { sigma_f, nlml, (double)info, sigma_n };  mean/var [m_ride] may be NULL when m_ride == 0. */
@@ -227,7 +262,9 @@ int sigp_detrend(sigp_handle* h, const double* data, int64_t P, int64_t T, int64
 
 /* named scalars of the last operation: "refine_residual" (fp32 engine: max|y - K~ alpha~| / max|y| after the last refinement
  * step), "matrix_bytes" (device bytes held by this handle's matrix / factor buffers), "cov_slices" (the K slices the last sigp_predict_cov
- * ran its covariance product with: what "cov_slices" = 0 chose), "dist_*" (see sigp_dist_fit). */
+ * ran its covariance product with: what "cov_slices" = 0 chose), "sparse_factor_a_ms" / "sparse_chunks_ms" / "sparse_factor_b_ms" (host clock of
+ * the three phases of the last sigp_sparse_fit, each closed by a synchronisation: staging Z and factoring k(Z,Z) + eps I; the chunk loop;
+ * assembling and factoring B), "dist_*" (see sigp_dist_fit). */
 int sigp_get_stat(sigp_handle* h, const char* name, double* value);
 
 /* K7 (explicit): alpha~ = K~^-1 y  [n]  (north/June1st.py:266; alpha of :271 is alpha~/sigma_f). */
@@ -763,6 +800,8 @@ int sigp_synchronize(sigp_handle* h);
  *   cov_slices [0]        sigp_predict_cov: K slices of the covariance product Z Z^T (one workgroup per 128 x 128 tile pair and slice): 0 = auto, the
  *                         smallest count that gives every CU two workgroups (capped by the n_pad / 128 block columns and by 1 GiB of partial
  *                         tiles); 1 .. n_pad / 128 = fixed (1: no partials, one workgroup walks the whole K of its tile)
+ *   sparse_chunk [4096]   sigp_sparse_fit: rows of X per chunk (a multiple of 128 in 128 .. 65536; the last chunk may be shorter): the K of the
+ *                         accumulation V_c V_c^T and the width of the whitening's products; V_c takes 8 m_pad sparse_chunk bytes
  *   cv_slices [0]         sigp_cv / sigp_cv_batch: K slices of the strip product U_S U_S^T (one workgroup per fold, slice and member): 0 = auto, the
  *                         smallest count that gives every CU two workgroups from one member's folds (at most 32; the same for a fit and for a lockstep group); otherwise the count, clipped to the 32-column stages
  *                         of the fit (1: one workgroup walks the whole strip); sigp_get_stat "cv_slices" = what the last call ran with

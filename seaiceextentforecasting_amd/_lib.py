@@ -14,6 +14,7 @@ KERNEL_IDS = {"netdiffusion": 0, "rbf": 1, "matern52": 2}
 KCLASS = {"kbuild": 0, "diag": 1, "trsm": 2, "update_small": 3, "syrk128": 4, "epilogue": 5, "small": 6, "mlii": 7}
 MAX_RIDE = 127
 MAX_COV = 8192                            # SIGP_MAX_COV: test points of one sigp_predict_cov call
+SPARSE_MAX_INDUCING = 8192                # SIGP_SPARSE_MAX_INDUCING: inducing points of one sigp_sparse_fit
 LOO_MODES = {"refit": 0, "fixed": 1}       # SIGP_LOO_REFIT / SIGP_LOO_FIXED
 CV_MAX_WINDOW, CV_SMALL_MAX_WINDOW = 128, 32   # SIGP_CV_MAX_WINDOW / SIGP_CV_SMALL_MAX_WINDOW: widest window block + 2 gap of a fold
 LOO_CRITERIA = {"loo_nlpd": "nlpd", "loo_sse": "sse"}   # optimiser criteria -> keys of GPR.loo's result
@@ -44,6 +45,8 @@ SIGNATURES = {
     "sigp_predict_ride": (C.c_int, [_h, _dp, _dp]),
     "sigp_predict": (C.c_int, [_h, _dp, _i64, _i64, _dp, _dp]),
     "sigp_predict_cov": (C.c_int, [_h, _dp, _i64, _i64, C.c_int, _dp, _dp, _i64]),
+    "sigp_sparse_fit": (C.c_int, [_h, C.c_int, _dp, _i64, C.c_double, C.c_double, _dp, _i64, _i64, _i64, _dp, _dp, _i64, _i64, _dp]),
+    "sigp_sparse_predict": (C.c_int, [_h, _dp, _i64, _i64, _dp, _dp]),
     "sigp_fit_predict": (C.c_int, [_h, C.c_int, C.c_double, C.c_double, _dp, _i64, _dp, _dp, _dp]),
     "sigp_fit_batch": (C.c_int, [_h, _i64, C.c_int, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dp, _dp,
                                  C.c_int, _dp, _dp, _dp]),

@@ -37,6 +37,7 @@
 #include "cvard.hpp"
 #include "hindcast.hpp"
 #include "score_layout.hpp"
+#include "sparse.hpp"
 
 using namespace sigp;
 
@@ -145,6 +146,25 @@ struct sigp_handle {
   std::vector<double> fit_res;                // epilogue reductions of the last fit (host copy)
   Slot slots[MAX_SLOTS];
   int nslots = 0;
+  // inducing-point (sparse) fit (sigp_sparse.inc): the factor of k(Z,Z) + eps I in slot spA, the factor of B = sn~ I + V V^T with w = L_B^-1 b as its
+  // solved ride row in slot spB; the staged inducing points [m_pad][dp], the staged chunk [chunk][dp] and its targets, V_c [m_pad][chunk], the
+  // trace-term partials [chunk / 64] + yy, the per-feature divisors [dp], the rows p and q of a prediction group, the chunk parameters of such a group
+  Slot spA, spB;
+  double* spZ = nullptr; long cap_spZ = 0;
+  double* spXc = nullptr; long cap_spXc = 0;
+  double* spY = nullptr; long cap_spY = 0;
+  double* spK = nullptr; long cap_spK = 0;
+  double* spT = nullptr; long cap_spT = 0;
+  double* spDiv = nullptr; long cap_spDiv = 0;
+  double* spP = nullptr; long cap_spP = 0;
+  double* spQ = nullptr; long cap_spQ = 0;
+  KParams* spKps = nullptr;
+  bool sp_fitted = false, sp_ard = false;
+  long sp_m = 0, sp_mpad = 0, sp_d = 0, sp_dp = 0, sp_n = 0;
+  KParams sp_kp{};
+  double sp_sn = 0, sp_sigma_f = 0;
+  double sp_ms[3] = {0, 0, 0};   // host clock of the last sparse fit's phases, each closed by a synchronisation: factor of k(Z,Z), the chunks, factor of B (sigp_get_stat "sparse_*_ms")
+  int opt_sparse_chunk = 4096;   // rows of X per chunk of sigp_sparse_fit (a multiple of 128)
   // batch data (device resident)
   double* bX = nullptr; double* by = nullptr; double* bXs = nullptr;
   long b_count = 0, b_n = 0, b_d = 0, b_dp = 0, b_m = 0, b_npad = 0;
@@ -824,7 +844,7 @@ int trtri_levels(sigp_handle* h, hipStream_t st, const Real* Lm, long ldl, const
 // =====================================================================================================
 extern "C" {
 
-int sigp_version(void) { return 630; }   // 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard; 6.2: sigp_hindcast_grad_ard_batch; 6.3: sigp_small_run_k, _k_grad, _k_loo, _k_cv, _k_hindcast
+int sigp_version(void) { return 640; }   // 6.4: sigp_sparse_fit, sigp_sparse_predict; 4.0: sigp_transport grew scatter / allgather (3.x callers: sigp_dist_init_transport2 with their struct's size); 5.0: sigp_small_run_grad, sigp_small_set_dweights, sigp_dist_init_transport2; 5.1: sigp_loo, sigp_loo_batch, sigp_small_run_loo; 5.2: sigp_predict_cov; 5.3: sigp_loo_grad, sigp_loo_grad_batch; 5.4: sigp_cv, sigp_cv_batch, sigp_small_run_cv; 5.5: sigp_set_length_scales, sigp_nlml_grad_ard; 5.6: sigp_loo_grad_ard; 5.7: sigp_cv_grad_ard; 5.8: sigp_batch_run_ard, sigp_nlml_grad_ard_batch; 5.9: sigp_loo_grad_ard_batch; 6.0: sigp_cv_grad_ard_batch; 6.1: sigp_hindcast, sigp_hindcast_batch, sigp_small_run_hindcast, sigp_hindcast_grad_ard; 6.2: sigp_hindcast_grad_ard_batch; 6.3: sigp_small_run_k, _k_grad, _k_loo, _k_cv, _k_hindcast
 
 // which HIP runtime serves this process (a process that also loads PyTorch-ROCm has two on disk; the first one mapped wins)
 int sigp_runtime_info(char* buf, int64_t len) {
@@ -861,7 +881,9 @@ int sigp_destroy(sigp_handle* h) {
   (void)hipDeviceSynchronize();
   prof_drain(h);
   for (auto& s : h->slots) slot_free(s);
-  double* bufs[] = {h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out, h->sm_ell,
+  slot_free(h->spA); slot_free(h->spB);
+  if (h->spKps) (void)hipFree(h->spKps);
+  double* bufs[] = {h->spZ, h->spXc, h->spY, h->spK, h->spT, h->spDiv, h->spP, h->spQ, h->X, h->y, h->Xs, h->scratchZ, h->T, h->Sig, h->XsA, h->stage, h->bX, h->by, h->bXs, h->gU, h->gK, h->gD, h->gPart, h->gV, h->gSig, h->gT, h->xq, h->rq, h->rpart, h->fpart, h->sm_A, h->sm_y, h->sm_lam, h->sm_dlam, h->sm_out, h->sm_ell,
                     h->covZ, h->covXs, h->covC, h->covPart, h->covRes, h->covTs, h->covK, h->cvPart, h->cvBlk, h->cvVec, h->cvAdj, h->Xraw, h->XsRaw, h->ardDiv, h->ardXc, h->bStage};
   dist_release(h);
   if (h->sm_sets_dev) (void)hipFree(h->sm_sets_dev);
@@ -927,6 +949,10 @@ int sigp_set_option(sigp_handle* h, const char* name, int64_t value) {
   if (!strcmp(name, "cv_slices")) {
     if (value < 0 || value > 4096) return fail(h, SIGP_BAD_ARG, "cv_slices: 0 (auto) or 1 .. 4096 slices required (got %lld)", (long long)value);
     h->opt_cv_slices = (int)value; return SIGP_OK;
+  }
+  if (!strcmp(name, "sparse_chunk")) {
+    if (value < 128 || value > 65536 || value % 128 != 0) return fail(h, SIGP_BAD_ARG, "sparse_chunk: a multiple of 128 in 128 .. 65536 rows required (got %lld)", (long long)value);
+    h->opt_sparse_chunk = (int)value; return SIGP_OK;
   }
   if (!strcmp(name, "loo_grad_tri")) { h->opt_loo_grad_tri = value != 0; return SIGP_OK; }
   if (!strcmp(name, "diag_tiles")) { h->opt_diag_tiles = value != 0; return SIGP_OK; }
@@ -1856,6 +1882,7 @@ int sigp_loo_batch(sigp_handle* h, int64_t first, int64_t count, int kernel_id, 
 #include "sigp_cvardbatch.inc"    // sigp_cv_grad_ard_batch: ... for lockstep groups; the driver it shares with sigp_loo_grad_ard_batch
 #include "sigp_hindcast.inc"   // sigp_hindcast, sigp_hindcast_batch, sigp_hindcast_grad_ard: expanding-window hindcast validation and its exact ARD gradient
 #include "sigp_hindcastbatch.inc"   // sigp_hindcast_grad_ard_batch: ... that gradient for lockstep groups
+#include "sigp_sparse.inc"    // sigp_sparse_fit, sigp_sparse_predict: inducing-point (sparse) regression for n past the dense limit
 #include "sigp_callers.inc"   // sigp_small_*, sigp_corr_tau, sigp_area_sums, sigp_detrend
 
 }  // extern "C"
@@ -1872,6 +1899,9 @@ int sigp_get_stat(sigp_handle* h, const char* name, double* value) {
   if (!h || !name || !value) return SIGP_BAD_ARG;
   if (!strcmp(name, "refine_residual")) { *value = h->refine_resid; return SIGP_OK; }
   if (!strcmp(name, "cov_slices")) { *value = h->cov_slices_used; return SIGP_OK; }
+  if (!strcmp(name, "sparse_factor_a_ms")) { *value = h->sp_ms[0]; return SIGP_OK; }
+  if (!strcmp(name, "sparse_chunks_ms")) { *value = h->sp_ms[1]; return SIGP_OK; }
+  if (!strcmp(name, "sparse_factor_b_ms")) { *value = h->sp_ms[2]; return SIGP_OK; }
   if (!strcmp(name, "cv_slices")) { *value = h->cv_slices_used; return SIGP_OK; }
   if (!strcmp(name, "matrix_bytes")) {
     double b = 0;

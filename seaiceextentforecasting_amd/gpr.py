@@ -284,6 +284,23 @@ class GPR:
         self._check(self._lib.sigp_predict(self._h, L.ptr(Xs), m, Xs.shape[1], L.ptr(mean), L.ptr(var)), "predict")
         return mean, var
 
+    # ---- inducing-point (sparse) regression for n past the dense limit ---------------------------------
+    def sparse_fit(self, X, y, Z, ell, sn_tilde, jitter=1e-8, kind=None):
+        """Inducing-point fit (DTC predictive, Titsias' collapsed bound; ``sigp_sparse_fit``) of ``y`` on ``X`` [n, d] with the inducing
+        points ``Z`` [m, d] (``select_inducing``), m <= 8192 and n as large as host memory holds: X and y are streamed to the device in
+        chunks (option ``sparse_chunk``), about 2 n m^2 flops.  ``ell``: a scalar or a sequence of d per-feature length scales;
+        ``jitter`` is added to the diagonal of k(Z,Z); ``kind``: 'rbf' / 'matern52' (default: the engine's kernel).  Returns
+        ``dict(sigma_f, nlml, bound, n, m)``: the profiled signal variance, the DTC negative log marginal likelihood and the collapsed
+        variational bound (>= nlml).  Raises LinAlgError when k(Z,Z) + jitter I or sn~ I + V V^T is not positive definite.  Nothing of
+        ``fit`` / ``set_data`` is involved: afterwards ``predict`` / ``loo`` / ... refuse as before any fit; ``sparse_predict`` predicts."""
+        from .sparse import sparse_fit
+        return sparse_fit(self, X, y, Z, ell, sn_tilde, jitter=jitter, kind=kind)
+
+    def sparse_predict(self, Xs):
+        """(mean [ms], var [ms]) at the rows of ``Xs`` from the last ``sparse_fit``; var includes the noise, as ``predict``'s."""
+        from .sparse import sparse_predict
+        return sparse_predict(self, Xs)
+
     # ---- joint posterior at new points -------------------------------------------------------------
     def predict_cov(self, Xs, noise=True):
         """(mean [m], cov [m, m]): the joint Gaussian posterior at the rows of ``Xs`` (``sigp_predict_cov``; 1 <= m <= 8192) from the factor on
